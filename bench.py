@@ -22,15 +22,16 @@ import time
 import numpy as np
 import torch
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # before the first GPU call; see embodied_object_detection_amd/__init__.py
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_F32_MFMA_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
+PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X microarchitecture guide: v_mfma_f32_32x32x2_f32, dense
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # same guide: bf16 dense (v_mfma_f32_32x32x16_bf16, 32 cycles per SIMD)
 PEAK_HBM_GBPS = 8000.0
 EPISODE_LEN = 20               # Detic/SMNet/loader.py: episodes of 20 frames; train_mp3d.py:186 passes one episode per call
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs writes at most this much
+DUMP_MASK_PIXELS = 32768       # mask pixels sampled per dumped step (shared by the B frames of a --batch step): at the 300
+                               # detections a frame can return, 300 x 32768 float32 = 39 MB
 
 
 def parse():
@@ -56,7 +57,13 @@ def parse():
                          "B scene objects on their own streams, only the trunk batched (modeling/batched.py)")
     ap.add_argument("--batch", type=int, default=1, help="B independent sequences per GPU in lock-step (BASELINE configs[4]: "
                     "--size 960 960 --grid 512 512 --cell 0.08 --batch 4); a step = B frames")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the Instances the last timed step returned as DIR/<name>.npy (float32 / float64; "
+                         "the masks as a fixed sample of pixel positions + every whole mask's area), for comparing two builds")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def frame_roofline(H: int, W: int, n_prop: float, n_det: float, sec_per_frame: float, math: str, n_mask_rois: float = None) -> dict:
@@ -288,6 +295,32 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def instances_arrays(inst, n_px: int, prefix: str = "") -> dict:
+    """One frame's Instances, as its caller receives them, as host float arrays: pred_boxes [D, 4], scores [D], pred_classes [D].
+    pred_masks (bool [D, H, W]: 491 MB as floats at 300 detections of 640x640) is stored as pred_masks_sample [D, n_px], every
+    mask at the same n_px pixel positions (flattened y * W + x, ascending) drawn without replacement by
+    np.random.default_rng(0), and pred_masks_area [D], the pixel count of every whole mask."""
+    H, W = inst.image_size
+    m = inst.pred_masks.reshape(len(inst), H * W)
+    pos = np.sort(np.random.default_rng(0).choice(H * W, size=min(n_px, H * W), replace=False))
+    return {prefix + "pred_boxes": inst.pred_boxes.tensor.float().cpu().numpy(),
+            prefix + "scores": inst.scores.float().cpu().numpy(),
+            prefix + "pred_classes": inst.pred_classes.float().cpu().numpy(),
+            prefix + "pred_masks_sample": m[:, torch.from_numpy(pos).to(m.device)].float().cpu().numpy(),
+            prefix + "pred_masks_area": m.sum(dim=1).double().cpu().numpy()}
+
+
+def write_dump(out_dir: str, arrays: dict) -> None:
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs, the limit is {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"--dump-outputs: {len(arrays)} arrays, {total} bytes -> {out_dir}")
+
+
 def cpu_baseline(sd, frames, args, budget_s):
     """The CPU oracle (a port: the reference's own CPU mode cannot run) timed on the host cores, SURVEY §8(d)
     protocol scaled to a bounded sample: warm-up frame(s) first (not timed: the first frame has an empty memory and cold
@@ -355,7 +388,8 @@ def relaunch_under_torchrun(args) -> int:
     return subprocess.call(cmd)
 
 
-def run_batched(H, W, map_w, map_h, cell, B, warmup, steps, lockstep="launches", memory_thresh=0.3, concurrent_scenes=0, sd=None) -> dict:
+def run_batched(H, W, map_w, map_h, cell, B, warmup, steps, lockstep="launches", memory_thresh=0.3, concurrent_scenes=0, sd=None,
+                dump_outputs=None) -> dict:
     """configs[4]: B sequences per GPU in lock-step, a step = B frames through the boundary -> the line's fields (single rank)."""
     from embodied_object_detection_amd import setup_cfg
     from embodied_object_detection_amd.checkpoint import synthetic_state_dict
@@ -395,6 +429,11 @@ def run_batched(H, W, map_w, map_h, cell, B, warmup, steps, lockstep="launches",
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     nd = float(np.mean([len(o["instances"]) for ob in outs for o in ob]))
+    if dump_outputs:         # the last timed step = the last frame of each of the B scenes
+        arrays = {}
+        for b, ob in enumerate(outs):
+            arrays.update(instances_arrays(ob[-1]["instances"], DUMP_MASK_PIXELS // B, prefix=f"scene{b}_"))
+        write_dump(dump_outputs, arrays)
     del model, eps, outs
     torch.cuda.empty_cache()
     return {
@@ -410,7 +449,7 @@ def bench_batched(args):
     H, W = args.size
     map_w, map_h = args.grid
     print(json.dumps(run_batched(H, W, map_w, map_h, args.cell, args.batch, args.warmup, args.steps, args.lockstep, args.memory_thresh,
-                                 args.concurrent_scenes)), flush=True)
+                                 args.concurrent_scenes, dump_outputs=args.dump_outputs)), flush=True)
 
 
 def config5_variant(sd, memory_thresh: float) -> dict:
@@ -594,14 +633,16 @@ def main():
         if distributed:
             dist.barrier()
 
-    def run_boundary(fr, lo, hi):
+    def run_boundary(fr, lo, hi, keep_last=None):
         """The reference's call shape (train_mp3d.py:186): `model([episode])` with episodes of 20 frames, `Instances`
-        (boxes, scores, classes, bool masks) materialised for every frame."""
+        (boxes, scores, classes, bool masks) materialised for every frame.  `keep_last`: a list that receives the last frame's."""
         n = 0
         for e0 in range(lo, hi, EPISODE_LEN):
             outs = model([fr[e0:min(hi, e0 + EPISODE_LEN)]])
             n += len(outs)
             assert all(o["instances"].pred_masks.dtype == torch.bool for o in outs)
+            if keep_last is not None:
+                keep_last[:] = [outs[-1]["instances"]]
         return n
 
     def run_enqueue(fr, lo, hi):
@@ -659,12 +700,17 @@ def main():
     # the events of the warm-up frames are dropped inside timed_pass's caller below: remember where the timed ones start
     ev_mark = []
 
+    last_timed = []         # --dump-outputs: the Instances of the last timed step
+
     def run_boundary_marked(fr, lo, hi):
         if lo == args.warmup:
             ev_mark.append(len(ev))
+            return run_boundary(fr, lo, hi, keep_last=last_timed if args.dump_outputs else None)
         return run_boundary(fr, lo, hi)
 
     elapsed = timed_pass(run_boundary_marked, frames, "boundary, resident inputs")
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, instances_arrays(last_timed.pop(), DUMP_MASK_PIXELS, prefix=f"rank{rank}_" if distributed else ""))
     ev = ev[ev_mark[0]:] if ev_mark else ev
     for conv in model.roi_heads.mask_convs:
         conv.event_log = None

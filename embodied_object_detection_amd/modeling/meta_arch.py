@@ -53,8 +53,8 @@ _DET_STREAMS: Dict[Tuple[int, int], torch.cuda.Stream] = {}
 
 def _det_stream(device: torch.device, priority: int) -> torch.cuda.Stream:
     """The detection-pass stream, also ONE per device and process.  A stream per model instance made the frame rate of otherwise
-    identical models bimodal (270 or 200-220 frames/s at 640x640, tools/knob_ab.py): the runtime hands hardware queues out round
-    robin (GPU_MAX_HW_QUEUES), and a later model's stream could land on the queue of one of the chain streams, which serialises
+    identical models bimodal (270 or 200-220 frames/s at 640x640, tools/knob_ab.py): the runtime hands its hardware queues out
+    round robin, and a later model's stream could land on the queue of one of the chain streams, which serialises
     the detection pass with that chain."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     key = (idx, int(priority))

@@ -673,3 +673,42 @@ def test_embodied_predictor_mirrors_the_robot_demo_call(synthetic_sd):
     with pytest.raises(ValueError):
         pred({"image": np.zeros((256, 320, 3), np.uint8), "memory": frames[0]["memory"], "proj_indices": np.zeros((256, 320, 1), np.int32),
               "memory_reset": True, "sequence_name": "x"})
+
+
+def test_bench_dump_outputs_is_the_last_timed_step_and_repeats(tmp_path):
+    """`bench.py --dump-outputs DIR`: float arrays under the 64 MB limit, what the last of the `--steps` timed frames returns through
+    the boundary, and the same bits from a second run with the same arguments (seeded inputs, deterministic kernels)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    H, W, warmup, steps = 128, 160, 2, 3
+    dumps = []
+    for name in ("a", "b"):
+        d = os.path.join(str(tmp_path), name)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--size", str(H), str(W), "--grid", "20", "20", "--cell", "0.5", "--no-variants", "--no-cpu-baseline",
+                            "--dump-outputs", d], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["warmup"] == warmup
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["pred_boxes", "pred_classes", "pred_masks_area", "pred_masks_sample", "scores"] == sorted(b)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    # the same frames through the same boundary in this process: the dump is frame warmup + steps - 1 of bench.py's sequence
+    from embodied_object_detection_amd import build_model
+    from embodied_object_detection_amd.checkpoint import synthetic_state_dict
+    from embodied_object_detection_amd.data.synthetic import SyntheticSequence
+    n = warmup + steps
+    seq = SyntheticSequence(0, H=H, W=W, n_frames=n + 4, map_w=20, map_h=20, cell=0.5, projector=None)
+    model = build_model(_cfg(**{"MODEL.DEVICE": "cuda:0"}), synthetic_state_dict(0))
+    fr = [seq.frame(i) for i in range(n)]
+    model([fr[:warmup]])
+    inst = model([fr[warmup:]])[-1]["instances"]
+    D = len(inst)
+    assert D > 0 and a["pred_boxes"].shape == (D, 4) and a["pred_masks_sample"].shape == (D, min(H * W, 32768))
+    assert np.array_equal(a["pred_boxes"], inst.pred_boxes.tensor.cpu().numpy()) and np.array_equal(a["scores"], inst.scores.cpu().numpy())
+    assert np.array_equal(a["pred_classes"], inst.pred_classes.cpu().numpy().astype(np.float32))
+    assert np.array_equal(a["pred_masks_area"], inst.pred_masks.sum(dim=(1, 2)).cpu().numpy().astype(np.float64))

@@ -4,7 +4,6 @@ sees): 20 back-to-back launches between one pair of events, / 20."""
 import os, sys
 import numpy as np
 import torch
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from embodied_object_detection_amd import ops
 from embodied_object_detection_amd.data.synthetic import SyntheticSequence

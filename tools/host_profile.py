@@ -1,5 +1,5 @@
 import os, sys, time, cProfile, pstats
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from embodied_object_detection_amd import build_model, setup_cfg
 from embodied_object_detection_amd.checkpoint import synthetic_state_dict

@@ -5,8 +5,9 @@
 #   bash tools/profile_round.sh r04
 set -o pipefail
 TAG=${1:-r04}
-cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 O=gpurun_out
+mkdir -p $O
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_640_default.json 2> $O/${TAG}_bench_640_default.log || exit 1
 echo "bench done"
 rocprofv3 --kernel-trace --stats -d $O/prof_${TAG} -o ${TAG} -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-variants --no-cpu-baseline > $O/${TAG}_prof_bench.json 2> $O/${TAG}_prof_bench.log || exit 1

@@ -10,7 +10,6 @@ import sys
 import numpy as np
 import torch
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from embodied_object_detection_amd import build_model, ops, setup_cfg
 from embodied_object_detection_amd.checkpoint import synthetic_state_dict
