@@ -335,7 +335,6 @@ class LockstepScenes:
         k = self._slot
         if self._ev_det[k] is not None:
             cur.wait_event(self._ev_det[k])                     # detection list set k is still read by the pass of RESULT_SETS steps ago
-        update_mem = use_mem or m.always_update_memory
         boxes = prop_boxes
         seg = dict(m_count=prop_count, m_unit=1, m_segments=B, plan_rows=self._pr(R))
         pending = None
@@ -353,7 +352,7 @@ class LockstepScenes:
             feat = self.feat0 if s_i == 0 else self.feat
             st["cls_bb0"](self.h2, B * R, 1, 1, relu=True, out=feat, split=(512, self.hb), **seg)
             last = s_i == rh.num_stages - 1
-            rescore = s_i == 0 and update_mem
+            rescore = s_i == 0      # the memory update's CLIP re-score: for every MEMORY_TYPE, as in the reference (custom_rcnn.py:515,573)
             if rh.fuse_stage_tail and not rh.fold_deltas:
                 # classifier tail + bbox_pred.2 + apply_deltas in one launch, as the single-scene model runs them (roi_heads._cascade)
                 ops.cascade_stage_tail(feat, st["zs"], self.prob, s_i > 0, self.featn0 if s_i == 0 else None, prop_count, R, C1, rh.norm_temp,
@@ -376,13 +375,12 @@ class LockstepScenes:
                 boxes = self.boxes[s_i + 1]
         # memory selection first: the step's critical chain waits for it (custom_rcnn.py:825-875)
         msel = self.mem_selector
-        if update_mem:
-            _, _, _, mem_rows, mem_cnt = msel(prop_boxes, self.mem_scores, prop_count, float(W), float(H), m.cls_score_thresh, 0.5)
-            for b in range(B):
-                if not active[b]:                               # idle slot: no instances -> its state stays as it is
-                    s_raw = torch.cuda.current_stream(dev).cuda_stream
-                    _lib.check(_lib.load().eod_fill_i32(mem_cnt[b:b + 1].data_ptr(), 0, 1, s_raw), "fill")
-                    _lib.check(_lib.load().eod_fill_i32(msel.uniq_count[b:b + 1].data_ptr(), 0, 1, s_raw), "fill")
+        _, _, _, mem_rows, mem_cnt = msel(prop_boxes, self.mem_scores, prop_count, float(W), float(H), m.cls_score_thresh, 0.5)
+        for b in range(B):
+            if not active[b]:                               # idle slot: no instances -> its state stays as it is
+                s_raw = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(_lib.load().eod_fill_i32(mem_cnt[b:b + 1].data_ptr(), 0, 1, s_raw), "fill")
+                _lib.check(_lib.load().eod_fill_i32(msel.uniq_count[b:b + 1].data_ptr(), 0, 1, s_raw), "fill")
         self._mark("cascade+mem_select")
         sel = self.selectors[k]
         det_boxes, det_scores, det_classes, det_rows, det_count = sel(boxes, self.prob, prop_count, float(W), float(H), rh.score_thresh,
@@ -393,7 +391,7 @@ class LockstepScenes:
         post = d["posts"][k]
         if self.trail_detection_pass:
             if self._det_stream is None:
-                self._det_stream = _det_stream(dev, m.det_stream_priority)
+                self._det_stream = _det_stream(dev)
                 self._ev_det = [torch.cuda.Event() for _ in range(RESULT_SETS)]
             ds = self._det_stream
             ds.wait_event(self._ev_box)
@@ -407,21 +405,20 @@ class LockstepScenes:
             self._detection_pass(views, h3, w3, sel, k, H, W, post)
 
         # mask head on the memory instances of all scenes (custom_rcnn.py:573-574, only the proposals 875-880 read), memory write
-        if update_mem:
-            ops.concat_lists(msel.uniq_rows, msel.uniq_count, R, R, B, self.glist_p, self.total_p)
-            self._mask_pass(views, h3, w3, prop_boxes, self.glist_p, self.total_p, B * self.Pcap, R, self.prop_masks, self.pm_bufs,
-                            plan_rois=self.Pcap, tag=("prop", self._step_no))
-            self._mark("prop_masks")
-            follow = m.snapshot_follows_write if m.snapshot_follows_write is not None else m.test_type in ("default", "episodic")
-            wr = d["writer"]
-            if follow and self._f16_valid and not self._dirty_pending:
-                wr(self.featn0, prop_boxes, self.prop_masks, mem_rows, mem_cnt, d["proj"], self.implicit_memory, self.observations,
-                   err=self._err, snapshot=self._mem_f16)
-            else:
-                wr(self.featn0, prop_boxes, self.prop_masks, mem_rows, mem_cnt, d["proj"], self.implicit_memory, self.observations,
-                   dirty=self._dirty, err=self._err)
-                self._dirty_pending = True
-            self._mark("mem_write")
+        ops.concat_lists(msel.uniq_rows, msel.uniq_count, R, R, B, self.glist_p, self.total_p)
+        self._mask_pass(views, h3, w3, prop_boxes, self.glist_p, self.total_p, B * self.Pcap, R, self.prop_masks, self.pm_bufs,
+                        plan_rois=self.Pcap, tag=("prop", self._step_no))
+        self._mark("prop_masks")
+        follow = m.snapshot_follows_write if m.snapshot_follows_write is not None else m.test_type in ("default", "episodic")
+        wr = d["writer"]
+        if follow and self._f16_valid and not self._dirty_pending:
+            wr(self.featn0, prop_boxes, self.prop_masks, mem_rows, mem_cnt, d["proj"], self.implicit_memory, self.observations,
+               err=self._err, snapshot=self._mem_f16)
+        else:
+            wr(self.featn0, prop_boxes, self.prop_masks, mem_rows, mem_cnt, d["proj"], self.implicit_memory, self.observations,
+               dirty=self._dirty, err=self._err)
+            self._dirty_pending = True
+        self._mark("mem_write")
         if self.trail_detection_pass and not trailing:
             cur.wait_event(self._ev_det[k])
         if self.stats_log is not None:

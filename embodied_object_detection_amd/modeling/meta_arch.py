@@ -7,10 +7,10 @@ Mirrors `Detic/detic/modeling/meta_arch/custom_rcnn.py`: `forward` eval branch (
 `CustomRCNN._postprocess` -> detectron2 `detector_postprocess` (579-580).
 
 Call convention: `model(batched_inputs: List[List[dict]]) -> List[dict]`; the module is stateful
-between calls.  A frame is enqueued with no host synchronisation on the current HIP stream plus two scheduling streams
-(box cascade + memory write; next frame's memory-independent trunk) that fork after the proposals and join before the
-frame ends; the only sync per frame is the read-back of the final detection count when the result `Instances` are
-materialised.
+between calls.  A frame is enqueued with no host synchronisation on the current HIP stream plus three scheduling streams
+(box cascade + memory selection + memory write; the coming frames' memory-independent trunk; the detection mask pass + paste,
+which may trail under the next frame of a call) -- or, with `overlap_branches = False`, in order on the current stream alone.
+The only sync per frame is the read-back of the final detection count when the result `Instances` are materialised.
 """
 from __future__ import annotations
 
@@ -40,27 +40,28 @@ PYRAMID_SETS = 6        # current frame, the frame before (its detection pass ma
 
 
 def _sched_streams(device: torch.device) -> Tuple[torch.cuda.Stream, ...]:
-    """(side, look-ahead, main chain, memory selection + write): four high-priority streams.  The device offers two priority levels (0 and -1); the
-    detection pass that trails under the next frame runs at 0, everything latency-bound at -1."""
+    """(side: box cascade + memory selection + memory write, look-ahead trunk, main chain): the high-priority streams.  The device
+    offers two priority levels (0 and -1); the detection pass that trails under the next frame runs at 0, everything latency-bound
+    at -1."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx not in _SCHED_STREAMS:
+        # four, not three: the fourth has no role, it stays because it decides which hardware queue every later stream lands on
         _SCHED_STREAMS[idx] = tuple(torch.cuda.Stream(device=device, priority=-1) for _ in range(4))
     return _SCHED_STREAMS[idx]
 
 
-_DET_STREAMS: Dict[Tuple[int, int], torch.cuda.Stream] = {}
+_DET_STREAMS: Dict[int, torch.cuda.Stream] = {}
 
 
-def _det_stream(device: torch.device, priority: int) -> torch.cuda.Stream:
-    """The detection-pass stream, also ONE per device and process.  A stream per model instance made the frame rate of otherwise
-    identical models bimodal (270 or 200-220 frames/s at 640x640, tools/knob_ab.py): the runtime hands its hardware queues out
-    round robin, and a later model's stream could land on the queue of one of the chain streams, which serialises
-    the detection pass with that chain."""
+def _det_stream(device: torch.device) -> torch.cuda.Stream:
+    """The detection-pass stream (normal priority), also ONE per device and process.  A stream per model instance made the frame
+    rate of otherwise identical models bimodal (270 or 200-220 frames/s at 640x640, tools/knob_ab.py): the runtime hands its
+    hardware queues out round robin, and a later model's stream could land on the queue of one of the chain streams, which
+    serialises the detection pass with that chain."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, int(priority))
-    if key not in _DET_STREAMS:
-        _DET_STREAMS[key] = torch.cuda.Stream(device=device, priority=0 if int(priority) >= 0 else -1)
-    return _DET_STREAMS[key]
+    if idx not in _DET_STREAMS:
+        _DET_STREAMS[idx] = torch.cuda.Stream(device=device, priority=0)
+    return _DET_STREAMS[idx]
 
 
 @META_ARCH_REGISTRY.register()
@@ -90,9 +91,6 @@ class CustomRCNNRecurrent:
         self.pixel_std = [float(v) for v in cfg.MODEL.PIXEL_STD]
         self.mask_threshold = 0.5
         self.training = False
-        # the memory write-back and the 256-proposal mask pass run for every MEMORY_TYPE in the reference
-        # (custom_rcnn.py:515,573); keep that for like-for-like timing
-        self.always_update_memory = True
         # Default: compute the proposal masks only for the proposals the memory update reads (<= 100 unique rows kept by
         # `inference_with_proposals`, custom_rcnn.py:875-880).  The reference runs the mask head on all 256 proposals
         # (custom_rcnn.py:573) and never reads the others; they are not observable through the boundary and every output is
@@ -106,43 +104,26 @@ class CustomRCNNRecurrent:
         # (tests/test_model_gpu.py::test_detection_mask_groups_give_identical_results).  `False` restores the reference-faithful
         # one-ROI-per-detection pass (bench.py reports it beside the headline).
         self.dedup_detection_masks = True
-        # The proposal mask pass (custom_rcnn.py:573) needs only the proposals and the FPN features, not the box cascade: the
-        # cascade's small latency-bound launches (15 FC GEMMs, 3 ROIAligns, the selection sorts) are enqueued on a second,
-        # high-priority HIP stream and run beside the proposal pass's large GEMMs.  The detection mask pass follows on the main
-        # stream after both (the two large passes never share the chip).  Same kernels, same inputs, same results;
-        # `overlap_branches = False` restores one stream.
+        # The frame has two schedules.  `overlap_branches = False`: every launch in order on the current stream (`_frame_in_order`).
+        # True (`_frame_pipelined`): the proposal mask pass (custom_rcnn.py:573) needs only the proposals and the FPN features, not the
+        # box cascade, so the cascade's small latency-bound launches (15 FC GEMMs, 3 ROIAligns, the selection sorts) and the memory
+        # write-back go to a second, high-priority stream beside the pass's large GEMMs; and nothing of frame t+1 depends on frame
+        # t's DETECTION masks (the memory write needs the proposal masks only), so the detection mask pass + post-processing + paste
+        # run on a normal-priority stream of their own, inside `forward([episode])` underneath frame t+1's memory read, tower,
+        # proposal decoding and box cascade (short chains that leave most of the chip idle).  PYRAMID_SETS pyramid sets and
+        # RESULT_SETS detection-list sets make the overlap hazard free.  Same kernels, same inputs, bitwise the same results.
         self.overlap_branches = True
         self._side_stream = None
-        self._ev_props = self._ev_pm = self._ev_box = self._ev_mem = self._ev_sel = self._ev_s0 = None
-        # Look-ahead: the ResNet trunk does not read the memory, so the NEXT frame's bottom-up pass and FPN top-down convs (known from the
-        # inner frame list of `forward`, or passed as `next_frame`) are enqueued on a third stream while this frame's mask passes
-        # run; they write the other of two pyramid buffer sets.
+        self._ev_props = self._ev_pm = self._ev_box = self._ev_mem = self._ev_sel = None
+        # Look-ahead: the ResNet trunk does not read the memory, so the NEXT frames' bottom-up pass and FPN top-down convs (known from
+        # the inner frame list of `forward`, or passed as `next_frame`) are enqueued on a third stream from the start of this frame
+        # on; they write pyramid sets of their own.
         self.prefetch_trunk = True
-        self.lookahead_at_start = True   # start it at the beginning of the frame (True) or once the proposals exist (False)
         self._ev_start = None
         self._trunk_stream = None
         self._ev_trunk = None
         self._prefetched = None      # (image object of the frame, padded H, W)
-        self._pyramid = 0            # which of the two FPN buffer sets the current frame uses
-        self.overlap_memory_write = True    # also the memory selection + write-back, beside the detection mask pass
-        # Cross-frame pipelining inside `forward([episode])`: nothing of frame t+1 depends on frame t's DETECTION masks (the
-        # memory write needs the proposal masks only), so the detection mask pass + post-processing + paste of frame t run on
-        # their own low-priority stream underneath frame t+1's memory read, tower, proposal decoding and box cascade (short
-        # latency-bound chains that leave most of the chip idle).  Three pyramid sets and two detection-list sets make the
-        # overlap hazard free; results are bitwise those of the in-order schedule.
-        self.pipeline_detection_pass = True
-        # may the detection pass of frame t still run when frame t+1 starts?  (False: the frame's chain joins it at the end of the frame)
-        self.trail_detection_pass = True
-        self.det_stream_priority = 0         # 0 = normal, -1 = high (like the chains)
-        self.trunk_stream_priority = -1      # -1 = high (default), 0 = a normal-priority stream of its own
-        # Memory selection right after cascade stage 0 on its own stream (it needs only the stage-0 features) instead of after the
-        # cascade.  Measured (tools/frame_schedule.py, same box): True lets the proposal-mask pass and the memory write finish
-        # early, the next frame then starts while the detection pass still runs and its latency-bound chain is slowed 3x by the
-        # resident GEMM workgroups (5.66 ms/frame); False keeps the detection pass inside its frame (5.52 ms/frame).  A CU mask
-        # on the detection stream (hipExtStreamCreateWithCUMask) would be the remedy; this runtime accepts the call and ignores
-        # the mask (an fp32 matmul on a half-masked stream takes the same time).
-        self.early_memory_selection = False
-        self.memory_selection_first = True     # on the side stream: cascade -> memory selection -> detection selection
+        self._pyramid = 0            # which of the PYRAMID_SETS FPN buffer sets the current frame uses
         # how many coming frames of an episode the look-ahead computes at once (their images are all there when `forward` is
         # called): 2 = the memory-independent trunk + FPN top-down of frames t+1 and t+2 as ONE N = 2 pass every second frame
         # (planned like one image: bitwise the N = 1 results).  Measured at 640x640: the pass costs 1.23 ms per image instead of 1.61
@@ -301,7 +282,7 @@ class CustomRCNNRecurrent:
                 raise RuntimeError("training mode needs a trainer: `modeling.training.Trainer(model, state_dict)` attaches itself to the "
                                    "model; then `model.train(); losses = model(data); trainer.optimizer_step()`")
             return self.trainer.forward_backward_frames(batched_inputs)
-        if self.overlap_branches and self.pipeline_detection_pass:
+        if self.overlap_branches:
             # The frame's own chain (memory read -> tower -> proposals -> proposal masks -> memory write) moves to a HIGH priority
             # stream for the duration of the call: the previous frame's detection pass trails at normal priority, and at equal
             # priority the short chain would queue behind the GEMMs' thousands of workgroups.  The caller's stream is joined on
@@ -334,7 +315,7 @@ class CustomRCNNRecurrent:
                 last = nxt is None and input_seq is batched_inputs[-1]
                 t0 = _time.perf_counter()
                 self.inference_frame(frame, refresh_memory_snapshot=refresh, materialize=False, next_frame=nxt,
-                                     trailing_detection_pass=(not last) and self.trail_detection_pass)
+                                     trailing_detection_pass=not last)
                 pending.append(self._post_ticket())
                 t1 = _time.perf_counter()
                 if len(pending) == RESULT_SETS:
@@ -355,7 +336,7 @@ class CustomRCNNRecurrent:
         cur = torch.cuda.current_stream(self.device)
         P["err_host"].copy_(self._err, non_blocking=True)
         k = self._post_slot
-        if self.overlap_branches and self.pipeline_detection_pass and self._det_stream is not None and self._ev_det[k] is not None:
+        if self.overlap_branches:
             # the detection pass of this frame may still be running on its own stream: the count is copied there, and the ticket's
             # event covers both streams
             ds = self._det_stream
@@ -397,7 +378,7 @@ class CustomRCNNRecurrent:
         if self._trunk_stream is None:
             # high priority like the side stream: its ~75 launches are small and must not queue behind the mask GEMMs' thousands
             # of workgroups
-            self._trunk_stream = _sched_streams(self.device)[1] if self.trunk_stream_priority < 0 else _det_stream(self.device, 1000)
+            self._trunk_stream = _sched_streams(self.device)[1]
             self._ev_trunk = torch.cuda.Event()
         ts = self._trunk_stream
         ts.wait_event(after)
@@ -451,6 +432,43 @@ class CustomRCNNRecurrent:
                 self._refresh_memory_snapshot()
             mem_f16 = self._mem_f16
 
+        coming = [] if next_frame is None else (list(next_frame) if isinstance(next_frame, (list, tuple)) else [next_frame])
+        pre, start_batch, first_ahead = self._claim_lookahead(frame, coming)
+        if start_batch:
+            # the look-ahead may start NOW, beside this frame's memory fusion, tower and proposal decoding (a short latency-bound
+            # chain that leaves most of the chip idle); the host enqueues that chain first so that the main stream never starves
+            if self._ev_start is None:
+                self._ev_start = torch.cuda.Event()
+            self._ev_start.record(torch.cuda.current_stream(self.device))
+        views, shapes, props = self._front(frame, pre, proj, mem_f16)
+        if start_batch:
+            self._enqueue_trunk(start_batch, self._ev_start, first_ahead)
+        self._mem_scores_frame = self._frame_no          # `mem_scores`: written by stage 0 of this frame's cascade
+        if self.overlap_branches:
+            self._frame_pipelined(frame, (H, W), views, shapes, props, proj, trailing_detection_pass)
+        else:
+            self._frame_in_order(frame, (H, W), views, shapes, props, proj)
+
+        P = self._post
+        self.last_stats = {"prop_count": props[2], "det_count": P["count"], "mem_k": self._writer.k_out,
+                           "det_mask_rois": self.roi_heads.last_selector.rep_count if self.dedup_detection_masks else P["count"]}
+        if self.stats_log is not None:      # bench.py: device-side copies of the frame's counters, read after the timed region
+            if self.overlap_branches and trailing_detection_pass:
+                with torch.cuda.stream(self._det_stream):      # the count is written by the trailing detection pass: copy it there
+                    cnt = P["count"].clone()
+            else:
+                cnt = P["count"].clone()
+            self.stats_log.append((props[2].clone(), cnt, self._writer.k_out.clone(), self._uniq_count.clone(),
+                                   self.last_stats["det_mask_rois"].clone()))
+        if not materialize:
+            return None
+        return {"instances": self._materialize(self._post_ticket())}
+
+    def _claim_lookahead(self, frame: dict, coming: List[dict]):
+        """The frame's place in the look-ahead window; bookkeeping and `wait_event`s on the current stream, no launch.  Moves
+        `self._pyramid` to the frame's pyramid set and returns (the entry of `self._ahead` that holds this frame's trunk, or None when
+        it has to be computed now; the frames of `coming` whose trunk pass starts in this frame, one batch of one image size, [] for
+        none; how many frames are ahead already)."""
         cur = torch.cuda.current_stream(self.device)
         ext, self._prefetched = self._prefetched, None
         if isinstance(ext, tuple):                 # (image, Hp, Wp) computed into the next set by BatchedSequences, its event in _ev_trunk
@@ -470,15 +488,13 @@ class CustomRCNNRecurrent:
         self._pyramid = (self._pyramid + 1) % PYRAMID_SETS
         if not hit and self._pyramid in self._pyr_reader:
             cur.wait_event(self._pyr_reader[self._pyramid])
-        coming = [] if next_frame is None else (list(next_frame) if isinstance(next_frame, (list, tuple)) else [next_frame])
         # frames further ahead stay valid only if the caller really passes them next (checked frame by frame)
         keep = 0
         while keep < len(ahead) and keep < len(coming) and ahead[keep]["image"] is coming[keep]["image"]:
             keep += 1
         for e in ahead[keep:]:
             cur.wait_event(e["event"])             # dropped: over before their sets are written again
-        ahead = ahead[:keep]
-        self._ahead = ahead
+        self._ahead = ahead = ahead[:keep]
         depth = max(1, int(self.lookahead_frames)) if self.lookahead_depth is None else max(1, int(self.lookahead_depth))
         batch = []
         if self.prefetch_trunk and self.overlap_branches and len(ahead) < min(depth, PYRAMID_SETS - 2):
@@ -491,164 +507,114 @@ class CustomRCNNRecurrent:
                     break
                 n_same += 1
             batch = batch[:n_same]
-        next_frame = batch if batch else None
-        look_ahead = next_frame is not None
-        first_ahead = len(ahead)
-        if look_ahead and self.lookahead_at_start:
-            # it may start NOW, beside this frame's memory fusion, tower and proposal decoding (a short latency-bound chain
-            # that leaves most of the chip idle); the host enqueues that chain first so that the main stream never starves
-            if self._ev_start is None:
-                self._ev_start = torch.cuda.Event()
-            self._ev_start.record(cur)
-        if hit:
+        return pre, batch, len(ahead)
+
+    def _front(self, frame: dict, pre: Optional[dict], proj, mem_f16):
+        """Memory read + fusion and the top of the pyramid (on the trunk computed ahead, `pre`, or behind the frame's own preprocess
+        + trunk), then the proposal generator -> (views, shapes, (proposal boxes, scores, count))."""
+        if pre is not None:
             feats, views, shapes, off = self.backbone.fuse_memory_and_top(pre["Hp"], pre["Wp"], mem_f16, proj, self._pyramid, self._err)
         else:
             x4, Hp, Wp = ops.preprocess_image(self._device_image(frame), self.pixel_mean, self.pixel_std)
             feats, views, shapes, off = self.backbone.forward(x4, Hp, Wp, mem_f16, proj, self._pyramid, self._err)
-        prop_boxes, prop_scores, prop_count = self.proposal_generator.forward(feats, shapes, off)
-        if look_ahead and self.lookahead_at_start:
-            self._enqueue_trunk(next_frame, self._ev_start, first_ahead)
-        update_mem = self.memory_type == "implicit_memory" or self.always_update_memory
+        return views, shapes, self.proposal_generator.forward(feats, shapes, off)
+
+    def _frame_in_order(self, frame: dict, image_hw, views, shapes, props, proj):
+        """`overlap_branches = False`: the rest of the frame on the current stream, one launch after the other."""
+        H, W = image_hw
+        prop_boxes, prop_scores, prop_count = props
+        det = self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W),
+                                         mem_rescore=(self.zs_weight, self.mem_scores))
+        det_boxes, det_scores, det_classes, det_rows, det_count = det
+        if self.front_event is not None:
+            # the latency-bound front of the frame (memory fusion, tower, proposal decoding, cascade) ends here; what follows is
+            # dense (mask passes): BatchedSequences staggers its scenes on this point
+            self.front_event.record(torch.cuda.current_stream(self.device))
+        self._detection_masks(views, shapes, det_boxes, det_count)
         mem_sel = None
-        mem_done = False
-        if self.overlap_branches:
-            main = torch.cuda.current_stream(self.device)
-            if self._side_stream is None:
-                self._side_stream = _sched_streams(self.device)[0]     # high priority: the small launches go first
-                self._ev_props, self._ev_pm, self._ev_box, self._ev_mem, self._ev_sel, self._ev_s0 = (torch.cuda.Event() for _ in range(6))
-            self._ev_props.record(main)
-            self._mark("proposals", main)
-            if look_ahead and not self.lookahead_at_start:
-                self._enqueue_trunk(next_frame, self._ev_props, first_ahead)
-            lazy = self.lazy_proposal_masks and update_mem
-            # Host enqueue order matters (the GPU runs behind the host here): first the large launches of the main stream, then
-            # the side stream's ~45 small ones -- they all execute beside the two mask passes.
-            if not lazy:
-                prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count,
-                                                                bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop_all", self._frame_no))
-                self._ev_pm.record(main)
-            self._side_stream.wait_event(self._ev_props)
-            with torch.cuda.stream(self._side_stream):
-                k = self._post_slot
-                if self._ev_det[k] is not None:
-                    self._side_stream.wait_event(self._ev_det[k])     # the detection list set k is still read by frame t-2's pass
-                # The frame's critical chain (proposal masks -> memory write -> next frame's memory read) waits for the MEMORY
-                # selection, which needs the cascade's stage-0 features only; the detection selection feeds the detection pass,
-                # which has slack.  Same stream, memory selection first (`memory_selection_first`).
-                sel_first = lazy and not self.early_memory_selection and self.memory_selection_first
-                box_sel = {}
-
-                def _select_memory():
-                    box_sel["mem"] = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
-                    self._ev_sel.record(self._side_stream)
-                    self._mark("mem_select", self._side_stream)
-
-                if update_mem:
-                    self._mem_scores_frame = self._frame_no          # written by stage 0 of the cascade below
-                det = self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W), sel=k,
-                                                 stage0_event=self._ev_s0 if (lazy and self.early_memory_selection) else None,
-                                                 mem_rescore=(self.zs_weight, self.mem_scores) if update_mem else None,
-                                                 after_cascade=_select_memory if sel_first else None)
-                det_boxes, det_scores, det_classes, det_rows, det_count = det
-                self._ev_box.record(self._side_stream)
-                self._mark("cascade+det_select", self._side_stream)
-                if sel_first:
-                    mem_sel = box_sel["mem"]
-            mem_stream = self._side_stream
-            if lazy and not self.early_memory_selection and not self.memory_selection_first:
-                with torch.cuda.stream(self._side_stream):
-                    mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
-                    self._ev_sel.record(self._side_stream)
-                    self._mark("mem_select", self._side_stream)
-            elif lazy and not self.early_memory_selection:
-                pass
-            elif lazy:
-                # The memory selection needs only stage 0 of the cascade (its CLIP-space features, custom_rcnn.py:825-875): it
-                # runs on its own stream beside stages 1-2 and the detection selection; the mask head then runs only on the
-                # proposals it keeps (same results: the other proposals' masks are never read, custom_rcnn.py:875-880).
-                mem_stream = _sched_streams(self.device)[3]
-                mem_stream.wait_event(self._ev_s0)
-                with torch.cuda.stream(mem_stream):
-                    mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
-                    self._ev_sel.record(mem_stream)
-                    self._mark("mem_select", mem_stream)
-            pipelined = self.pipeline_detection_pass
-            det_after = self.detection_pass_after if (pipelined and lazy and update_mem and self.overlap_memory_write) else "cascade"
-            if pipelined and det_after == "cascade":
-                self._enqueue_detection_pass(views, shapes, det, (H, W), frame)
-            elif pipelined:
-                pass        # enqueued below, behind the proposal masks / the memory write
-            else:
-                main.wait_event(self._ev_box)
-                self._detection_masks(views, shapes, det_boxes, det_count)
-            if lazy:
-                main.wait_event(self._ev_sel)
-                prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, rows=self._uniq_rows,
-                                                                rows_count=self._uniq_count,
-                                                                bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop", self._frame_no))
-                self._ev_pm.record(main)
-                self._mark("prop_masks", main)
-            if pipelined and det_after == "proposal_masks":
-                self._enqueue_detection_pass(views, shapes, det, (H, W), frame, after=self._ev_pm)
-            if update_mem and self.overlap_memory_write:
-                # the memory write needs the proposal masks (main stream) and the selection (side stream): it runs on the side
-                # stream beside the detection mask pass; the main stream joins at the end of the frame
-                with torch.cuda.stream(mem_stream):
-                    if not lazy:
-                        mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
-                    mem_stream.wait_event(self._ev_pm)
-                    self.update_implicit_memory(prop_boxes, prop_scores, prop_count, prop_masks, proj, (H, W), mem_sel)
-                    self._ev_mem.record(mem_stream)
-                    self._mark("mem_write", mem_stream)
-                mem_done = True
-                if pipelined and det_after == "memory_write":
-                    self._enqueue_detection_pass(views, shapes, det, (H, W), frame, after=self._ev_mem)
+        if self.lazy_proposal_masks:
+            # select the memory instances first, then run the mask head only on those proposals (same results: the other
+            # proposals' masks are never read, custom_rcnn.py:875-880)
+            mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
+            prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, rows=self._uniq_rows,
+                                                            rows_count=self._uniq_count, tag=("prop", self._frame_no))
         else:
-            pipelined = False
-            det = self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W),
-                                             mem_rescore=(self.zs_weight, self.mem_scores) if update_mem else None)
-            if update_mem:
-                self._mem_scores_frame = self._frame_no
-            det_boxes, det_scores, det_classes, det_rows, det_count = det
-            if self.front_event is not None:
-                # the latency-bound front of the frame (memory fusion, tower, proposal decoding, cascade) ends here; what follows is
-                # dense (mask passes): BatchedSequences staggers its scenes on this point
-                self.front_event.record(torch.cuda.current_stream(self.device))
-            self._detection_masks(views, shapes, det_boxes, det_count)
-            if self.lazy_proposal_masks and update_mem:
-                # select the memory instances first, then run the mask head only on those proposals (same results: the other
-                # proposals' masks are never read, custom_rcnn.py:875-880)
-                mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
-                prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, rows=self._uniq_rows,
-                                                                rows_count=self._uniq_count, tag=("prop", self._frame_no))
-            else:
-                prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, tag=("prop_all", self._frame_no))
-
+            prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, tag=("prop_all", self._frame_no))
         # detector_postprocess (custom_rcnn.py:579-580)
-        P = self._post
-        if not pipelined:
-            self._postprocess_and_paste(det_boxes, det_scores, det_classes, det_count, (H, W), frame, P)
-
+        self._postprocess_and_paste(det_boxes, det_scores, det_classes, det_count, (H, W), frame, self._post)
         # memory update (custom_rcnn.py:515)
-        if mem_done:
-            torch.cuda.current_stream(self.device).wait_event(self._ev_mem)
-        elif update_mem:
+        self.update_implicit_memory(prop_boxes, prop_scores, prop_count, prop_masks, proj, (H, W), mem_sel)
+
+    def _frame_pipelined(self, frame: dict, image_hw, views, shapes, props, proj, trailing_detection_pass: bool):
+        """`overlap_branches`: the rest of the frame over three streams, in the order the host enqueues it.
+        main (the current stream): proposal masks; joins the memory write -- and the detection pass unless it may trail.
+        side: box cascade -> memory selection -> detection selection -> memory write.
+        detection stream: detection masks + post-processing + paste, behind `detection_pass_after`."""
+        H, W = image_hw
+        prop_boxes, prop_scores, prop_count = props
+        main = torch.cuda.current_stream(self.device)
+        if self._side_stream is None:
+            self._side_stream = _sched_streams(self.device)[0]     # high priority: the small launches go first
+            self._ev_props, self._ev_pm, self._ev_box, self._ev_mem, self._ev_sel = (torch.cuda.Event() for _ in range(5))
+        side = self._side_stream
+        self._ev_props.record(main)
+        self._mark("proposals", main)
+        lazy = self.lazy_proposal_masks
+        # Host enqueue order matters (the GPU runs behind the host here): first the large launches of the main stream, then
+        # the side stream's ~45 small ones -- they all execute beside the two mask passes.
+        if not lazy:
+            prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count,
+                                                            bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop_all", self._frame_no))
+            self._ev_pm.record(main)
+        mem_sel = None
+
+        def select_memory():
+            nonlocal mem_sel
+            mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
+            self._ev_sel.record(side)
+            self._mark("mem_select", side)
+
+        side.wait_event(self._ev_props)
+        with torch.cuda.stream(side):
+            k = self._post_slot
+            if self._ev_det[k] is not None:
+                side.wait_event(self._ev_det[k])     # the detection list set k is still read by frame t-2's pass
+            # The frame's critical chain (proposal masks -> memory write -> next frame's memory read) waits for the MEMORY
+            # selection; the detection selection feeds the detection pass, which has slack: the memory selection goes between
+            # the cascade and the detection selection.
+            det = self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W), sel=k,
+                                             mem_rescore=(self.zs_weight, self.mem_scores),
+                                             after_cascade=select_memory if lazy else None)
+            self._ev_box.record(side)
+            self._mark("cascade+det_select", side)
+        det_after = self.detection_pass_after if lazy else "cascade"
+        if det_after == "cascade":
+            self._enqueue_detection_pass(views, shapes, det, (H, W), frame)
+        if lazy:
+            # the mask head runs only on the proposals the memory selection keeps (same results: the other proposals' masks are
+            # never read, custom_rcnn.py:875-880)
+            main.wait_event(self._ev_sel)
+            prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, rows=self._uniq_rows,
+                                                            rows_count=self._uniq_count,
+                                                            bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop", self._frame_no))
+            self._ev_pm.record(main)
+            self._mark("prop_masks", main)
+        if det_after == "proposal_masks":
+            self._enqueue_detection_pass(views, shapes, det, (H, W), frame, after=self._ev_pm)
+        # memory update (custom_rcnn.py:515): it needs the proposal masks (main stream) and the selection (side stream) and runs
+        # on the side stream beside the detection mask pass; the main stream joins below
+        with torch.cuda.stream(side):
+            if not lazy:
+                mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
+            side.wait_event(self._ev_pm)
             self.update_implicit_memory(prop_boxes, prop_scores, prop_count, prop_masks, proj, (H, W), mem_sel)
-        self.last_stats = {"prop_count": prop_count, "det_count": P["count"], "mem_k": self._writer.k_out,
-                           "det_mask_rois": self.roi_heads.last_selector.rep_count if self.dedup_detection_masks else P["count"]}
-        if pipelined and not trailing_detection_pass:
-            torch.cuda.current_stream(self.device).wait_event(self._ev_det[self._post_slot])     # in-order callers see a finished frame
-        if self.stats_log is not None:      # bench.py: device-side copies of the frame's counters, read after the timed region
-            if pipelined and trailing_detection_pass:
-                with torch.cuda.stream(self._det_stream):      # the count is written by the trailing detection pass: copy it there
-                    cnt = P["count"].clone()
-            else:
-                cnt = P["count"].clone()
-            self.stats_log.append((prop_count.clone(), cnt, self._writer.k_out.clone(), self._uniq_count.clone(),
-                                   self.last_stats["det_mask_rois"].clone()))
-        if not materialize:
-            return None
-        return {"instances": self._materialize(self._post_ticket())}
+            self._ev_mem.record(side)
+            self._mark("mem_write", side)
+        if det_after == "memory_write":
+            self._enqueue_detection_pass(views, shapes, det, (H, W), frame, after=self._ev_mem)
+        main.wait_event(self._ev_mem)
+        if not trailing_detection_pass:
+            main.wait_event(self._ev_det[self._post_slot])     # in-order callers see a finished frame
 
     def _mark(self, name: str, stream=None):
         """Diagnostics (`model.trace = []`): a timing event on `stream` (default: current) at a named point of the frame's schedule;
@@ -692,7 +658,7 @@ class CustomRCNNRecurrent:
         frame on the detection stream (lowest priority: its GEMMs fill whatever the latency-bound chains of the frame -- and of
         the next frame -- leave idle)."""
         if self._det_stream is None:
-            self._det_stream = _det_stream(self.device, self.det_stream_priority)
+            self._det_stream = _det_stream(self.device)
             self._ev_det = [torch.cuda.Event() for _ in range(RESULT_SETS)]
         ds = self._det_stream
         det_boxes, det_scores, det_classes, det_rows, det_count = det
@@ -719,6 +685,7 @@ class CustomRCNNRecurrent:
         return rows, cnt
 
     def update_implicit_memory(self, prop_boxes, prop_scores, prop_count, prop_masks, proj, image_hw, mem_sel=None):
+        """The write-back; like the reference, the frame runs it for every MEMORY_TYPE (custom_rcnn.py:515,573)."""
         rows, cnt = mem_sel if mem_sel is not None else self.select_memory_instances(prop_boxes, prop_scores, prop_count, image_hw)
         self._last_write = (prop_boxes, prop_masks, rows, cnt, proj)          # bench.py's HBM-class probe replays it
         follow = self.snapshot_follows_write if self.snapshot_follows_write is not None else self.test_type in ("default", "episodic")

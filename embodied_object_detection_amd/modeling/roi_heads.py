@@ -112,7 +112,7 @@ class DeticCascadeROIHeads:
         self.graph_cascade = False
         self._graphs = {}
         # three detection-list sets: the detection mask pass of frame t may still read set t % 3 while the cascades of the next
-        # frames write the others (meta_arch.py, pipeline_detection_pass / RESULT_SETS)
+        # frames write the others (meta_arch.py, `_enqueue_detection_pass` / RESULT_SETS)
         # LDS reserve of the DETECTION mask pass's launches (the pass that trails under the frame's / the next frame's latency-bound
         # chains): see EodConvDesc.lds_reserve.  0 = the kernel's natural occupancy.
         self.det_pass_lds_reserve = int(__import__("os").environ.get("EOD_DET_LDS_RESERVE", "0"))
@@ -122,36 +122,35 @@ class DeticCascadeROIHeads:
 
     # ---- cascade box heads ------------------------------------------------------------------------
     def forward_box(self, views: List[torch.Tensor], shapes, prop_boxes: torch.Tensor, prop_scores: torch.Tensor, count: torch.Tensor,
-                    image_hw: Tuple[int, int], sel: int = 0, stage0_event=None, mem_rescore=None, after_cascade=None):
-        """`stage0_event` (optional torch.cuda.Event): recorded once stage 0 has produced `feat0` / `featn0` -- all that the memory
-        selection (custom_rcnn.py:825-875) needs from the cascade.  `mem_rescore = (zs_weight of the meta-architecture, out [R, C1])`:
-        stage 0's classifier launch also writes the memory update's CLIP re-score of the proposals (custom_rcnn.py:838-861).
+                    image_hw: Tuple[int, int], sel: int = 0, mem_rescore=None, after_cascade=None):
+        """`mem_rescore = (zs_weight of the meta-architecture, out [R, C1])`: stage 0's classifier launch also writes the memory
+        update's CLIP re-score of the proposals (custom_rcnn.py:838-861).
         `after_cascade` (optional callable): enqueued between the cascade and the detection selection (the frame's critical chain
         waits for the memory selection, not for the detections)."""
         h3, w3 = shapes[0]
         H, W = image_hw
         R = self.R
-        if self.graph_cascade and stage0_event is None:
+        if self.graph_cascade:
             # Experiment (`graph_cascade`): the cascade's 21 launches as ONE hipGraph per (pyramid set, inputs) combination, captured on
             # first use and replayed.  Every buffer of the segment is static; the events around it stay outside the graph.
             key = (views[0].data_ptr(), prop_boxes.data_ptr(), prop_scores.data_ptr(), count.data_ptr(), mem_rescore is not None, H, W)
             g = self._graphs.get(key)
             if g is None:
-                self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, None, mem_rescore)     # eager once: workspaces exist
+                self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore)     # eager once: workspaces exist
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, None, mem_rescore)
+                    self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore)
                 self._graphs[key] = g
             g.replay()
             boxes = self.boxes[self.num_stages]
         else:
-            boxes = self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, stage0_event, mem_rescore)
+            boxes = self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore)
         if after_cascade is not None:
             after_cascade()
         self.last_selector = self.selectors[sel]
         return self.selectors[sel](boxes, self.prob, count, float(W), float(H), self.score_thresh, self.nms_thresh)
 
-    def _cascade(self, views, shapes, prop_boxes, prop_scores, count, image_hw, stage0_event, mem_rescore):
+    def _cascade(self, views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore):
         """The three cascade stages (detic_roi_heads.py:88-175) -> the final boxes buffer; scores land in `self.prob`."""
         h3, w3 = shapes[0]
         H, W = image_hw
@@ -185,8 +184,6 @@ class DeticCascadeROIHeads:
                                        prop_scores=prop_scores if (last or (k == 0 and mem_rescore is not None)) else None,
                                        mem_scores_out=mem_rescore[1] if (k == 0 and mem_rescore is not None) else None,
                                        final_inv_stages=1.0 / self.num_stages if last else 0.0, deltas_out=self.deltas)
-                if k == 0 and stage0_event is not None:
-                    stage0_event.record(torch.cuda.current_stream(self.device))
                 boxes = self.boxes[k + 1]
                 continue
             # the last stage's launch also fuses the cascade's scores: sqrt(mean_k(prob) * proposal score) (detic_roi_heads.py:164-173)
@@ -195,8 +192,6 @@ class DeticCascadeROIHeads:
                             prop_scores=prop_scores if (last or (k == 0 and mem_rescore is not None)) else None,
                             mem_scores_out=mem_rescore[1] if (k == 0 and mem_rescore is not None) else None,
                             final_inv_stages=1.0 / self.num_stages if last else 0.0)
-            if k == 0 and stage0_event is not None:
-                stage0_event.record(torch.cuda.current_stream(self.device))
             if not self.merge_cls_bb0:
                 st["bb0"](self.h2, R, 1, 1, relu=True, m_count=count, m_unit=1, out=self.hb)
             st["bb2"](self.hb, R, 1, 1, m_count=count, m_unit=1, out=self.deltas)

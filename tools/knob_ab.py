@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """A/B of model attributes through the boundary (`model([episode])`, Instances materialised) in one process on the GPU box.
 
-    python tools/knob_ab.py "" "early_memory_selection=True" "dedup_detection_masks=False;lazy_proposal_masks=False"
+    python tools/knob_ab.py "" "detection_pass_after='proposal_masks'" "dedup_detection_masks=False;lazy_proposal_masks=False"
 
 Each argument is a ';'-separated list of `attr=value` (attributes of the model; `roi_heads.x=v` / `backbone.x=v` reach the parts);
 the empty string is the default configuration.  Every configuration is run twice (interleaved) on the same 60 resident frames."""
