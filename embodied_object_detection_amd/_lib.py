@@ -43,6 +43,11 @@ class EodConvDesc(C.Structure):
     ]
 
 
+class EodConvPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tile", "bm", "bn", "bk", "splitk", "cps", "nchunks", "wavek", "glds", "tiles_m", "tiles_n",
+                                         "gn_fused")]
+
+
 class EodBoxRefine(C.Structure):
     _fields_ = [("deltas", C.c_void_p), ("ld", C.c_int32), ("wx", C.c_float), ("wy", C.c_float), ("ww", C.c_float), ("wh", C.c_float),
                 ("clip", C.c_int32), ("img_w", C.c_float), ("img_h", C.c_float), ("boxes_out", C.c_void_p)]
@@ -127,6 +132,7 @@ SIGNATURES = {
     "eod_conv2d": (C.c_int, [C.POINTER(EodConvDesc), C.c_void_p]),
     "eod_conv2d_workspace_bytes": (C.c_size_t, [C.POINTER(EodConvDesc)]),
     "eod_conv2d_gn_fused": (C.c_int, [C.POINTER(EodConvDesc)]),
+    "eod_conv2d_plan": (C.c_int, [C.POINTER(EodConvDesc), C.POINTER(EodConvPlan)]),
     "eod_groupnorm_partial_offset": (C.c_size_t, [C.c_int, C.c_int]),
     "eod_set_conv_math": (C.c_int, [C.c_int]),
     "eod_get_conv_math": (C.c_int, []),

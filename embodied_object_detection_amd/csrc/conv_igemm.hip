@@ -187,10 +187,12 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
   else if (M >= 32768 && big_tile_env() >= 1 && big_tile_env() <= 3) pick = big_tile_env() - 1;   // experiment knob
   const bool bk64_ok = !d->tap4 && d->Cin % 64 == 0 && d->Kpad % 64 == 0;
   pl.glds = (fbk == 5 && !d->tap4 && !d->in_relu) ? 2 : 0;
+  // tile and split-K are decided on `plan_rows` when given (a batch planned like one image: identical K walk, bitwise equal results)
+  const int Mp = (d->plan_rows > 0 && d->plan_rows < M) ? d->plan_rows : M;
   if (d->force_tile == 0 && math_mode().load(std::memory_order_relaxed) == EOD_MATH_BF16X3 && !d->tap4 && !d->in_relu) {
     pl.glds = 2;
-    const long t128 = (long)((M + 127) / 128) * ((d->Cout + 127) / 128);
-    const long t256 = (long)((M + 255) / 256) * ((d->Cout + 127) / 128);
+    const long t128 = (long)((Mp + 127) / 128) * ((d->Cout + 127) / 128);
+    const long t256 = (long)((Mp + 255) / 256) * ((d->Cout + 127) / 128);
     // measured (profiles/r01_bf16x3_accuracy_speed.log): 256x128 (8 waves, one workgroup per CU) once it fills the chip,
     // 128x128 once it fills two workgroups per CU, else the finest tile
     pick = t256 >= 256 ? 3 : (t128 >= 512 ? 0 : 2);
@@ -212,8 +214,6 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
   pl.bn = cfg[pick][1];
   pl.tiles_m = (M + pl.bm - 1) / pl.bm;
   pl.tiles_n = (d->Cout + pl.bn - 1) / pl.bn;
-  // split-K is decided on `plan_rows` when given (a batch planned like one image: identical K walk, bitwise equal results)
-  const int Mp = (d->plan_rows > 0 && d->plan_rows < M) ? d->plan_rows : M;
   const long tiles = (long)((Mp + pl.bm - 1) / pl.bm) * pl.tiles_n;
   int splitk = 1;
   if (d->out_mode == 2) {
@@ -362,6 +362,19 @@ extern "C" int eod_conv2d_gn_fused(const EodConvDesc* d) {
   t.gn_partial = nullptr;
   if (check_desc(&t) != EOD_OK) return 0;
   return make_plan(&t, total_rows(&t), t.Kpad / 32).splitk > 1 ? 1 : 0;
+}
+
+extern "C" int eod_conv2d_plan(const EodConvDesc* d, EodConvPlan* out) {
+  if (!out) return EOD_ERR_NULL;
+  const int st = check_desc(d);
+  if (st != EOD_OK) return st;
+  const Plan pl = make_plan(d, total_rows(d), d->Kpad / 32);
+  out->tile = pl.tile; out->bm = pl.bm; out->bn = pl.bn; out->bk = pl.bk;
+  out->splitk = pl.splitk; out->cps = pl.cps; out->nchunks = pl.nchunks;
+  out->wavek = pl.wavek; out->glds = pl.glds;
+  out->tiles_m = pl.tiles_m; out->tiles_n = pl.tiles_n;
+  out->gn_fused = (d->gn_partial && pl.splitk > 1) ? 1 : 0;
+  return EOD_OK;
 }
 
 extern "C" size_t eod_conv2d_workspace_bytes(const EodConvDesc* d) {

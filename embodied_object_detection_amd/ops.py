@@ -221,6 +221,13 @@ class Conv:
         check(self._lib.eod_conv2d(C.byref(d), _stream()), f"eod_conv2d[{self.name}]")
         return out
 
+    def plan(self) -> Dict[str, int]:
+        """The plan `eod_conv2d` makes for the descriptor of this layer's last call in the current arithmetic mode (EodConvPlan of
+        include/eod_hip.h as a dict): a read-back of the planner, nothing is launched."""
+        p = _lib.EodConvPlan()
+        check(self._lib.eod_conv2d_plan(C.byref(self.desc), C.byref(p)), f"eod_conv2d_plan[{self.name}]")
+        return {n: int(getattr(p, n)) for n, _t in p._fields_}
+
 
 # ----------------------------------------------------------------------------------------------------
 # elementwise / pooling

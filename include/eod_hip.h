@@ -126,6 +126,18 @@ typedef struct EodConvDesc {
 int eod_conv2d(const EodConvDesc* d, eod_stream_t stream);
 int eod_conv2d_gn_fused(const EodConvDesc* d); /* 1 when this layer can carry gn_partial (its plan has a slab reduce), else 0 */
 size_t eod_conv2d_workspace_bytes(const EodConvDesc* d);
+/* The plan eod_conv2d(d) would run, read back without launching anything (tests and tools: which kernel does a layer get at this
+ * shape, in the current arithmetic mode?).  The same planner call the launch makes; EOD_ERR_* for a descriptor eod_conv2d refuses. */
+typedef struct EodConvPlan {
+  int32_t tile;             /* 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 256x128 (bf16x3 only), 5 = 64x256 (out_mode 2 only) */
+  int32_t bm, bn, bk;       /* rows x columns of a workgroup's output tile (32 x 32 with wavek), K chunk per barrier pair */
+  int32_t splitk, cps, nchunks; /* K slabs summed by the reduce launch (1 = none), chunks per slab, Kpad / bk */
+  int32_t wavek;            /* 0, or the waves (4 / 8) the 32x32-tile kernel splits K over */
+  int32_t glds;             /* 2 = bf16x3 split kernel, 0 = fp32 MFMA kernel */
+  int32_t tiles_m, tiles_n; /* the grid is tiles_m * tiles_n x splitk */
+  int32_t gn_fused;         /* 1 when the slab reduce also writes d->gn_partial */
+} EodConvPlan;
+int eod_conv2d_plan(const EodConvDesc* d, EodConvPlan* out);
 /* Arithmetic of eod_conv2d when force_tile == 0 (process-wide, read at every call; initial value from the environment variable
  * EOD_CONV_MATH = fp32 | bf16x3):
  *   EOD_MATH_FP32   (0, default) fp32 matrix-core FMAs (v_mfma_f32_32x32x2_f32): the reference's arithmetic class;

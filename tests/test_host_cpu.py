@@ -478,7 +478,7 @@ def test_ctypes_descriptors_match_the_header_layout(tmp_path):
     gcc = shutil.which("gcc")
     if gcc is None:
         pytest.skip("no gcc")
-    structs = [getattr(_lib, n) for n in ("EodConvDesc", "EodProposalDesc", "EodDetDesc", "EodMemWriteDesc")]
+    structs = [getattr(_lib, n) for n in ("EodConvDesc", "EodConvPlan", "EodProposalDesc", "EodDetDesc", "EodMemWriteDesc")]
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "eod_hip.h")}"', "int main(void) {"]
     for st in structs:
         lines.append(f'  printf("{st.__name__} %zu\\n", sizeof({st.__name__}));')
