@@ -40,6 +40,7 @@ class EodConvDesc(C.Structure):
         ("level_w", C.c_int32 * MAX_LEVELS), ("fuse_w", C.c_void_p), ("out_units", C.c_void_p), ("fuse_b", C.c_float), ("w_split", C.c_void_p),
         ("plan_rows", C.c_int32), ("lds_reserve", C.c_int32), ("gn_partial", C.c_void_p), ("gn_groups", C.c_int32),
         ("y2", C.c_void_p), ("split_n", C.c_int32), ("prefetch2", C.c_int32), ("gate", C.c_void_p),
+        ("w_half", C.c_void_p),
     ]
 
 
@@ -138,6 +139,8 @@ SIGNATURES = {
     "eod_get_conv_math": (C.c_int, []),
     "eod_conv_split_weights_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "eod_conv_split_weights_bf16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "eod_conv_half_weights_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "eod_conv_half_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "eod_preprocess_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]),
     "eod_maxpool3x3s2": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),

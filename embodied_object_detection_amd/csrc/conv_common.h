@@ -1,5 +1,5 @@
 // Shared by the convolution translation units: launch arguments, the fused epilogue and the launch entry points of the
-// kernel families (fp32 MFMA: conv_fp32.hip, bf16x3 split: conv_bf16x3.hip).  Planning,
+// kernel families (fp32 MFMA: conv_fp32.hip, bf16x3 split: conv_bf16x3.hip, f16 operands: conv_f16.hip).  Planning,
 // argument checks and the C ABI live in conv_igemm.hip.
 #pragma once
 #include "eod_common.h"
@@ -33,6 +33,8 @@ struct ConvArgs {
   unsigned x_bytes, w_bytes;   // sizes of the two operand buffers (range of the buffer descriptors)
   const void* w3;              // optional pre-split weights of the bf16x3 kernels (eod_conv_split_weights_bf16x3)
   unsigned w3_bytes;
+  const void* wh;              // optional half copy of the weights for the f16 kernels (eod_conv_half_weights)
+  unsigned wh_bytes;
   double* gn_partial;          // optional (pyramid mode + split-K): GroupNorm partial sums written by the slab reduce (EodConvDesc)
   int gn_groups;
   float* y2;                   // optional second output: columns [split_n, Cout) go to y2 [M, Cout - split_n] (with the ReLU), columns
@@ -162,5 +164,8 @@ void launch_conv_fp32(const ConvArgs& a, int tile, int bk, bool tap4, dim3 grid,
 void launch_conv_bf16x3(const ConvArgs& a, int tile, dim3 grid, hipStream_t s);
 void launch_conv_wavek(const ConvArgs& a, int nw, dim3 grid, hipStream_t s);
 void launch_split_weights(const float* w, void* out, int Cout, int Kpad, hipStream_t s);
+// f16 operands, fp32 accumulate: tile 3 = 64x64 (4 waves), 4 = 256x128 (8 waves); bk 64 or 32
+void launch_conv_f16(const ConvArgs& a, int tile, int bk, dim3 grid, hipStream_t s);
+void launch_half_weights(const float* w, void* out, int Cout, int Kpad, hipStream_t s);
 
 }  // namespace eodconv

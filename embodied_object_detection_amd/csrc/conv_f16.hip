@@ -1,0 +1,272 @@
+// Convolution with operands rounded to binary16 on the f16 matrix cores, fp32 accumulate: opt-in arithmetic mode, DESIGN.md §3.
+#include "conv_common.h"
+
+namespace eodconv {
+namespace {
+
+// ------------------------------------------------------------------------------------------------------
+// y = epilogue( sum_k half(x)_k * half(w)_k ) on v_mfma_f32_32x32x16_f16: what torch.autocast makes of conv2d / linear.
+//   * half() is v_cvt_pk_f16_f32: IEEE round-to-nearest-even, |v| > 65504 -> inf, subnormals kept, NaN stays NaN.  Nothing is
+//     clamped or scaled, so inf / NaN propagate as IEEE says (0 * inf = NaN included);
+//   * the products of two halves are exact in fp32 and summed in the fp32 MFMA accumulator; split-K slabs and the epilogue are the
+//     fp32 ones of conv_common.h, the output is stored as unrounded fp32;
+//   * the activations are fetched as fp32 exactly like the other kernels (same buffer-load addressing and padding mask),
+//     converted in registers at staging time and written to LDS as [row][BK halves] + 16 B pad: 144-byte rows for BK = 64, 80 for
+//     BK = 32 (9 / 5 slots of 16 B: an odd pitch, so the 16-lane groups of ds_read_b128 are conflict free);
+//   * one ds_read_b128 per (32-row tile, K = 16 step) feeds the MFMA fragment directly: lane (r, h) takes k = 8h .. 8h+7 of its row;
+//   * WH: the weights come as a half copy ([Cout][Kpad] binary16, eod_conv_half_weights): their LDS image is a plain copy of
+//     16-byte pieces.  Without it they are fetched as fp32 and rounded like the activations (same values, twice the bytes).
+//   * two LDS stages: the halves of chunk c+1 are written into the other stage in the iteration that multiplies chunk c, the
+//     fp32 registers are refilled with chunk c+2 at once: one barrier per chunk, a full iteration for every load to land.
+// The planner uses BK = 32 (measured: two 256x128 workgroups per CU instead of one); BK = 64 is selectable and needs Cin % 64 == 0
+// (a chunk never straddles two filter taps).
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned pk_f16(float a, float b) {
+  f32x2_t v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));   // v_cvt_pk_f16_f32 (RNE)
+}
+__device__ __forceinline__ uint2 half4(f32x4 v) { return make_uint2(pk_f16(v.x, v.y), pk_f16(v.z, v.w)); }
+
+template <int BM, int BN, int NT, int BK, bool MULTI, bool WH>
+__global__ __launch_bounds__(NT) void conv_f16_kernel(ConvArgs p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int ROWB = 2 * BK + 16;              // bytes per tile row
+  constexpr int STAGE = (BM + BN) * ROWB;
+  constexpr int WM = NT / 128;                   // waves as WM x 2
+  constexpr int TM = BM / (32 * WM), TN = BN / 64;
+  constexpr int TPR = BK / 4;                    // threads per row at one float4 each
+  constexpr int RPP = NT / TPR;                  // rows per staging pass
+  constexpr int AR = BM / RPP, BR = WH ? 0 : BN / RPP, UNITS = AR + BR;
+  constexpr int PPR = BK / 8;                    // WH: 16-byte weight pieces per row and chunk
+  constexpr int BP = WH ? BN * PPR / NT : 0;
+  static_assert(TM >= 1 && TN >= 1 && AR >= 1 && BN % RPP == 0 && (BN * PPR) % NT == 0, "tile / thread shape");
+  extern __shared__ __attribute__((aligned(16))) char lds_dyn[];
+  char* lds = lds_dyn;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+
+  int M = p.M;
+  M = conv_row_limit(p, M);
+  const int ntiles = ((M + BM - 1) / BM) * p.tiles_n;
+  if ((int)blockIdx.x >= ntiles) return;
+  const int t = xcd_remap(blockIdx.x, ntiles);
+  const int tile_m = t / p.tiles_n;
+  const int tile_n = t - tile_m * p.tiles_n;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  if (!conv_tile_active(p, m0, BM)) return;
+  const int z = blockIdx.y;
+  const int c_begin = z * p.cps;
+  int c_end = c_begin + p.cps;
+  if (c_end > p.nchunks) c_end = p.nchunks;
+
+  const int lr = tid / TPR, lq = tid % TPR;
+  unsigned a_voff[AR];
+  unsigned long long a_mask[AR];
+  unsigned a_pitch[MULTI ? AR : 1];
+#pragma unroll
+  for (int i = 0; i < AR; ++i) {
+    const int m = m0 + lr + RPP * i;
+    int iy0 = 0, ix0 = 0, off = 0, hh = 1, ww = 1;
+    const bool rowok = m < M;
+    if (rowok) {
+      if (MULTI) {
+        int l = 0;
+        while (l + 1 < p.nlv && m >= p.lv_off[l + 1]) ++l;
+        const int local = m - p.lv_off[l];
+        ww = p.lv_w[l];
+        hh = p.lv_h[l];
+        const int oy = local / ww;
+        iy0 = oy - p.pad;
+        ix0 = (local - oy * ww) - p.pad;
+        off = p.lv_off[l];
+      } else {
+        const int tq = (int)fdiv((unsigned)m, p.div_ow);
+        const int ox = m - tq * p.OW;
+        const int img = (int)fdiv((unsigned)tq, p.div_oh);
+        const int oy = tq - img * p.OH;
+        iy0 = oy * p.stride - p.pad;
+        ix0 = ox * p.stride - p.pad;
+        off = img * p.H * p.W;
+        hh = p.H;
+        ww = p.W;
+      }
+    }
+    unsigned long long mask = 0;
+    if (rowok) {
+      mask = tap_mask(iy0, ix0, hh, ww, p.KH, p.KW);
+    }
+    a_mask[i] = mask;
+    a_voff[i] = (unsigned)(((off + iy0 * ww + ix0) * p.Cin + 4 * lq) * 4);
+    if (MULTI) a_pitch[i] = (unsigned)(ww * p.Cin * 4);
+  }
+  unsigned w_voff[BR > 0 ? BR : 1];
+#pragma unroll
+  for (int j = 0; j < BR; ++j) {
+    const int n = n0 + lr + RPP * j;
+    w_voff[j] = n < p.Cout ? (unsigned)((n * p.Kpad + 4 * lq) * 4) : 0xFFFFFFFFu;
+  }
+  // WH: piece q = tid + NT u of the [BN rows][PPR pieces] weight tile
+  unsigned wh_voff[BP > 0 ? BP : 1];
+  int wh_lds[BP > 0 ? BP : 1];
+#pragma unroll
+  for (int u = 0; u < BP; ++u) {
+    const int q = tid + NT * u;
+    const int row = q / PPR, pc = q - row * PPR;
+    const int n = n0 + row;
+    wh_voff[u] = n < p.Cout ? (unsigned)(n * p.Kpad * 2 + pc * 16) : 0xFFFFFFFFu;
+    wh_lds[u] = (BM + row) * ROWB + pc * 16;
+  }
+  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_wh = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wh), 0, WH ? p.wh_bytes : 0u, 0x00020000);
+
+  f32x4 raw[UNITS];
+  u32x4_t braw[BP > 0 ? BP : 1];
+  struct TapInfo { int tap, ky; unsigned tap_off, k0b; };
+  // tap_info() is called for consecutive chunks (c_begin, c_begin + 1, ...): the (tap, channel) position is advanced instead of
+  // re-derived with two divisions per chunk.  The one or two calls past c_end describe chunks that are fetched (range-checked
+  // buffer loads) and never used.
+  int nx_tap, nx_c0, nx_ky, nx_kx, nx_k0 = c_begin * BK;
+  nx_tap = nx_k0 / p.Cin;
+  nx_c0 = nx_k0 - nx_tap * p.Cin;
+  nx_ky = nx_tap / p.KW;
+  nx_kx = nx_tap - nx_ky * p.KW;
+  auto tap_info = [&]() {
+    TapInfo ti;
+    ti.tap = nx_tap < 63 ? nx_tap : 63;
+    ti.ky = nx_ky;
+    ti.tap_off = MULTI ? (unsigned)((nx_kx * p.Cin + nx_c0) * 4) : (unsigned)(((nx_ky * p.W + nx_kx) * p.Cin + nx_c0) * 4);
+    ti.k0b = (unsigned)(nx_k0 * 4);
+    nx_k0 += BK;
+    nx_c0 += BK;
+    if (nx_c0 >= p.Cin) {
+      nx_c0 = 0;
+      ++nx_tap;
+      if (++nx_kx == p.KW) {
+        nx_kx = 0;
+        ++nx_ky;
+      }
+    }
+    return ti;
+  };
+  auto load_chunk = [&](const TapInfo& ti) {
+#pragma unroll
+    for (int u = 0; u < UNITS; ++u) {
+      if (u < AR) {
+        const bool ok = (a_mask[u] >> ti.tap) & 1ull;
+        unsigned vo = a_voff[u] + ti.tap_off;
+        if (MULTI) vo += (unsigned)ti.ky * a_pitch[u];
+        vo = ok ? vo : 0xFFFFFFFFu;
+        raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, 0, 0));
+      } else {
+        raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[u - AR], ti.k0b, 0));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < BP; ++u) braw[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_wh, wh_voff[u], ti.k0b >> 1, 0);
+  };
+  // rounds the fp32 registers to half and writes the tile image of one chunk
+  auto stage_chunk = [&](char* stage) {
+#pragma unroll
+    for (int u = 0; u < UNITS; ++u) {
+      const int row = u < AR ? lr + RPP * u : BM + lr + RPP * (u - AR);
+      *reinterpret_cast<uint2*>(stage + row * ROWB + lq * 8) = half4(raw[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < BP; ++u) *reinterpret_cast<u32x4_t*>(stage + wh_lds[u]) = braw[u];
+  };
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  const int frow = lane & 31, fh = lane >> 5;
+  const int a_fo = (wm * TM * 32 + frow) * ROWB + fh * 16;
+  const int b_fo = (BM + wn * TN * 32 + frow) * ROWB + fh * 16;
+
+  load_chunk(tap_info());
+  stage_chunk(lds);
+  load_chunk(tap_info());
+  for (int chunk = c_begin; chunk < c_end; ++chunk) {
+    const int st = (chunk - c_begin) & 1;
+    const char* cur = lds + st * STAGE;
+    char* nxt = lds + (st ^ 1) * STAGE;
+    __syncthreads();      // stage `cur` fully written (previous iteration), stage `nxt` no longer read
+    stage_chunk(nxt);     // chunk + 1, fetched one iteration ago
+    load_chunk(tap_info());   // chunk + 2
+#pragma unroll
+    for (int s = 0; s < BK / 16; ++s) {
+      f16x8_t af[TM], bfr[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) af[i] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(cur + a_fo + i * 32 * ROWB + s * 32));
+#pragma unroll
+      for (int j = 0; j < TN; ++j) bfr[j] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(cur + b_fo + j * 32 * ROWB + s * 32));
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    }
+  }
+
+  store_wave_tiles<TM, TN>(p, acc, m0 + wm * TM * 32, n0 + wn * TN * 32, M, z, lane);
+#endif
+}
+
+}  // namespace
+
+// [Cout][Kpad] fp32 -> [Cout][Kpad] binary16 (round-to-nearest-even), eight values per thread and step
+__global__ __launch_bounds__(256) void half_weights_kernel(const float* __restrict__ w, uint4* __restrict__ out, size_t octs) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < octs; i += (size_t)gridDim.x * blockDim.x) {
+    const uint2 lo = half4(*reinterpret_cast<const f32x4*>(w + i * 8));
+    const uint2 hi = half4(*reinterpret_cast<const f32x4*>(w + i * 8 + 4));
+    out[i] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+  }
+}
+
+void launch_half_weights(const float* w, void* out, int Cout, int Kpad, hipStream_t s) {
+  const size_t octs = (size_t)Cout * Kpad / 8;
+  int blocks = (int)((octs + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(half_weights_kernel, dim3(blocks), dim3(256), 0, s, w, static_cast<uint4*>(out), octs);
+}
+
+template <int BM, int BN, int NT, int BK, bool MULTI, bool WH>
+static void launch_f16_one(const ConvArgs& a, dim3 grid, hipStream_t s) {
+  constexpr int kLds = 2 * (BM + BN) * (2 * BK + 16);
+  // above the 64 KiB a kernel gets without asking; a refused attribute shows up as a launch error (EOD_ERR_LAUNCH)
+  static const bool attr = kLds <= 65536 || hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<BM, BN, NT, BK, MULTI, WH>),
+                                                                hipFuncAttributeMaxDynamicSharedMemorySize, kLds) == hipSuccess;
+  (void)attr;
+  hipLaunchKernelGGL((conv_f16_kernel<BM, BN, NT, BK, MULTI, WH>), grid, dim3(NT), kLds, s, a);
+}
+
+template <int BM, int BN, int NT>
+static void launch_f16_tile(const ConvArgs& a, int bk, dim3 grid, hipStream_t s) {
+  const bool multi = a.nlv > 0, wh = a.wh != nullptr;
+  if (bk == 64) {
+    if (multi) wh ? launch_f16_one<BM, BN, NT, 64, true, true>(a, grid, s) : launch_f16_one<BM, BN, NT, 64, true, false>(a, grid, s);
+    else wh ? launch_f16_one<BM, BN, NT, 64, false, true>(a, grid, s) : launch_f16_one<BM, BN, NT, 64, false, false>(a, grid, s);
+  } else {
+    if (multi) wh ? launch_f16_one<BM, BN, NT, 32, true, true>(a, grid, s) : launch_f16_one<BM, BN, NT, 32, true, false>(a, grid, s);
+    else wh ? launch_f16_one<BM, BN, NT, 32, false, true>(a, grid, s) : launch_f16_one<BM, BN, NT, 32, false, false>(a, grid, s);
+  }
+}
+
+// tile 4 = 256x128 (8 waves), anything else 64x64 (4 waves); bk = 64 only by force_tile and with Cin % 64 == 0 (make_plan)
+void launch_conv_f16(const ConvArgs& a, int tile, int bk, dim3 grid, hipStream_t s) {
+  if (tile == 4) launch_f16_tile<256, 128, 512>(a, bk, grid, s);
+  else launch_f16_tile<64, 64, 256>(a, bk, grid, s);
+}
+
+}  // namespace eodconv

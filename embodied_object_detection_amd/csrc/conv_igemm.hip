@@ -3,12 +3,14 @@
 //   y[m][n] = act( (sum_k A[m][k] * Wt[n][k] + bias[n]) * out_scale + res[m][n] )
 //
 // A[m][k] is the im2col view of the NHWC input (m = (img, oy, ox), k = (ky, kx, c), c fastest), Wt is [Cout][Kpad].  The kernels
-// live in conv_fp32.hip (fp32 MFMA, default) and conv_bf16x3.hip (opt-in split-bf16 arithmetic); this file picks one, sizes the grid and, for small problems, splits K into fp32 slabs that
+// live in conv_fp32.hip (fp32 MFMA, default), conv_bf16x3.hip (opt-in split-bf16 arithmetic) and conv_f16.hip (opt-in: operands rounded
+// to half, fp32 accumulate); this file picks one, sizes the grid and, for small problems, splits K into fp32 slabs that
 // conv_splitk_reduce_kernel sums in a fixed order before the fused epilogue (deterministic, no atomics).
 #include "conv_common.h"
 #include "../../include/eod_hip.h"
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 
 namespace {
 
@@ -140,11 +142,14 @@ inline int default_bk() {
   return v;
 }
 
-// Process-wide arithmetic mode of eod_conv2d (eod_set_conv_math / EOD_CONV_MATH): 0 fp32 MFMA, 1 bf16x3 split.
+// Process-wide arithmetic mode of eod_conv2d (eod_set_conv_math / EOD_CONV_MATH): 0 fp32 MFMA, 1 bf16x3 split, 2 f16 operands.
+// The environment value is matched exactly; anything else (unset, empty, a misspelling) is the fp32 default.
 std::atomic<int>& math_mode() {
   static std::atomic<int> v([] {
     const char* e = getenv("EOD_CONV_MATH");
-    return (e && e[0] == 'b') ? EOD_MATH_BF16X3 : EOD_MATH_FP32;
+    if (e && strcmp(e, "bf16x3") == 0) return EOD_MATH_BF16X3;
+    if (e && strcmp(e, "f16") == 0) return EOD_MATH_F16;
+    return EOD_MATH_FP32;
   }());
   return v;
 }
@@ -152,7 +157,7 @@ std::atomic<int>& math_mode() {
 struct Plan {
   int tile;  // 1=128x128 2=128x64 3=64x64
   int bk;    // K chunk staged per barrier pair: 32 or 64
-  int glds;  // 2: bf16x3 split kernel (BK = 32); 0: fp32 MFMA kernel
+  int glds;  // 2: bf16x3 split kernel (BK = 32); 3: f16 kernel (BK = 32; 64 by force_tile 8x); 0: fp32 MFMA kernel
   int bm, bn, tiles_m, tiles_n, splitk, cps, nchunks;
   int wavek;  // 0, or the number of waves (4 / 8) of the 32x32-tile kernel that splits K over the waves of a workgroup
 };
@@ -174,22 +179,32 @@ inline int wavek_env() {
 }
 
 Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
-  // 256x128: bf16x3 8-wave kernel only; 64x256: fused mask-head tail (out_mode 2) only
+  // 256x128: bf16x3 / f16 8-wave kernels only; 64x256: fused mask-head tail (out_mode 2) only
   static const int cfg[5][2] = {{128, 128}, {128, 64}, {64, 64}, {256, 128}, {64, 256}};
   Plan pl{};
   // Measured on MI355X (tools/conv_bench.py, profiles/r01_conv_bench.log): the 64x64 tile (7 waves/SIMD, finest
   // tile quantisation over 256 CUs) is the fastest or ties on every shape of this path, including the
   // 50k x 256 x 2304 mask-head GEMM (107 vs 92 TFLOP/s for 128x128).  The larger tiles stay selectable.
   int pick = 2;
-  const int ft = d->force_tile % 10, fbk = d->force_tile / 10;   // force_tile = tile + 10 (BK 32) / + 20 (BK 64)
-  if (ft >= 1 && ft <= 3) pick = ft - 1;
-  else if (ft == 4 && fbk == 5 && !d->tap4 && !d->in_relu) pick = 3;
+  // force_tile = tile + 10 (BK 32) / + 20 (BK 64); + 50: bf16x3 kernels; + 90 / + 80: f16 kernels (tile 3 or 4) with BK 32 (the planner's) / 64
+  const int ft = d->force_tile % 10, fbk = d->force_tile / 10;
+  const bool half_ok = !d->tap4 && !d->in_relu;                  // what the bf16x3 and f16 kernels take; the rest stays fp32
+  const bool f16_forced = (fbk == 8 || fbk == 9) && half_ok;
+  if (f16_forced) pick = ft == 4 ? 3 : 2;
+  else if (ft >= 1 && ft <= 3) pick = ft - 1;
+  else if (ft == 4 && fbk == 5 && half_ok) pick = 3;
   else if (M >= 32768 && big_tile_env() >= 1 && big_tile_env() <= 3) pick = big_tile_env() - 1;   // experiment knob
   const bool bk64_ok = !d->tap4 && d->Cin % 64 == 0 && d->Kpad % 64 == 0;
-  pl.glds = (fbk == 5 && !d->tap4 && !d->in_relu) ? 2 : 0;
+  pl.glds = f16_forced ? 3 : ((fbk == 5 && half_ok) ? 2 : 0);
   // tile and split-K are decided on `plan_rows` when given (a batch planned like one image: identical K walk, bitwise equal results)
   const int Mp = (d->plan_rows > 0 && d->plan_rows < M) ? d->plan_rows : M;
-  if (d->force_tile == 0 && math_mode().load(std::memory_order_relaxed) == EOD_MATH_BF16X3 && !d->tap4 && !d->in_relu) {
+  const int math = math_mode().load(std::memory_order_relaxed);
+  if (d->force_tile == 0 && math == EOD_MATH_F16 && half_ok) {
+    pl.glds = 3;
+    // like bf16x3: the 8-wave 256x128 tile once it fills the chip, else the finest tile; decided on plan_rows like the slabs
+    pick = (long)((Mp + 255) / 256) * ((d->Cout + 127) / 128) >= 256 ? 3 : 2;
+  }
+  if (d->force_tile == 0 && math == EOD_MATH_BF16X3 && half_ok) {
     pl.glds = 2;
     const long t128 = (long)((Mp + 127) / 128) * ((d->Cout + 127) / 128);
     const long t256 = (long)((Mp + 255) / 256) * ((d->Cout + 127) / 128);
@@ -205,7 +220,10 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
     pick = 2;
     pl.glds = 0;
   }
-  pl.bk = (pl.glds || d->out_mode == 2) ? 32 : ((fbk == 2 && bk64_ok) ? 64 : (fbk == 1 ? 32 : (bk64_ok && default_bk() == 64 ? 64 : 32)));
+  // f16: BK = 32 measured faster or equal on the frame's layers (two 256x128 workgroups per CU instead of one; tools/f16_check.py);
+  // BK = 64 stays selectable (force_tile 8x) where Cin % 64 == 0, so that a chunk never straddles two filter taps
+  if (pl.glds == 3) pl.bk = (fbk == 8 && d->Cin % 64 == 0) ? 64 : 32;
+  else pl.bk = (pl.glds || d->out_mode == 2) ? 32 : ((fbk == 2 && bk64_ok) ? 64 : (fbk == 1 ? 32 : (bk64_ok && default_bk() == 64 ? 64 : 32)));
   const int nchunks = d->Kpad / pl.bk;
   (void)nchunks32;
   pl.nchunks = nchunks;
@@ -317,7 +335,9 @@ int check_desc(const EodConvDesc* d) {
   }
   if (d->gate && (d->out_mode != 0 || d->split_n != 0 || d->gn_partial)) return EOD_ERR_BAD_DIMS;
   if (d->gate && d->force_tile != 0 && d->force_tile % 10 != 3 && d->force_tile != 6 && d->force_tile != 7) return EOD_ERR_BAD_DIMS;
-  if (d->gate && d->force_tile / 10 == 5) return EOD_ERR_BAD_DIMS;          // no gated epilogue in the bf16x3 kernels
+  if (d->gate && (d->force_tile / 10 == 5 || d->force_tile / 10 == 8 || d->force_tile / 10 == 9))
+    return EOD_ERR_BAD_DIMS;                                                // no gated epilogue in the bf16x3 and f16 kernels
+  if ((d->force_tile / 10 == 8 || d->force_tile / 10 == 9) && d->force_tile % 10 != 3 && d->force_tile % 10 != 4) return EOD_ERR_BAD_DIMS;
   if (d->lds_reserve < 0 || d->lds_reserve > 48 * 1024) return EOD_ERR_BAD_DIMS;
   if (d->split_n != 0) {
     if (!d->y2) return EOD_ERR_NULL;
@@ -332,14 +352,14 @@ int check_desc(const EodConvDesc* d) {
         64 % (cpg / 4) != 0)
       return EOD_ERR_BAD_DIMS;
   }
-  if (!eod_aligned16(d->x) || !eod_aligned16(d->w) || !eod_aligned16(d->w_split)) return EOD_ERR_ALIGN;
+  if (!eod_aligned16(d->x) || !eod_aligned16(d->w) || !eod_aligned16(d->w_split) || !eod_aligned16(d->w_half)) return EOD_ERR_ALIGN;
   return EOD_OK;
 }
 
 }  // namespace
 
 extern "C" int eod_set_conv_math(int mode) {
-  if (mode != EOD_MATH_FP32 && mode != EOD_MATH_BF16X3) return EOD_ERR_BAD_DIMS;
+  if (mode != EOD_MATH_FP32 && mode != EOD_MATH_BF16X3 && mode != EOD_MATH_F16) return EOD_ERR_BAD_DIMS;
   return math_mode().exchange(mode);
 }
 
@@ -354,6 +374,18 @@ extern "C" int eod_conv_split_weights_bf16x3(const float* w, int Cout, int Kpad,
   if (Cout <= 0 || Kpad <= 0 || Kpad % 32 != 0 || (long)Cout * Kpad * 6 >= (1L << 32)) return EOD_ERR_BAD_DIMS;
   if (!eod_aligned16(w) || !eod_aligned16(out)) return EOD_ERR_ALIGN;
   launch_split_weights(w, out, Cout, Kpad, static_cast<hipStream_t>(stream));
+  return eod_launch_status();
+}
+
+extern "C" size_t eod_conv_half_weights_bytes(int Cout, int Kpad) {
+  return (Cout > 0 && Kpad > 0 && Kpad % 32 == 0) ? (size_t)Cout * Kpad * 2 : 0;
+}
+
+extern "C" int eod_conv_half_weights(const float* w, int Cout, int Kpad, void* out, eod_stream_t stream) {
+  if (!w || !out) return EOD_ERR_NULL;
+  if (Cout <= 0 || Kpad <= 0 || Kpad % 32 != 0 || (long)Cout * Kpad >= (1L << 29)) return EOD_ERR_BAD_DIMS;
+  if (!eod_aligned16(w) || !eod_aligned16(out)) return EOD_ERR_ALIGN;
+  launch_half_weights(w, out, Cout, Kpad, static_cast<hipStream_t>(stream));
   return eod_launch_status();
 }
 
@@ -410,6 +442,8 @@ extern "C" int eod_conv2d(const EodConvDesc* d, eod_stream_t stream) {
     a.w_bytes = (unsigned)((size_t)d->Cout * d->Kpad * sizeof(float));
     a.w3 = d->w_split;
     a.w3_bytes = (unsigned)((size_t)d->Cout * d->Kpad * 6);
+    a.wh = d->w_half;
+    a.wh_bytes = (unsigned)((size_t)d->Cout * d->Kpad * 2);
   }
   a.nlv = d->levels > 0 ? d->levels : 0;
   for (int l = 0; l < a.nlv; ++l) {
@@ -435,6 +469,7 @@ extern "C" int eod_conv2d(const EodConvDesc* d, eod_stream_t stream) {
   }
   dim3 grid(pl.tiles_m * pl.tiles_n, pl.splitk);
   if (pl.wavek) launch_conv_wavek(a, pl.wavek, grid, s);
+  else if (pl.glds == 3) launch_conv_f16(a, pl.tile, pl.bk, grid, s);
   else if (pl.glds == 2) launch_conv_bf16x3(a, pl.tile, grid, s);
   else launch_conv_fp32(a, pl.tile, pl.bk, d->tap4 != 0, grid, s, d->lds_reserve, d->prefetch2);
   if (pl.splitk > 1) {

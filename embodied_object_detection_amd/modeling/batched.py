@@ -38,7 +38,7 @@ def _share_weights(dst: CustomRCNNRecurrent, src: CustomRCNNRecurrent):
         return out
 
     for a, b in zip(convs(dst), convs(src)):
-        a.w, a.bias, a.w_split = b.w, b.bias, b.w_split
+        a.w, a.bias, a.w_split, a.w_half = b.w, b.bias, b.w_split, b.w_half
     dst.backbone.merge.prepared = src.backbone.merge.prepared
     for a, b in zip(dst.proposal_generator.tower, src.proposal_generator.tower):
         pass   # GroupNorm gamma / beta are tiny; left per scene

@@ -304,6 +304,7 @@ class ProposalTrainer:
             pg.out_conv.w.copy_(out32.w[:5])
             pg.out_conv.bias.copy_(out32.bias[:5])
             pg.out_conv.w_split = None                               # bf16x3 pieces of the old weights, if that arithmetic was in use
+            pg.out_conv.w_half = None
         self.after.append(sync_out_conv)
         self.scales = torch.tensor(pg.scales, dtype=torch.float32, device=dev)
         add(f"{h}.scales", self.scales, lambda g: g["scales"])    # five scalar parameters `scales.{l}.scale`, stepped as one tensor
@@ -337,11 +338,13 @@ class ProposalTrainer:
                     st["bb2"].w.copy_(det.bb2_32[k].w[:4])
                     st["bb2"].bias.copy_(det.bb2_32[k].bias[:4])
                     st["bb2"].w_split = None
+                    st["bb2"].w_half = None
                     st["cls_bb0"].w[:512].copy_(st["cls"].w)
                     st["cls_bb0"].w[512:].copy_(st["bb0"].w)
                     st["cls_bb0"].bias[:512].copy_(st["cls"].bias)
                     st["cls_bb0"].bias[512:].copy_(st["bb0"].bias)
                     st["cls_bb0"].w_split = None
+                    st["cls_bb0"].w_half = None
             self.after.append(sync_roi_heads)
 
         def stale_caches():
@@ -350,6 +353,7 @@ class ProposalTrainer:
             ops.ConvBackward.refresh_all(bws)                    # rotated weights of the dgrad convs: all layers in 4 launches
             for bw in bws:
                 bw.conv.w_split = None                           # bf16x3 pieces, if that arithmetic was in use
+                bw.conv.w_half = None
         self.after.append(stale_caches)
         s = cfg.SOLVER
         if bool(cfg.FP16):
@@ -690,11 +694,20 @@ class ForwardModelTraining:
         return out
 
 
+def _refuse_f16_training(what: str) -> None:
+    """The "f16" conv arithmetic is an inference mode: the input-gradient convolutions also go through eod_conv2d and would pick it
+    up unannounced, and autocast training (FP16: True) needs half weight gradients, rounding epilogues and a loss scaler."""
+    if ops.get_conv_math() == "f16":
+        raise ValueError(f'{what} while the conv arithmetic is "f16": that mode rounds the operands of every eod_conv2d launch to half '
+                         'and is for inference only; ops.set_conv_math("fp32") (or "bf16x3") before training')
+
+
 class Trainer(ProposalTrainer):
     """One optimizer over every trainable parameter of the recurrent detector (build_custom_optimizer's groups, custom_solver.py:19-79)
     and `forward_model`'s full loss dict per step: `ProposalTrainer` with the ROI heads' half."""
 
     def __init__(self, model, sd: Dict[str, torch.Tensor]):
+        _refuse_f16_training("Trainer")
         super().__init__(model, sd, roi_heads=True)
         self._acc = None
         self._copy_stream = None
@@ -797,6 +810,7 @@ class Trainer(ProposalTrainer):
 
     def optimizer_step(self, lr_factor: float = 1.0):
         """`optimizer.step()` + `scheduler.step()`'s factor (train_mp3d.py:625,633) on the gradients of the last `forward_backward_frames`."""
+        _refuse_f16_training("optimizer_step")
         if self._acc is None:
             raise RuntimeError("optimizer_step without gradients: call forward_backward_frames (or model(data) in training mode) first")
         self.opt.step(self._acc, lr_factor=lr_factor)

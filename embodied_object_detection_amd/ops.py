@@ -58,14 +58,18 @@ _conv_ws = Workspace()
 # ----------------------------------------------------------------------------------------------------
 # weight preparation (host, once per model build)
 # ----------------------------------------------------------------------------------------------------
-_CONV_MATH = {"fp32": 0, "bf16x3": 1}
+_CONV_MATH = {"fp32": 0, "bf16x3": 1, "f16": 2}
 
 
 def set_conv_math(mode: str) -> str:
-    """Arithmetic of every conv / linear launch from now on (process-wide): "fp32" (fp32 MFMA, default) or "bf16x3" (three-way
-    bf16 operand split on the bf16 MFMA pipe, fp32 accumulate; include/eod_hip.h eod_set_conv_math).  Returns the previous mode."""
+    """Arithmetic of every conv / linear launch from now on (process-wide): "fp32" (fp32 MFMA, default), "bf16x3" (three-way
+    bf16 operand split on the bf16 MFMA pipe, fp32 accumulate) or "f16" (operands rounded to half, fp32 accumulate, fp32 outputs:
+    inference only; include/eod_hip.h eod_set_conv_math).  Returns the previous mode."""
     if mode not in _CONV_MATH:
-        raise ValueError(f"conv math must be one of {sorted(_CONV_MATH)}, got {mode!r}")
+        hint = ""
+        if str(mode).lower() == "fp16":
+            hint = ' ("fp16" / FP16 is the config key of autocast training, which is not implemented; the inference arithmetic is "f16")'
+        raise ValueError(f"conv math must be one of {sorted(_CONV_MATH)}, got {mode!r}{hint}")
     prev = _lib.load().eod_set_conv_math(_CONV_MATH[mode])
     check(min(prev, 0), "eod_set_conv_math")
     return {v: k for k, v in _CONV_MATH.items()}[prev]
@@ -126,6 +130,7 @@ class Conv:
         self.desc = EodConvDesc()
         self._lib = _lib.load()
         self.w_split = None     # bf16x3 pieces of the weights, made on first use in that arithmetic mode
+        self.w_half = None      # the weights rounded to half, made on first use in f16 mode; dropped wherever w_split is
         self.event_log = None   # bench.py: list that receives (start_event, end_event, event_tag) per launch
         self.event_tag = None   # what the caller wants to know the launch by (no device work: a clone of m_count would be a launch)
         self.lds_reserve = 0    # EodConvDesc.lds_reserve: caps this layer's workgroups per CU (see include/eod_hip.h)
@@ -202,6 +207,17 @@ class Conv:
             check(self._lib.eod_conv_split_weights_bf16x3(self.w.data_ptr(), self.Cout, self.Kpad, self.w_split.data_ptr(), _stream()),
                   f"eod_conv_split_weights_bf16x3[{self.name}]")
         d.w_split = self.w_split.data_ptr() if (use_split and self.w_split is not None and presplit) else None
+        use_half = force_tile // 10 in (8, 9) if force_tile else (get_conv_math() == "f16")
+        if use_half and self.w_half is None and not self.tap4:
+            nb = self._lib.eod_conv_half_weights_bytes(self.Cout, self.Kpad)
+            self.w_half = torch.empty((nb,), dtype=torch.uint8, device=self.w.device)
+            check(self._lib.eod_conv_half_weights(self.w.data_ptr(), self.Cout, self.Kpad, self.w_half.data_ptr(), _stream()),
+                  f"eod_conv_half_weights[{self.name}]")
+            # the copy is used by every later launch of the layer, on whatever stream (the look-ahead trunk runs beside the frame
+            # that made it): finished before anybody can see it.  Once per layer; inside a graph capture it is ordered by the capture.
+            if not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(self.w.device).synchronize()
+        d.w_half = self.w_half.data_ptr() if (use_half and self.w_half is not None and presplit) else None
         if gn_stats is not None and levels is not None and self._lib.eod_conv2d_gn_fused(C.byref(d)):
             d.gn_partial = gn_stats.data_ptr() + self._lib.eod_groupnorm_partial_offset(len(levels[1]), gn_groups)
             d.gn_groups = gn_groups
@@ -588,6 +604,7 @@ class MemoryProjectorBackward:
         for c, w in zip(self.convs, weights):
             c.w[:, :256].copy_(w.detach().reshape(256, 512).t())
             c.w_split = None
+            c.w_half = None
 
     def __call__(self, grads: Sequence[torch.Tensor], pooled_f16: torch.Tensor, H: int, W: int, weight: float,
                  need_input_grad: bool = True):
@@ -695,6 +712,7 @@ class ConvBackward:
                 check(self.lib.eod_conv_rotate_weights(c.w.data_ptr(), c.Cout, c.KH, c.KW, c.Cin, c.Kpad, self._flipped.w.data_ptr(),
                                                        self._flipped.Kpad, _stream()), "eod_conv_rotate_weights")
                 self._flipped.w_split = None
+                self._flipped.w_half = None
             self._flipped_of = key
         return self._flipped
 
@@ -747,6 +765,7 @@ class ConvBackward:
         check(_lib.load().eod_conv_rotate_weights_multi(descs, len(todo), _stream()), "eod_conv_rotate_weights_multi")
         for bw in todo:
             bw._flipped.w_split = None
+            bw._flipped.w_half = None
             bw._flipped_of = (bw.conv.w.data_ptr(), bw.conv.w._version)
 
     def __call__(self, x: torch.Tensor, y: Optional[torch.Tensor], g_out: torch.Tensor, relu: bool = False, need_dx: bool = True,

@@ -122,6 +122,9 @@ typedef struct EodConvDesc {
    * = the skip connection's gradient: y = relu'(gate) * (conv(x) + res), a bottleneck block's timm.py:277-299 backward in one
    * launch instead of conv, add, mask). */
   const float* gate;
+  /* optional: the same weights rounded to binary16 for the f16 kernels (eod_conv_half_weights), Cout * Kpad * 2 bytes; the f16
+   * kernels copy it instead of fetching and rounding w per tile (same values either way); ignored by every other kernel */
+  const void* w_half;
 } EodConvDesc;
 int eod_conv2d(const EodConvDesc* d, eod_stream_t stream);
 int eod_conv2d_gn_fused(const EodConvDesc* d); /* 1 when this layer can carry gn_partial (its plan has a slab reduce), else 0 */
@@ -129,30 +132,41 @@ size_t eod_conv2d_workspace_bytes(const EodConvDesc* d);
 /* The plan eod_conv2d(d) would run, read back without launching anything (tests and tools: which kernel does a layer get at this
  * shape, in the current arithmetic mode?).  The same planner call the launch makes; EOD_ERR_* for a descriptor eod_conv2d refuses. */
 typedef struct EodConvPlan {
-  int32_t tile;             /* 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 256x128 (bf16x3 only), 5 = 64x256 (out_mode 2 only) */
+  int32_t tile;             /* 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 256x128 (bf16x3 and f16 only), 5 = 64x256 (out_mode 2 only) */
   int32_t bm, bn, bk;       /* rows x columns of a workgroup's output tile (32 x 32 with wavek), K chunk per barrier pair */
   int32_t splitk, cps, nchunks; /* K slabs summed by the reduce launch (1 = none), chunks per slab, Kpad / bk */
   int32_t wavek;            /* 0, or the waves (4 / 8) the 32x32-tile kernel splits K over */
-  int32_t glds;             /* 2 = bf16x3 split kernel, 0 = fp32 MFMA kernel */
+  int32_t glds;             /* 3 = f16 kernel, 2 = bf16x3 split kernel, 0 = fp32 MFMA kernel */
   int32_t tiles_m, tiles_n; /* the grid is tiles_m * tiles_n x splitk */
   int32_t gn_fused;         /* 1 when the slab reduce also writes d->gn_partial */
 } EodConvPlan;
 int eod_conv2d_plan(const EodConvDesc* d, EodConvPlan* out);
 /* Arithmetic of eod_conv2d when force_tile == 0 (process-wide, read at every call; initial value from the environment variable
- * EOD_CONV_MATH = fp32 | bf16x3):
+ * EOD_CONV_MATH = fp32 | bf16x3 | f16, matched exactly; anything else is fp32):
  *   EOD_MATH_FP32   (0, default) fp32 matrix-core FMAs (v_mfma_f32_32x32x2_f32): the reference's arithmetic class;
  *   EOD_MATH_BF16X3 (1) every fp32 operand split into three bf16 pieces, six bf16 MFMAs per product term set, fp32 accumulate:
  *                   fp32-class accuracy (error vs an fp64 convolution within 2x of the fp32 path's, tests/test_kernels_gpu.py)
  *                   at 16/6 of the fp32-MFMA ceiling.  The 7x7 stem and in_relu convs stay on the fp32 kernel.
+ *   EOD_MATH_F16    (2) every operand rounded to binary16 (IEEE round-to-nearest-even as v_cvt_pk_f16_f32 does it: |v| > 65504
+ *                   becomes inf, subnormals are kept, NaN stays NaN; nothing is clamped or scaled, so inf / NaN propagate as IEEE
+ *                   says), exact products summed in fp32 on v_mfma_f32_32x32x16_f16, fp32 epilogue, unrounded fp32 output: what
+ *                   torch.autocast makes of conv2d / linear, minus the rounding of the output.  Inference only (the training
+ *                   step refuses the mode).  The 7x7 stem, in_relu convs, the fused mask tail (out_mode 2) and gated layers stay
+ *                   on the fp32 kernel.  force_tile 93 / 94 (64x64 / 256x128, BK = 32 as the planner picks; 83 / 84: BK = 64) pick its kernels
+ *                   whatever the mode.
  * Returns the previous mode, or EOD_ERR_BAD_DIMS for an unknown one.  Nothing in the reference to mirror (build-defined). */
 #define EOD_MATH_FP32 0
 #define EOD_MATH_BF16X3 1
+#define EOD_MATH_F16 2
 int eod_set_conv_math(int mode);
 int eod_get_conv_math(void);
 /* w [Cout][Kpad] fp32 -> out [Cout][Kpad/32][ xh(32) | xm(32) | xl(32) ] bf16 (three round-to-nearest bf16 pieces of every
  * weight, 192 bytes per 32-wide K chunk = the LDS row image of the bf16x3 kernels).  Static weights are split once. */
 size_t eod_conv_split_weights_bytes(int Cout, int Kpad);
 int eod_conv_split_weights_bf16x3(const float* w, int Cout, int Kpad, void* out, eod_stream_t stream);
+/* w [Cout][Kpad] fp32 -> out [Cout][Kpad] binary16, round-to-nearest-even (EodConvDesc.w_half).  Static weights are rounded once. */
+size_t eod_conv_half_weights_bytes(int Cout, int Kpad);
+int eod_conv_half_weights(const float* w, int Cout, int Kpad, void* out, eod_stream_t stream);
 
 /* ---- small dense / elementwise ops -------------------------------------------------------------------- */
 /* d2 GeneralizedRCNN.preprocess_image (custom_rcnn.py:557): u8 CHW RGB -> (x-mean)/std, NHWC4 (4th channel

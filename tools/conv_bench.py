@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Micro-benchmark of the implicit-GEMM conv kernel on the shapes of the hot path (GPU box only)."""
+"""Micro-benchmark of the implicit-GEMM conv kernel on the shapes of the hot path (GPU box only).  `modes`: the per-layer table of
+the three arithmetic modes (fp32 / bf16x3 / f16) with the planner's own choice."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -36,7 +37,61 @@ def bench(name, N, H, W, Cin, Cout, k, stride, pad, tiles=(0, 1, 2, 3), splitks=
             except Exception as ex:
                 print(name, t, sk, "ERR", ex)
 
+F16_PEAK, HBM_TBS = 2516.0, 8.0      # dense f16 MFMA TFLOP/s (16 x the fp32 MFMA's 157) and HBM TB/s of the chip
+
+
+def modes(name, N, H, W, Cin, Cout, k, stride, pad, iters=30):
+    """One layer with the planner's own choice in the three arithmetic modes: time, plan, and for f16 the fraction of the f16 MFMA peak
+    next to the fraction of the HBM rate its least traffic (fp32 activations in and out, half weights) would need in that time."""
+    x = torch.randn((N, H, W, Cin), generator=g).to(dev)
+    w = torch.randn((Cout, Cin, k, k), generator=g) * 0.05
+    conv = ops.Conv(w, torch.zeros(Cout), stride=stride, pad=pad, device=dev)
+    OH, OW = conv.out_hw(H, W)
+    flops = 2.0 * N * OH * OW * Cout * Cin * k * k
+    least = 4.0 * N * H * W * Cin + 4.0 * N * OH * OW * Cout + 2.0 * Cout * Cin * k * k
+    cols = []
+    for mode in ("fp32", "bf16x3", "f16"):
+        prev = ops.set_conv_math(mode)
+        try:
+            out = conv(x, N, H, W, relu=True)
+            for _ in range(3):
+                conv(x, N, H, W, relu=True, out=out)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                conv(x, N, H, W, relu=True, out=out)
+            e1.record()
+            torch.cuda.synchronize()
+            p = conv.plan()
+        finally:
+            ops.set_conv_math(prev)
+        us = e0.elapsed_time(e1) / iters * 1e3
+        kern = f"wave-K {p['wavek']}" if p["wavek"] else f"{p['bm']}x{p['bn']} BK{p['bk']}" + (f" sk{p['splitk']}" if p["splitk"] > 1 else "")
+        cols.append((mode, us, kern))
+    us16 = cols[2][1]
+    tf, tb = flops / us16 / 1e6, least / us16 / 1e6
+    bound = "HBM-bound" if tb / HBM_TBS > 4 * tf / F16_PEAK and tb / HBM_TBS > 0.25 else ("latency / launch" if us16 < 15 else "mixed")
+    print(f"{name:26s} " + "  ".join(f"{m} {us:7.1f} us ({kern})" for m, us, kern in cols) +
+          f"  | f16 {tf:6.1f} TFLOP/s = {tf / F16_PEAK * 100:4.1f} % of the f16 peak, >= {tb:4.2f} TB/s = {tb / HBM_TBS * 100:4.1f} % of HBM: {bound};"
+          f" x{cols[0][1] / us16:.2f} of fp32, x{cols[1][1] / us16:.2f} of bf16x3", flush=True)
+
+
 which = sys.argv[1] if len(sys.argv) > 1 else "all"
+if which == "modes":
+    # the layers of one 640x640 frame (ResNet-50 trunk, FPN, tower, box and mask heads) in fp32 / bf16x3 / f16 arithmetic
+    for sh in [("l1 conv1 1x1 256->64", 1, 160, 160, 256, 64, 1, 1, 0), ("l1 conv2 3x3 64->64", 1, 160, 160, 64, 64, 3, 1, 1),
+               ("l1 conv3 1x1 64->256", 1, 160, 160, 64, 256, 1, 1, 0), ("l2 conv1 1x1 512->128", 1, 80, 80, 512, 128, 1, 1, 0),
+               ("l2 conv2 3x3 128->128", 1, 80, 80, 128, 128, 3, 1, 1), ("l2 conv3 1x1 128->512", 1, 80, 80, 128, 512, 1, 1, 0),
+               ("l3 conv1 1x1 1024->256", 1, 40, 40, 1024, 256, 1, 1, 0), ("l3 conv2 3x3 256->256", 1, 40, 40, 256, 256, 3, 1, 1),
+               ("l3 conv3 1x1 256->1024", 1, 40, 40, 256, 1024, 1, 1, 0), ("l4 conv1 1x1 2048->512", 1, 20, 20, 2048, 512, 1, 1, 0),
+               ("l4 conv2 3x3 512->512", 1, 20, 20, 512, 512, 3, 1, 1), ("l4 conv3 1x1 512->2048", 1, 20, 20, 512, 2048, 1, 1, 0),
+               ("fpn out3 3x3 256 80x80", 1, 80, 80, 256, 256, 3, 1, 1), ("tower-like 3x3 256 92x93", 1, 92, 93, 256, 256, 3, 1, 1),
+               ("fc1 256x12544->1024", 256, 1, 1, 12544, 1024, 1, 1, 0), ("fc2 256x1024->1024", 256, 1, 1, 1024, 1024, 1, 1, 0),
+               ("mask_fcn 43 rois", 43, 14, 14, 256, 256, 3, 1, 1), ("mask_fcn 92 rois", 92, 14, 14, 256, 256, 3, 1, 1),
+               ("mask_fcn 300 rois", 300, 14, 14, 256, 256, 3, 1, 1)]:
+        modes(*sh)
+    sys.exit(0)
 if which == "pipe":
     # pipeline variants of the 64x64 kernel (EodConvDesc.prefetch2: 0 default, 2 = double-buffered LDS) on shapes of the frame
     shapes = [("stem-like l1 conv1 256->64", 1, 160, 160, 256, 64, 1, 1, 0), ("l1 conv2 3x3 64->64", 1, 160, 160, 64, 64, 3, 1, 1),
