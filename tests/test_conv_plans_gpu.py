@@ -14,10 +14,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _conv_cases import SENTINEL, ceiling as _ceiling, exact_hw as _hw, plan_in as _plan_in
+
 pytestmark = pytest.mark.gpu
 
 MODES = ("fp32", "bf16x3")
-SENTINEL = -777.0
 # size name -> (H, W, memory grid, cell, scenes in lock-step)
 SIZES = {
     "640x640": (640, 640, 200, 0.2, 1),
@@ -99,16 +100,6 @@ class Call:
         return dict(res_mode=self.res_mode, relu=self.relu, in_relu=self.in_relu, out_scale=self.out_scale, gn_groups=self.gn_groups,
                     plan_rows=self.plan_rows, m_segments=self.m_segments, m_unit=self.m_unit, force_tile=self.force_tile,
                     force_splitk=self.force_splitk, levels=None if self.levels is None else (list(self.levels[0]), list(self.levels[1])))
-
-
-def _plan_in(conv, mode):
-    """The plan of the layer's last descriptor in `mode`, with the process's mode put back."""
-    from embodied_object_detection_amd import ops
-    prev = ops.set_conv_math(mode)
-    try:
-        return conv.plan()
-    finally:
-        ops.set_conv_math(prev)
 
 
 def _record(run) -> List[Call]:
@@ -386,13 +377,6 @@ def _line(tag, c: Call, plan: dict, e, e32) -> str:
             f"  cpu fp32 mean {e32[0]:.2e} max {e32[1]:.2e}")
 
 
-# Ceiling on mean |y - ref64| / mean |ref64| that does not depend on the CPU's own summation order (tests/test_kernels_gpu.py,
-# test_conv_bf16x3_accuracy): 3e-6 up to K = 4608, 1e-5 up to the box head's fc1 (K = 12544).
-def _ceiling(K: int) -> float:
-    assert K <= 12544, K
-    return 3e-6 if K <= 4608 else 1e-5
-
-
 def _check(c: Call, dev, tag: str, seed: int, expect_plans: Optional[dict] = None, modes=MODES) -> List[str]:
     """Replays the call alone in every mode against fp64 -> the list of what is wrong with it (empty = fine); prints one line per
     mode and count."""
@@ -574,14 +558,6 @@ def test_batch_of_4_is_bitwise_4_single_image_calls(dev, recorded):
 # ------------------------------------------------------------------------------------------------
 # 3. edges the production list does not hold but the planner's branch conditions invite
 # ------------------------------------------------------------------------------------------------
-def _hw(M: int) -> Tuple[int, int]:
-    """An image of exactly M positions, as square as M's divisors allow."""
-    h = int(M ** 0.5)
-    while M % h:
-        h -= 1
-    return h, M // h
-
-
 def _layer(dev, Cin, Cout, k=1, stride=1, seed=0, name="", deconv=False):
     from embodied_object_detection_amd import ops
     g = torch.Generator().manual_seed(seed)
