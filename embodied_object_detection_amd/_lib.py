@@ -40,7 +40,7 @@ class EodConvDesc(C.Structure):
         ("level_w", C.c_int32 * MAX_LEVELS), ("fuse_w", C.c_void_p), ("out_units", C.c_void_p), ("fuse_b", C.c_float), ("w_split", C.c_void_p),
         ("plan_rows", C.c_int32), ("lds_reserve", C.c_int32), ("gn_partial", C.c_void_p), ("gn_groups", C.c_int32),
         ("y2", C.c_void_p), ("split_n", C.c_int32), ("prefetch2", C.c_int32), ("gate", C.c_void_p),
-        ("w_half", C.c_void_p),
+        ("w_half", C.c_void_p), ("math", C.c_int32),
     ]
 
 
@@ -108,7 +108,7 @@ class EodStageTailDesc(C.Structure):
 class EodAdamWTensor(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_size_t),
                 ("lr", C.c_double), ("weight_decay", C.c_double), ("step", C.c_int32), ("folded_out", C.c_void_p), ("row_scale", C.c_void_p),
-                ("cols", C.c_int32), ("ld_out", C.c_int32), ("grad_of_folded", C.c_int32)]
+                ("cols", C.c_int32), ("ld_out", C.c_int32), ("grad_of_folded", C.c_int32), ("inv_scale", C.c_float), ("found_inf", C.c_void_p)]
 
 
 class EodRotateTensor(C.Structure):

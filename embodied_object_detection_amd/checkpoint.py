@@ -277,7 +277,7 @@ def export_state_dict(entries, base_sd: Dict[str, torch.Tensor], num_classes: in
 
 
 def save_checkpoint(path: str, sd: Dict[str, torch.Tensor], iteration: int = 0, optimizer: Optional[Dict] = None,
-                    scheduler: Optional[Dict] = None) -> None:
+                    scheduler: Optional[Dict] = None, scaler: Optional[Dict] = None) -> None:
     """What DetectionCheckpointer.save writes (train_mp3d.py:521-523,654): {'model': state dict, 'iteration': n} and, when given, the
     checkpointables 'optimizer' / 'scheduler'; the directory's `last_checkpoint` file names the newest save (fvcore
     `Checkpointer.tag_last_checkpoint`), which is what `--resume` follows."""
@@ -286,6 +286,10 @@ def save_checkpoint(path: str, sd: Dict[str, torch.Tensor], iteration: int = 0, 
         obj["optimizer"] = optimizer
     if scheduler is not None:
         obj["scheduler"] = scheduler
+    if scaler is not None:
+        # the AMP loss scaler's state (`ops.LossScaler.state_dict`, torch.amp.GradScaler's keys) beside the other checkpointables; the
+        # reference never stores its scaler and so restarts at the initial scale on every resume, which a file without this key does too
+        obj["scaler"] = scaler
     torch.save(obj, path)
     with open(os.path.join(os.path.dirname(os.path.abspath(path)), "last_checkpoint"), "w") as fh:
         fh.write(os.path.basename(path))
@@ -310,4 +314,5 @@ def load_training_state(path: str) -> Dict:
     obj = torch.load(path, map_location="cpu", weights_only=False)
     it = int(obj.get("iteration", -1)) if isinstance(obj, dict) else -1
     return {"iteration": it, "optimizer": obj.get("optimizer") if isinstance(obj, dict) else None,
-            "scheduler": (obj.get("scheduler") if isinstance(obj, dict) else None) or {"last_epoch": max(it, 0)}}
+            "scheduler": (obj.get("scheduler") if isinstance(obj, dict) else None) or {"last_epoch": max(it, 0)},
+            "scaler": obj.get("scaler") if isinstance(obj, dict) else None}

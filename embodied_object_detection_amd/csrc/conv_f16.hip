@@ -31,7 +31,10 @@ __device__ __forceinline__ unsigned pk_f16(float a, float b) {
 }
 __device__ __forceinline__ uint2 half4(f32x4 v) { return make_uint2(pk_f16(v.x, v.y), pk_f16(v.z, v.w)); }
 
-template <int BM, int BN, int NT, int BK, bool MULTI, bool WH>
+// GATE: the kernel honours ConvArgs.gate (EodConvDesc.gate: a ReLU's backward, with res_mode 1 the shortcut's sum, on the way out of
+// an input-gradient launch).  Compiled into the 64x64 image-mode instantiations only, the ones the planner gives a gated f16 call:
+// in the wide tiles the extra load spilled (conv_common.h), and the build refuses a kernel that uses scratch.
+template <int BM, int BN, int NT, int BK, bool MULTI, bool WH, bool GATE = false>
 __global__ __launch_bounds__(NT) void conv_f16_kernel(ConvArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int ROWB = 2 * BK + 16;              // bytes per tile row
@@ -219,7 +222,7 @@ __global__ __launch_bounds__(NT) void conv_f16_kernel(ConvArgs p) {
     }
   }
 
-  store_wave_tiles<TM, TN>(p, acc, m0 + wm * TM * 32, n0 + wn * TN * 32, M, z, lane);
+  store_wave_tiles<TM, TN, GATE>(p, acc, m0 + wm * TM * 32, n0 + wn * TN * 32, M, z, lane);
 #endif
 }
 
@@ -241,14 +244,14 @@ void launch_half_weights(const float* w, void* out, int Cout, int Kpad, hipStrea
   hipLaunchKernelGGL(half_weights_kernel, dim3(blocks), dim3(256), 0, s, w, static_cast<uint4*>(out), octs);
 }
 
-template <int BM, int BN, int NT, int BK, bool MULTI, bool WH>
+template <int BM, int BN, int NT, int BK, bool MULTI, bool WH, bool GATE = false>
 static void launch_f16_one(const ConvArgs& a, dim3 grid, hipStream_t s) {
   constexpr int kLds = 2 * (BM + BN) * (2 * BK + 16);
   // above the 64 KiB a kernel gets without asking; a refused attribute shows up as a launch error (EOD_ERR_LAUNCH)
-  static const bool attr = kLds <= 65536 || hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<BM, BN, NT, BK, MULTI, WH>),
+  static const bool attr = kLds <= 65536 || hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<BM, BN, NT, BK, MULTI, WH, GATE>),
                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kLds) == hipSuccess;
   (void)attr;
-  hipLaunchKernelGGL((conv_f16_kernel<BM, BN, NT, BK, MULTI, WH>), grid, dim3(NT), kLds, s, a);
+  hipLaunchKernelGGL((conv_f16_kernel<BM, BN, NT, BK, MULTI, WH, GATE>), grid, dim3(NT), kLds, s, a);
 }
 
 template <int BM, int BN, int NT>
@@ -263,9 +266,17 @@ static void launch_f16_tile(const ConvArgs& a, int bk, dim3 grid, hipStream_t s)
   }
 }
 
+// the gated 64x64 tile (image mode: make_plan gives a gated pyramid launch the fp32 kernel)
+static void launch_f16_gated(const ConvArgs& a, int bk, dim3 grid, hipStream_t s) {
+  const bool wh = a.wh != nullptr;
+  if (bk == 64) wh ? launch_f16_one<64, 64, 256, 64, false, true, true>(a, grid, s) : launch_f16_one<64, 64, 256, 64, false, false, true>(a, grid, s);
+  else wh ? launch_f16_one<64, 64, 256, 32, false, true, true>(a, grid, s) : launch_f16_one<64, 64, 256, 32, false, false, true>(a, grid, s);
+}
+
 // tile 4 = 256x128 (8 waves), anything else 64x64 (4 waves); bk = 64 only by force_tile and with Cin % 64 == 0 (make_plan)
 void launch_conv_f16(const ConvArgs& a, int tile, int bk, dim3 grid, hipStream_t s) {
-  if (tile == 4) launch_f16_tile<256, 128, 512>(a, bk, grid, s);
+  if (a.gate) launch_f16_gated(a, bk, grid, s);
+  else if (tile == 4) launch_f16_tile<256, 128, 512>(a, bk, grid, s);
   else launch_f16_tile<64, 64, 256>(a, bk, grid, s);
 }
 

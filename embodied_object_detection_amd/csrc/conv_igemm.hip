@@ -198,7 +198,8 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
   pl.glds = f16_forced ? 3 : ((fbk == 5 && half_ok) ? 2 : 0);
   // tile and split-K are decided on `plan_rows` when given (a batch planned like one image: identical K walk, bitwise equal results)
   const int Mp = (d->plan_rows > 0 && d->plan_rows < M) ? d->plan_rows : M;
-  const int math = math_mode().load(std::memory_order_relaxed);
+  // EodConvDesc.math: this call's arithmetic (EOD_MATH_* + 1), 0 = the process-wide mode
+  const int math = d->math > 0 ? d->math - 1 : math_mode().load(std::memory_order_relaxed);
   if (d->force_tile == 0 && math == EOD_MATH_F16 && half_ok) {
     pl.glds = 3;
     // like bf16x3: the 8-wave 256x128 tile once it fills the chip, else the finest tile; decided on plan_rows like the slabs
@@ -216,9 +217,12 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
     pick = 4;
     pl.glds = 0;
   }
-  if (d->gate) {            // the gated epilogue lives in the 64x64 fp32 tile, the wave-K kernel and the slab reduces
+  if (d->gate) {            // the gated epilogue lives in the 64x64 fp32 tile, the wave-K kernel and the slab reduces ...
+    // ... and in the 64x64 f16 tile, which a call that asks for f16 itself (EodConvDesc.math: the AMP step's input-gradient
+    // launches) gets; the process-wide f16 mode is for inference and keeps gated launches in fp32 as before
+    const bool f16_gated = d->math == EOD_MATH_F16 + 1 && half_ok && d->levels <= 0 && (d->force_tile == 0 || f16_forced);
     pick = 2;
-    pl.glds = 0;
+    pl.glds = f16_gated ? 3 : 0;
   }
   // f16: BK = 32 measured faster or equal on the frame's layers (two 256x128 workgroups per CU instead of one; tools/f16_check.py);
   // BK = 64 stays selectable (force_tile 8x) where Cin % 64 == 0, so that a chunk never straddles two filter taps
@@ -335,8 +339,12 @@ int check_desc(const EodConvDesc* d) {
   }
   if (d->gate && (d->out_mode != 0 || d->split_n != 0 || d->gn_partial)) return EOD_ERR_BAD_DIMS;
   if (d->gate && d->force_tile != 0 && d->force_tile % 10 != 3 && d->force_tile != 6 && d->force_tile != 7) return EOD_ERR_BAD_DIMS;
-  if (d->gate && (d->force_tile / 10 == 5 || d->force_tile / 10 == 8 || d->force_tile / 10 == 9))
-    return EOD_ERR_BAD_DIMS;                                                // no gated epilogue in the bf16x3 and f16 kernels
+  if (d->gate && d->force_tile / 10 == 5) return EOD_ERR_BAD_DIMS;          // no gated epilogue in the bf16x3 kernels
+  // ... and in the f16 family only in the 64x64 tile of a call that asks for f16 itself (image mode, no in_relu / tap4)
+  if (d->gate && (d->force_tile / 10 == 8 || d->force_tile / 10 == 9) &&
+      (d->math != EOD_MATH_F16 + 1 || d->force_tile % 10 != 3 || d->levels > 0 || d->tap4 || d->in_relu))
+    return EOD_ERR_BAD_DIMS;
+  if (d->math < 0 || d->math > EOD_MATH_F16 + 1) return EOD_ERR_BAD_DIMS;
   if ((d->force_tile / 10 == 8 || d->force_tile / 10 == 9) && d->force_tile % 10 != 3 && d->force_tile % 10 != 4) return EOD_ERR_BAD_DIMS;
   if (d->lds_reserve < 0 || d->lds_reserve > 48 * 1024) return EOD_ERR_BAD_DIMS;
   if (d->split_n != 0) {

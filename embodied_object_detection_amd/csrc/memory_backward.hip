@@ -189,6 +189,10 @@ struct AdamWMulti {
   unsigned grad_of_folded;             // bit t: g is the gradient of the FOLDED weights (x row_scale = the master's, chain rule)
   int count;
   float one_minus_b1, b2, one_minus_b2, eps, clip;
+  // loss scaler (EodAdamWTensor.inv_scale / found_inf): g is multiplied by inv_scale[t] first (0 = off); with `found_inf` the whole
+  // launch leaves everything as it is when the flag is set (GradScaler.step skipping optimizer.step)
+  float inv_scale[ADAMW_MULTI];
+  const int* found_inf;
 };
 
 __global__ __launch_bounds__(256) void adamw_multi_kernel(AdamWMulti a) {
@@ -206,8 +210,11 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(AdamWMulti a) {
   const float* __restrict__ rs = a.row_scale[t];
   const unsigned cols = a.cols[t], ldo = a.ld_out[t];
   const bool gscale = (a.grad_of_folded >> t) & 1u;
+  const float inv = a.inv_scale[t];
+  if (a.found_inf && *a.found_inf != 0) return;
   for (size_t i = (size_t)(blockIdx.x - first) * blockDim.x + threadIdx.x; i < n; i += nb * blockDim.x) {
     float gi = g[i];
+    if (inv != 0.f) gi *= inv;
     if (gscale) gi *= rs[(unsigned)(i / cols)];
     if (a.clip > 0.f) gi = fminf(fmaxf(gi, -a.clip), a.clip);
     float pi = p[i] * decay;
@@ -224,6 +231,30 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(AdamWMulti a) {
       folded[(size_t)r * ldo + c] = pi * rs[r];
     }
   }
+}
+
+// The loss scaler's found-inf pass over up to FINITE_MULTI gradient tensors in one launch (the check entries of eod_adamw_step_multi):
+// *flag = 1 when any element is inf or NaN (exponent all ones).  Every writer stores the same value: no atomics, no order.
+#define FINITE_MULTI 32
+struct FiniteMulti {
+  const float* g[FINITE_MULTI];
+  unsigned long long n[FINITE_MULTI];
+  unsigned block_end[FINITE_MULTI];
+  int count;
+  int* flag;
+};
+
+__global__ __launch_bounds__(256) void grads_nonfinite_kernel(FiniteMulti a) {
+  int t = 0;
+  while (t + 1 < a.count && blockIdx.x >= a.block_end[t]) ++t;
+  const unsigned first = t ? a.block_end[t - 1] : 0u;
+  const size_t nb = a.block_end[t] - first;
+  const unsigned* __restrict__ g = reinterpret_cast<const unsigned*>(a.g[t]);
+  const size_t n = a.n[t];
+  bool bad = false;
+  for (size_t i = (size_t)(blockIdx.x - first) * blockDim.x + threadIdx.x; i < n; i += nb * blockDim.x)
+    bad |= (g[i] & 0x7F800000u) == 0x7F800000u;
+  if (bad) *a.flag = 1;
 }
 
 // Third slice: backward of a stride-1 'same' convolution layer (FPN output convs timm.py:118-136, CenterNet tower
@@ -520,6 +551,114 @@ __global__ __launch_bounds__(256) void conv_backward_weights_lds_kernel(ConvBwdA
 #pragma unroll
     for (int kk = 0; kk < PK / 2; ++kk)
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[kk * 2 * TC], bp[kk * 2 * TC], acc, 0, 0, 0);
+    __syncthreads();
+  }
+  // C/D layout: column (ci) = lane & 31, row (co) = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
+  const int Ktot = a.KH * a.KW * a.Cin;
+  float* dw = a.splits > 1 ? a.part + (size_t)blockIdx.z * a.Cout * Ktot : a.dw;
+  float* db = a.splits > 1 ? a.bpart + (size_t)blockIdx.z * a.Cout : a.db;
+  const int ci = ci0 + wn * 32 + r;
+  if (ci < a.Cin) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int co = co0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * kh;
+      if (co < a.Cout) dw[(size_t)co * Ktot + (size_t)tap * a.Cin + ci] = acc[q];
+    }
+  }
+  if (a.db && tap == 0 && (tile % ci_tiles) == 0) {
+    // db[co] = sum over the positions: the 16 loader rows' sums, added in row order
+    bred[lp][c4 + 0] = bsum.x; bred[lp][c4 + 1] = bsum.y; bred[lp][c4 + 2] = bsum.z; bred[lp][c4 + 3] = bsum.w;
+    __syncthreads();
+    if (tid < TC && co0 + tid < a.Cout) {
+      float v = 0.f;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) v += bred[q][tid];
+      db[co0 + tid] = v;
+    }
+  }
+}
+
+// The LDS-tiled weight gradient in f16 arithmetic (the AMP training step): dW = half(G)^T . half(X) on
+// v_mfma_f32_32x32x16_f16, fp32 accumulate; db = the fp32 sum of the unrounded G.  Same workgroup shape (2 x 2 waves, 64 co x 64 ci of
+// one tap), position ranges and partial-result layout as the fp32 kernel above.  The contraction index is the position, and the f16
+// MFMA wants 8 consecutive k per lane, so the operands are transposed on their way into LDS: a loader thread fetches four channels
+// of FOUR consecutive positions (four 16-byte loads per operand and chunk of 64 positions), rounds them (v_cvt_pk_f16_f32: RNE,
+// overflow to inf, nothing clamped) and writes, per channel, its four positions as one 8-byte store into the [channel][position]
+// image.  Rows are 64 halves + 16 bytes (144: an odd number of 16-byte slots, as in conv_f16.hip), so that the one ds_read_b128
+// per operand and MFMA (lane = channel, half wave = positions 8h .. 8h + 7 of the K = 16 step) is conflict free.
+typedef _Float16 wg_f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
+typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ unsigned wg_pk_f16(float a, float b) {
+  wg_f32x2 v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wg_f16x2));   // v_cvt_pk_f16_f32 (RNE)
+}
+
+__global__ __launch_bounds__(256) void conv_backward_weights_f16_kernel(ConvBwdArgs a) {
+  constexpr int PK = 64, TC = 64, ROWB = 2 * PK + 16;
+  __shared__ __attribute__((aligned(16))) char As[TC * ROWB];     // half(G)^T: [co][position]
+  __shared__ __attribute__((aligned(16))) char Bs[TC * ROWB];     // half(X)^T: [ci][position]
+  __shared__ float bred[16][TC];
+  const int ci_tiles = (a.Cin + 63) >> 6;
+  const int tile = blockIdx.x;
+  const int co0 = (tile / ci_tiles) * 64, ci0 = (tile % ci_tiles) * 64;
+  const int tap = blockIdx.y;
+  const int ky = tap / a.KW, kx = tap - ky * a.KW;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int r = lane & 31, kh = lane >> 5;
+  const int P = a.N * a.OH * a.OW;
+  const int chunks = (P + PK - 1) / PK;
+  const int cps = (chunks + a.splits - 1) / a.splits;
+  const int c_begin = blockIdx.z * cps;
+  const int c_end = min(c_begin + cps, chunks);
+  // loader role: thread -> (positions 4 lp .. 4 lp + 3 of the chunk, channels c4 .. c4 + 3)
+  const int lp = tid >> 4, c4 = (tid & 15) * 4;
+  const bool g_ok = co0 + c4 < a.Cout, x_ok = ci0 + c4 < a.Cin;          // Cout, Cin are multiples of 32 (and of 4)
+  f32x4 gr[4], xr[4];
+  auto load_chunk = [&](int c) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int pos = c * PK + 4 * lp + i;
+      f32x4 gv = {0.f, 0.f, 0.f, 0.f}, xv = {0.f, 0.f, 0.f, 0.f};
+      if (pos < P) {
+        if (g_ok) gv = *reinterpret_cast<const f32x4*>(a.g + (size_t)pos * a.Cout + co0 + c4);
+        const int row = (int)fdiv((unsigned)pos, a.div_w);           // n * OH + oy
+        const int ox = pos - row * a.OW;
+        const int n = (int)fdiv((unsigned)row, a.div_h);
+        const int oy = row - n * a.OH;
+        const int iy = oy * a.stride + ky - a.pad, ix = ox * a.stride + kx - a.pad;
+        if (x_ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
+          xv = *reinterpret_cast<const f32x4*>(a.x + ((size_t)(n * a.H + iy) * a.W + ix) * a.Cin + ci0 + c4);
+      }
+      gr[i] = gv;
+      xr[i] = xv;
+    }
+  };
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+  f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
+  if (c_begin < c_end) load_chunk(c_begin);
+  for (int c = c_begin; c < c_end; ++c) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                                      // channel c4 + j: its four positions, rounded, 8 bytes
+      *reinterpret_cast<uint2*>(As + (c4 + j) * ROWB + lp * 8) = make_uint2(wg_pk_f16(gr[0][j], gr[1][j]), wg_pk_f16(gr[2][j], gr[3][j]));
+      *reinterpret_cast<uint2*>(Bs + (c4 + j) * ROWB + lp * 8) = make_uint2(wg_pk_f16(xr[0][j], xr[1][j]), wg_pk_f16(xr[2][j], xr[3][j]));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bsum += gr[i];                         // positions in ascending order, unrounded
+    __syncthreads();
+    if (c + 1 < c_end) load_chunk(c + 1);
+    const char* ap = As + (wm * 32 + r) * ROWB + kh * 16;
+    const char* bp = Bs + (wn * 32 + r) * ROWB + kh * 16;
+#pragma unroll
+    for (int s = 0; s < PK / 16; ++s) {
+      const wg_f16x8 af = __builtin_bit_cast(wg_f16x8, *reinterpret_cast<const uint4*>(ap + s * 32));
+      const wg_f16x8 bf = __builtin_bit_cast(wg_f16x8, *reinterpret_cast<const uint4*>(bp + s * 32));
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc, 0, 0, 0);
+    }
     __syncthreads();
   }
   // C/D layout: column (ci) = lane & 31, row (co) = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
@@ -847,6 +986,8 @@ static int wgrad_splits(int N, int H, int W, int Cin, int Cout, int KH, int KW, 
 
 extern "C" size_t eod_conv2d_backward_weights_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride) {
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || pad < 0 || stride < 1) return 0;
+  stride &= ~EOD_WGRAD_F16;                    // the f16 kernel cuts the positions like the fp32 one
+  if (stride < 1) return 0;
   const int s = wgrad_splits(N, H, W, Cin, Cout, KH, KW, pad, stride);
   return s > 1 ? (size_t)s * ((size_t)Cout * KH * KW * Cin + Cout) * sizeof(float) : 0;
 }
@@ -854,6 +995,11 @@ extern "C" size_t eod_conv2d_backward_weights_workspace_bytes(int N, int H, int 
 static int conv2d_backward_weights_impl(const float* x, const float* g, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad,
                                         int stride, float* dw, float* db, void* workspace, size_t workspace_bytes, eod_stream_t stream) {
   if (!x || !g || !dw) return EOD_ERR_NULL;
+  // EOD_WGRAD_F16 on the stride argument: the f16 kernel (32-multiple channel counts; the 4-channel stem has no f16 form)
+  const bool f16 = stride > 0 && (stride & EOD_WGRAD_F16) != 0;
+  if (stride > 0) stride &= ~EOD_WGRAD_F16;
+  if (f16 && Cin == 4) return EOD_ERR_BAD_DIMS;
+  if (f16 && (!eod_aligned16(x) || !eod_aligned16(g))) return EOD_ERR_ALIGN;
   ConvBwdArgs a{};
   const int st = conv_bwd_args(a, N, H, W, Cin == 4 ? 32 : Cin, Cout, KH, KW, pad, stride);     // Cin == 4: the stem's tap layout
   if (st != EOD_OK) return st;
@@ -870,7 +1016,10 @@ static int conv2d_backward_weights_impl(const float* x, const float* g, int N, i
       a.bpart = a.part + (size_t)a.splits * n;
     }
   }
-  if (Cin == 4 && KW <= 8)
+  if (f16)
+    hipLaunchKernelGGL(conv_backward_weights_f16_kernel, dim3(((Cout + 63) >> 6) * ((Cin + 63) >> 6), KH * KW, a.splits), dim3(256), 0,
+                       (hipStream_t)stream, a);
+  else if (Cin == 4 && KW <= 8)
     hipLaunchKernelGGL(conv_backward_weights_tap4_mfma_kernel, dim3((Cout >> 5) * KH, 1, a.splits), dim3(256), 0, (hipStream_t)stream, a);
   else if (Cin == 4)
     hipLaunchKernelGGL(conv_backward_weights_tap4_kernel, dim3(KH * KW, Cout >> 4, a.splits), dim3(1024), 0, (hipStream_t)stream, a);
@@ -1111,8 +1260,37 @@ extern "C" int eod_adamw_step_multi(const EodAdamWTensor* tensors, int count, do
                                     eod_stream_t stream) {
   if (!tensors) return EOD_ERR_NULL;
   if (count < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return EOD_ERR_BAD_DIMS;
+  // check entries (param == NULL; all entries of a call or none): the loss scaler's found-inf pass, nothing is stepped
+  int checks = 0;
+  for (int i = 0; i < count; ++i) checks += tensors[i].param ? 0 : 1;
+  if (checks) {
+    int* flag = tensors[0].found_inf;
+    if (checks != count) return EOD_ERR_BAD_DIMS;
+    if (!flag) return EOD_ERR_NULL;
+    for (int i = 0; i < count; ++i) {
+      if (!tensors[i].grad) return EOD_ERR_NULL;
+      if (tensors[i].n == 0 || tensors[i].found_inf != flag) return EOD_ERR_BAD_DIMS;
+    }
+    for (int i0 = 0; i0 < count; i0 += FINITE_MULTI) {
+      FiniteMulti f{};
+      f.count = std::min(FINITE_MULTI, count - i0);
+      f.flag = flag;
+      unsigned blocks = 0;
+      for (int k = 0; k < f.count; ++k) {
+        const EodAdamWTensor& t = tensors[i0 + k];
+        f.g[k] = t.grad; f.n[k] = t.n;
+        size_t nb = (t.n + 1023) / 1024;
+        if (nb > 1024) nb = 1024;
+        blocks += (unsigned)nb;
+        f.block_end[k] = blocks;
+      }
+      hipLaunchKernelGGL(grads_nonfinite_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, f);
+    }
+    return eod_launch_status();
+  }
   for (int i = 0; i < count; ++i) {
     const EodAdamWTensor& t = tensors[i];
+    if (t.found_inf != tensors[0].found_inf || !(t.inv_scale >= 0.f)) return EOD_ERR_BAD_DIMS;
     if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return EOD_ERR_NULL;
     if (t.n == 0 || t.step < 1 || !(t.lr >= 0.0)) return EOD_ERR_BAD_DIMS;
     if (t.folded_out && (!t.row_scale || t.cols <= 0 || t.ld_out < t.cols || t.n % (size_t)t.cols != 0)) return EOD_ERR_BAD_DIMS;
@@ -1130,6 +1308,8 @@ extern "C" int eod_adamw_step_multi(const EodAdamWTensor* tensors, int count, do
       a.p[k] = t.param; a.g[k] = t.grad; a.m[k] = t.exp_avg; a.v[k] = t.exp_avg_sq; a.n[k] = t.n;
       a.folded[k] = t.folded_out; a.row_scale[k] = t.row_scale; a.cols[k] = (unsigned)t.cols; a.ld_out[k] = (unsigned)t.ld_out;
       if (t.grad_of_folded) a.grad_of_folded |= 1u << k;
+      a.inv_scale[k] = t.inv_scale;
+      a.found_inf = t.found_inf;
       a.decay[k] = (float)(1.0 - t.lr * t.weight_decay);
       a.step_size[k] = (float)(t.lr / bc1);
       a.bc2_sqrt[k] = (float)sqrt(bc2);

@@ -14,7 +14,9 @@ rhythm (`tests/golden/mp3d_train_driver.json`).  Three things the reference's lo
   * a resumed run starts at stored iteration + 1 (:524-525) and the body adds one again: the iteration numbered stored + 1 never
     runs -- a run resumed from `model_final` written at max_iter - 1 does nothing;
   * the schedule is built from SOLVER.MAX_ITER (`build_lr_scheduler`, :519) even when SOLVER.TRAIN_ITER caps the loop (:529).
-What is not here: the AMP GradScaler (`Trainer` refuses FP16: True), TensorBoard / JSON writers (a `log` callable takes their rows at
+The AMP GradScaler (train_mp3d.py:577-578,628-631) lives in the trainer: with `FP16: True` `modeling.training.build_trainer` returns
+an `AmpTrainer`, whose `optimizer_step` is `scaler.step(optimizer); scaler.update()`; the loop logs its scale and skipped steps and
+checkpoints its state under 'scaler'.  What is not here: TensorBoard / JSON writers (a `log` callable takes their rows at
 the writers' rhythm, :647-650).  The loader's worker processes (:563-572) are `training_batches(..., workers=2)`.
 """
 from __future__ import annotations
@@ -103,8 +105,12 @@ def do_train(cfg, model, trainer, batches: Iterator[List], *, resume_state: Opti
         sched_step = int(resume_state["scheduler"]["last_epoch"])
         if resume_state.get("optimizer") is not None and hasattr(trainer, "load_optimizer_state"):
             trainer.load_optimizer_state(resume_state["optimizer"])
+        # the AMP loss scaler (`AmpTrainer.scaler`): a checkpoint without its state starts at the initial scale, as the reference does
+        if resume_state.get("scaler") and getattr(trainer, "scaler", None) is not None:
+            trainer.scaler.load_state_dict(resume_state["scaler"])
     model.train()
     rows: List[Dict] = []
+    scaler = getattr(trainer, "scaler", None)                                    # FP16: True (`AmpTrainer`): logged and checkpointed
 
     def save(name: str, iteration: int):
         if on_save is not None:
@@ -112,7 +118,8 @@ def do_train(cfg, model, trainer, batches: Iterator[List], *, resume_state: Opti
         if output_dir and base_state_dict is not None:
             opt_state = trainer.optimizer_state() if hasattr(trainer, "optimizer_state") else None
             checkpoint.save_checkpoint(os.path.join(output_dir, name), trainer.state_dict(base_state_dict), iteration,
-                                       optimizer=opt_state, scheduler={"last_epoch": sched_step})
+                                       optimizer=opt_state, scheduler={"last_epoch": sched_step},
+                                       **({"scaler": scaler.state_dict()} if scaler is not None else {}))
 
     t_data = time.perf_counter()
     for data, iteration in zip(batches, range(start_iter, max_iter)):
@@ -130,6 +137,9 @@ def do_train(cfg, model, trainer, batches: Iterator[List], *, resume_state: Opti
         trainer.optimizer_step(lr_factor=factor)
         row = {"iteration": iteration, "total_loss": total, **values, "lr": base_lr * factor, "time": time.perf_counter() - t0,
                "data_time": data_time}
+        if scaler is not None:
+            # the scale this iteration's gradients were computed with, and the optimizer steps skipped so far (non-finite gradients)
+            row.update(loss_scale=float(trainer.step_fn.grad_scale), skipped_steps=int(scaler.skipped))
         rows.append(row)
         sched_step += 1                                                          # scheduler.step() (:633)
         if do_test is not None and eval_period > 0 and iteration % eval_period == 0 and iteration != max_iter:    # :636-640

@@ -20,11 +20,17 @@ from .backbone import CustomRecurrentFPN
 
 
 class BackboneBackward:
-    def __init__(self, backbone: CustomRecurrentFPN, merge_weights: Optional[List[torch.Tensor]] = None, side_stream: bool = False):
+    def __init__(self, backbone: CustomRecurrentFPN, merge_weights: Optional[List[torch.Tensor]] = None, side_stream: bool = False,
+                 math: Optional[str] = None):
         """`merge_weights`: the three `backbone.map_merge_projection{1,2,3}.weight` tensors ([256,512,1,1] fp32 masters), needed
         only when the forward runs with a memory.  `side_stream`: the layers' weight-gradient launches go to a second stream
-        (`ops.ConvBackward`); the caller joins it (`ops.ConvBackward.join`) before it reads a dW / db."""
+        (`ops.ConvBackward`); the caller joins it (`ops.ConvBackward.join`) before it reads a dW / db.  `math="f16"`: the autocast
+        region of the AMP step -- forward, input-gradient and weight-gradient products of every convolution here take
+        their operands rounded to half, per launch; the 4-channel stem and P7 (`in_relu`) stay fp32 in all three, the map_merge
+        projections keep their own kernels."""
         self.side = bool(side_stream)
+        self.math = math
+        self._mk = {} if math is None else {"math": math}
         if backbone.feat_fusion not in ("sum", "image_only"):
             raise ValueError("the backbone's backward covers MAP_FEAT_FUSION sum / image_only (mem_only has no image gradient)")
         self.bb = backbone
@@ -35,7 +41,9 @@ class BackboneBackward:
 
     def _b(self, conv: ops.Conv) -> ops.ConvBackward:
         if id(conv) not in self._bw:
-            self._bw[id(conv)] = ops.ConvBackward(conv, side_stream=self.side)
+            # P7 reads relu(P6) (`in_relu`): its forward stays on the fp32 kernel in every arithmetic, and so does its backward
+            math = None if conv is self.bb.p7 else self.math
+            self._bw[id(conv)] = ops.ConvBackward(conv, side_stream=self.side, **({} if math is None else {"math": math}))
         return self._bw[id(conv)]
 
     # ---- forward that keeps its activations -------------------------------------------------------------------------------
@@ -47,17 +55,18 @@ class BackboneBackward:
         """-> ([p3, p4, p5] as [N,h,w,256] before the memory fusion, keep)."""
         bb = self.bb
         keep: dict = {}
-        c = bb.bottom_up.forward(x4, H, W, N, keep=keep)
+        c = bb.bottom_up.forward(x4, H, W, N, keep=keep, **self._mk)
         (c5, h5, w5), (c4, h4, w4), (c3, h3, w3) = c["layer5"], c["layer4"], c["layer3"]
         # N > 1: planned like a single image (`plan_rows`: the same split-K walk), so every image's levels are bitwise those of its
         # own N = 1 pass -- as the trunk's layers are (`ResNet50Trunk.forward`) -- and the selections behind them cannot flip
         pr = (lambda h, w: h * w) if N > 1 else (lambda h, w: 0)
-        lat5 = bb.lateral[5](c5, N, h5, w5, plan_rows=pr(h5, w5))
-        p5 = bb.output[5](lat5, N, h5, w5, plan_rows=pr(h5, w5))
-        lat4 = bb.lateral[4](c4, N, h4, w4, res=lat5, res_mode=2, plan_rows=pr(h4, w4))
-        p4 = bb.output[4](lat4, N, h4, w4, plan_rows=pr(h4, w4))
-        lat3 = bb.lateral[3](c3, N, h3, w3, res=lat4, res_mode=2, plan_rows=pr(h3, w3))
-        p3 = bb.output[3](lat3, N, h3, w3, plan_rows=pr(h3, w3))
+        mk = self._mk
+        lat5 = bb.lateral[5](c5, N, h5, w5, plan_rows=pr(h5, w5), **mk)
+        p5 = bb.output[5](lat5, N, h5, w5, plan_rows=pr(h5, w5), **mk)
+        lat4 = bb.lateral[4](c4, N, h4, w4, res=lat5, res_mode=2, plan_rows=pr(h4, w4), **mk)
+        p4 = bb.output[4](lat4, N, h4, w4, plan_rows=pr(h4, w4), **mk)
+        lat3 = bb.lateral[3](c3, N, h3, w3, res=lat4, res_mode=2, plan_rows=pr(h3, w3), **mk)
+        p3 = bb.output[3](lat3, N, h3, w3, plan_rows=pr(h3, w3), **mk)
         h6, w6 = bb.p6.out_hw(h5, w5)
         keep["fpn"] = dict(c=(c3, c4, c5), lat=(lat3, lat4, lat5), hw=((h3, w3), (h4, w4), (h5, w5), (h6, w6)))
         keep["N"], keep["x4"], keep["HW"] = N, x4, (H, W)
@@ -82,7 +91,7 @@ class BackboneBackward:
             for i, p in enumerate(P):
                 P[i] = rows[o:o + p.shape[1] * p.shape[2]].view(p.shape)
                 o += p.shape[1] * p.shape[2]
-        p6 = bb.p6(P[2], n, h5, w5)
+        p6 = bb.p6(P[2], n, h5, w5, **self._mk)
         h6, w6 = bb.p6.out_hw(h5, w5)
         p7 = bb.p7(p6, n, h6, w6, in_relu=True)
         return P + [p6, p7], dict(P=P, p6=p6, pooled=pooled, HW=(H, W))

@@ -17,8 +17,11 @@ from .backward import BackboneBackward
 
 
 class ProposalTraining:
-    def __init__(self, model, sd: Dict[str, torch.Tensor], side_stream: bool = False):
+    def __init__(self, model, sd: Dict[str, torch.Tensor], side_stream: bool = False, math: Optional[str] = None):
         """`model`: the built `CustomRCNNRecurrent`; `sd`: its state dict (fp32 masters of the parameters the step differentiates).
+        `math="f16"`: the backbone (everything `BackboneBackward` owns) runs in f16 arithmetic, per launch; `self.grad_scale` (a
+        power of two, 1.0 = off) then multiplies the five pyramid gradients where the heads' backward hands them to the backbone's:
+        bit for bit what scaling the loss gives every backbone gradient, while the heads' gradients never see the scale.
         `side_stream`: the weight-gradient launches run on a second stream beside the dgrad chain (`ops.ConvBackward`); joined at
         the end of `forward_backward`.  Measured at 640x640 (tools/train_step_bench.py, same call): the whole step 15.6 ms either
         way, the proposal half 14.0 against 10.9 ms -- two events and four `record_stream` calls per layer cost the host more than
@@ -35,7 +38,9 @@ class ProposalTraining:
             raise NotImplementedError("proposal losses: LOC_LOSS_TYPE giou, NOT_NORM_REG, no MORE_POS / NO_REDUCE (the recurrent yaml)")
         self.target_cfg = dict(strides=list(c.FPN_STRIDES), sizes_of_interest=[tuple(x) for x in c.SOI],
                                hm_min_overlap=float(c.HM_MIN_OVERLAP), min_radius=float(c.MIN_RADIUS))
-        self.bb = BackboneBackward(model.backbone, [sd[f"backbone.map_merge_projection{i}.weight"] for i in (1, 2, 3)], side_stream=self.side)
+        self.bb = BackboneBackward(model.backbone, [sd[f"backbone.map_merge_projection{i}.weight"] for i in (1, 2, 3)], side_stream=self.side,
+                                   **({} if math is None else {"math": math}))
+        self.grad_scale = 1.0
         h = "proposal_generator.centernet_head"
         w = torch.zeros((32, 256, 3, 3))
         b = torch.zeros((32,))
@@ -177,6 +182,8 @@ class ProposalTraining:
         if roi_dP is not None:
             for l, d in enumerate(roi_dP):
                 dP[l] = (dP[l] + d.view(dP[l].shape)).contiguous()
+        if self.grad_scale != 1.0:
+            dP = torch._foreach_mul([d.contiguous() for d in dP], float(self.grad_scale))       # the loss scale enters here (a power of two: exact)
         tgrads, g_out = self.bb.backward_tail(tail, dP)
         grads.update(tgrads)
         return losses, grads, g_out
@@ -216,12 +223,20 @@ class ProposalTrainer:
     packed weights in place; the trunk's convs step a raw master and are re-folded with their FrozenBatchNorm (whose weight / bias are
     buffers, not parameters: timm.py:277-299); the map_merge projections are re-prepared; the level scales go back to the decoder."""
 
+    amp = False          # `AmpTrainer`: FP16: True is its configuration, the backbone runs in f16 arithmetic under a loss scaler
+
     def __init__(self, model, sd: Dict[str, torch.Tensor], roi_heads: bool = False):
         """`roi_heads=True` (`Trainer`): `forward_model` with both halves -- the 30 tensors of the cascade's box heads / predictors
         join the optimizer and the ROI heads' losses and pyramid gradients the step."""
         from .. import solver
+        if bool(model.cfg.FP16) and not self.amp:
+            # custom_rcnn.py:607-618 runs the backbone under autocast on a half image and train_mp3d.py:577-578,628-631 scales the loss
+            # with a GradScaler; this class computes in fp32 throughout.  Silently training in another arithmetic is not an option.
+            raise NotImplementedError("FP16: True (autocast backbone + GradScaler, custom_rcnn.py:607-618, train_mp3d.py:577-631) is not "
+                                      f"what {type(self).__name__} does: its step computes in fp32.  Build the trainer with "
+                                      "`build_trainer(model, sd)` (-> `AmpTrainer`), or pass `FP16 False` to train in fp32.")
         self.model, self.dev = model, model.device
-        self.step_fn = ProposalTraining(model, sd)
+        self.step_fn = ProposalTraining(model, sd, **({"math": "f16"} if self.amp else {}))
         self.fm = ForwardModelTraining(model, sd, prop=self.step_fn) if roi_heads else None
         cfg = model.cfg
         dev = self.dev
@@ -356,11 +371,6 @@ class ProposalTrainer:
                 bw.conv.w_half = None
         self.after.append(stale_caches)
         s = cfg.SOLVER
-        if bool(cfg.FP16):
-            # custom_rcnn.py:607-618 runs the backbone under autocast on a half image and train_mp3d.py:577-578,628-631 scales the loss
-            # with a GradScaler; this step computes in fp32 throughout.  Silently training in another arithmetic is not an option.
-            raise NotImplementedError("FP16: True (autocast backbone + GradScaler, custom_rcnn.py:607-618, train_mp3d.py:577-631) is not "
-                                      "implemented: the training step computes in fp32.  Pass `FP16 False` to train in fp32.")
         if str(s.OPTIMIZER) != "ADAMW":
             raise NotImplementedError("the device optimizer is AdamW (SOLVER.OPTIMIZER ADAMW, Base-...recurrent.yaml)")
         frozen = []
@@ -696,7 +706,7 @@ class ForwardModelTraining:
 
 def _refuse_f16_training(what: str) -> None:
     """The "f16" conv arithmetic is an inference mode: the input-gradient convolutions also go through eod_conv2d and would pick it
-    up unannounced, and autocast training (FP16: True) needs half weight gradients, rounding epilogues and a loss scaler."""
+    up unannounced.  Autocast training (FP16: True) is `AmpTrainer`, which chooses the arithmetic per launch instead."""
     if ops.get_conv_math() == "f16":
         raise ValueError(f'{what} while the conv arithmetic is "f16": that mode rounds the operands of every eod_conv2d launch to half '
                          'and is for inference only; ops.set_conv_math("fp32") (or "bf16x3") before training')
@@ -818,3 +828,68 @@ class Trainer(ProposalTrainer):
             f()
         self._acc = None
         self.iteration += 1
+
+
+class AmpTrainer(Trainer):
+    """`FP16: True` (the shipped yaml): `Trainer` with the backbone's convolutions -- forward, input gradient, weight gradient -- in f16
+    arithmetic (operands rounded to half at the matrix cores, fp32 accumulate, fp32 activations in memory; the 4-channel stem, P7 and
+    the map_merge projections as DESIGN 9.3 says) and `torch.amp.GradScaler`'s loss scaling (custom_rcnn.py:607-618,
+    train_mp3d.py:577-578,628-631).  The arithmetic is chosen per launch: the process-wide mode of `ops.set_conv_math` is not touched,
+    and its "f16" value stays refused here as for every trainer.
+
+    The scale multiplies the pyramid gradients on their way into the backbone's backward (`ProposalTraining.grad_scale`); the
+    optimizer's launch multiplies the backbone's gradients by 1 / scale again, and skips itself on the device when the found-inf pass
+    over all gradients has set its flag.  The host reads that flag once per iteration, after the step has been enqueued, for what it
+    keeps itself: step counts, the scale, the hooks that follow a step."""
+    amp = True
+
+    def __init__(self, model, sd: Dict[str, torch.Tensor], scaler: Optional[ops.LossScaler] = None):
+        super().__init__(model, sd)
+        self.scaler = scaler if scaler is not None else ops.LossScaler()
+        self._found_inf = torch.zeros((1,), dtype=torch.int32, device=self.dev)
+        # the tensors whose gradients come out of the backbone's backward carry the scale; the heads' never see it
+        self._scaled = [g["name"].startswith("backbone.") for g in self.groups]
+        self.last_step_skipped = False
+
+    def forward_backward_frames(self, batched_inputs, generator: Optional[torch.Generator] = None):
+        self.step_fn.grad_scale = self.scaler.get_scale()
+        return super().forward_backward_frames(batched_inputs, generator=generator)
+
+    def step(self, image_u8, gt_boxes, memory=None, lr_factor: float = 1.0, gt_classes=None, proposals=None, keys=None, generator=None):
+        """One iteration on one frame (`ProposalTrainer.step` under the scaler)."""
+        self.step_fn.grad_scale = self.scaler.get_scale()
+        losses, grads = self.fm.forward_backward(image_u8, gt_boxes, gt_classes, memory=memory, proposals=proposals, keys=keys,
+                                                 generator=generator)
+        self._acc = [self.step_getters[g["name"]](grads) for g in self.groups]
+        self.optimizer_step(lr_factor=lr_factor)
+        return losses
+
+    def optimizer_step(self, lr_factor: float = 1.0):
+        """`scaler.step(optimizer); scaler.update()` (train_mp3d.py:629-631) on the gradients of the last `forward_backward_frames`:
+        found-inf pass over every gradient, unscale inside the optimizer's launch, skip on a non-finite value."""
+        _refuse_f16_training("optimizer_step")
+        if self._acc is None:
+            raise RuntimeError("optimizer_step without gradients: call forward_backward_frames (or model(data) in training mode) first")
+        acc, self._acc = self._acc, None
+        scale = float(self.step_fn.grad_scale)
+        inv = [1.0 / scale if (s and scale != 1.0) else 0.0 for s in self._scaled]
+        self._found_inf.zero_()
+        self.opt.nonfinite(acc, self._found_inf)
+        self.opt.step(acc, lr_factor=lr_factor, inv_scale=inv, found_inf=self._found_inf)
+        # One 4-byte read-back per iteration, after the step is enqueued.  It cannot ride on the speculation check of the frames: the
+        # gradients it covers are the sum over all frames of the iteration, complete only behind the last frame's read-back.
+        # (Multi-rank training, which train_mp3d refuses today, would all-reduce the flag here, before the optimizer's launch.)
+        found = bool(self._found_inf.cpu()[0])
+        self.last_step_skipped = found
+        if found:
+            self.opt.rewind(acc)                # the launch skipped itself: parameters, moments, folded and rotated weights untouched
+        else:
+            for f in self.after:
+                f()
+            self.iteration += 1
+        self.scaler.update(found)
+
+
+def build_trainer(model, sd: Dict[str, torch.Tensor]):
+    """The trainer of the model's configuration: `AmpTrainer` with `FP16: True` (the shipped yaml), else `Trainer`."""
+    return AmpTrainer(model, sd) if bool(model.cfg.FP16) else Trainer(model, sd)

@@ -59,6 +59,7 @@ _conv_ws = Workspace()
 # weight preparation (host, once per model build)
 # ----------------------------------------------------------------------------------------------------
 _CONV_MATH = {"fp32": 0, "bf16x3": 1, "f16": 2}
+WGRAD_F16 = 512      # EOD_WGRAD_F16 of include/eod_hip.h: on the stride argument of eod_conv2d_backward_weights_ws
 
 
 def set_conv_math(mode: str) -> str:
@@ -68,7 +69,8 @@ def set_conv_math(mode: str) -> str:
     if mode not in _CONV_MATH:
         hint = ""
         if str(mode).lower() == "fp16":
-            hint = ' ("fp16" / FP16 is the config key of autocast training, which is not implemented; the inference arithmetic is "f16")'
+            hint = (' ("fp16" / FP16 is the config key of autocast training: modeling.training.build_trainer / AmpTrainer, which choose '
+                    'the arithmetic per launch; the process-wide inference arithmetic is "f16")')
         raise ValueError(f"conv math must be one of {sorted(_CONV_MATH)}, got {mode!r}{hint}")
     prev = _lib.load().eod_set_conv_math(_CONV_MATH[mode])
     check(min(prev, 0), "eod_set_conv_math")
@@ -146,8 +148,10 @@ class Conv:
                  fuse: Optional[Tuple[torch.Tensor, float, Optional[torch.Tensor]]] = None, presplit: bool = True,
                  plan_rows: int = 0, gn_stats: Optional[torch.Tensor] = None, gn_groups: int = 32,
                  split: Optional[Tuple[int, torch.Tensor]] = None, m_segments: int = 0,
-                 gate: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 gate: Optional[torch.Tensor] = None, math: Optional[str] = None) -> torch.Tensor:
         """`levels=(row_offsets, [(h, w), ...])` runs the layer once over a whole feature pyramid stored as one row list.
+        `math` ("fp32" | "bf16x3" | "f16"; None = the process-wide mode of `set_conv_math`): the arithmetic of THIS call
+        (EodConvDesc.math) -- the AMP training step runs the backbone's launches in f16 beside fp32 heads this way.
         `split=(n0, out2)`: the layer is two stacked linear layers; columns [0, n0) go to `out` [rows, n0] without the ReLU, columns
         [n0, Cout) to `out2` [rows, Cout - n0] with it (EodConvDesc.split_n).
         `m_segments` = B: the N images are B unit lists back to back, `m_count` holds B counts (EodConvDesc.m_segments).
@@ -173,6 +177,9 @@ class Conv:
         d.x, d.w, d.bias, d.res, d.y = x.data_ptr(), self.w.data_ptr(), _ptr(self.bias), _ptr(res), out.data_ptr()
         d.m_count, d.m_unit, d.m_segments = _ptr(m_count), m_unit, int(m_segments)
         d.gate = _ptr(gate)
+        if math is not None and math not in _CONV_MATH:
+            raise ValueError(f"math={math!r}: one of {sorted(_CONV_MATH)} or None")
+        d.math = 0 if math is None else _CONV_MATH[math] + 1
         d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout = N, H, W, self.Cin, OH, OW, self.Cout
         d.KH, d.KW, d.stride, d.pad, d.Kpad = self.KH, self.KW, self.stride, self.pad, self.Kpad
         d.relu, d.res_mode, d.in_relu, d.out_mode, d.tap4 = int(relu), res_mode, int(in_relu), self.out_mode, self.tap4
@@ -200,14 +207,15 @@ class Conv:
                 d.level_h[i], d.level_w[i] = h, w
         else:
             d.levels = 0
-        use_split = force_tile // 10 == 5 if force_tile else (get_conv_math() == "bf16x3")
+        mode = math if math is not None else get_conv_math()
+        use_split = force_tile // 10 == 5 if force_tile else (mode == "bf16x3")
         if use_split and self.w_split is None and not self.tap4:
             nb = self._lib.eod_conv_split_weights_bytes(self.Cout, self.Kpad)
             self.w_split = torch.empty((nb,), dtype=torch.uint8, device=self.w.device)
             check(self._lib.eod_conv_split_weights_bf16x3(self.w.data_ptr(), self.Cout, self.Kpad, self.w_split.data_ptr(), _stream()),
                   f"eod_conv_split_weights_bf16x3[{self.name}]")
         d.w_split = self.w_split.data_ptr() if (use_split and self.w_split is not None and presplit) else None
-        use_half = force_tile // 10 in (8, 9) if force_tile else (get_conv_math() == "f16")
+        use_half = force_tile // 10 in (8, 9) if force_tile else (mode == "f16")
         if use_half and self.w_half is None and not self.tap4:
             nb = self._lib.eod_conv_half_weights_bytes(self.Cout, self.Kpad)
             self.w_half = torch.empty((nb,), dtype=torch.uint8, device=self.w.device)
@@ -682,9 +690,16 @@ class ConvBackward:
                 st[1] = ev
         return ctx()
 
-    def __init__(self, conv: "Conv", side_stream: bool = False):
+    def __init__(self, conv: "Conv", side_stream: bool = False, math: Optional[str] = None):
+        """`math` ("f16" or None = as before): the arithmetic of this layer's backward -- "f16" hands the input-gradient convolution
+        (zero-insert form included) `math="f16"` and takes the weight gradient from the f16 kernel (EOD_WGRAD_F16); the 4-channel
+        stem's weight gradient and the pyramid-mode weight gradient have no f16 form and stay fp32."""
         if conv.out_mode != 0:
             raise ValueError("ConvBackward covers plain convolutions (no deconv)")
+        if math not in (None, "fp32", "f16"):
+            raise ValueError(f"ConvBackward(math={math!r}): None, 'fp32' or 'f16'")
+        self.math = None if math == "fp32" else math
+        self._mk = {} if self.math is None else {"math": self.math}        # what the dgrad conv's call gets on top
         self.side_stream = bool(side_stream)
         # stride-1 'same' layers: dX on the matrix cores (eod_conv2d with rotated weights); anything else: the gather kernel
         self.same = conv.stride == 1 and conv.KH == conv.KW and conv.pad * 2 == conv.KH - 1
@@ -745,7 +760,8 @@ class ConvBackward:
                                                           ws.numel() * 4 if need else 0, _stream()), "eod_conv2d_backward_weights_levels")
         dx = None
         if need_dx:
-            dx = self._dgrad_conv()(g, 1, 0, 0, levels=(off, shapes), res=dx_res, res_mode=1 if dx_res is not None else 0, gate=dx_gate)
+            dx = self._dgrad_conv()(g, 1, 0, 0, levels=(off, shapes), res=dx_res, res_mode=1 if dx_res is not None else 0, gate=dx_gate,
+                                    **self._mk)
         return dict(dx=dx, dw=dw, db=db)
 
     @staticmethod
@@ -793,7 +809,8 @@ class ConvBackward:
             ws = ConvBackward._workspace.get(x.device)
             if need and (ws is None or ws.numel() * 4 < need):
                 ws = ConvBackward._workspace[x.device] = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=x.device)
-            check(self.lib.eod_conv2d_backward_weights_ws(x.data_ptr(), g.data_ptr(), N, H, W, c.Cin, c.Cout, c.KH, c.KW, c.pad, c.stride,
+            stride = c.stride | WGRAD_F16 if (self.math == "f16" and not c.tap4) else c.stride
+            check(self.lib.eod_conv2d_backward_weights_ws(x.data_ptr(), g.data_ptr(), N, H, W, c.Cin, c.Cout, c.KH, c.KW, c.pad, stride,
                                                           dw.data_ptr(), db.data_ptr(), ws.data_ptr() if need else None,
                                                           ws.numel() * 4 if need else 0, _stream()), "eod_conv2d_backward_weights_ws")
             return dw, db
@@ -818,7 +835,7 @@ class ConvBackward:
         # `dx_res` (a second gradient of x: the skip connection's) and `dx_gate` (the ReLU output x came out of: its backward) ride
         # on the input-gradient convolution's epilogue: dx = relu'(dx_gate) * (conv(g) + dx_res) in one launch
         dx = None
-        tail = dict(res=dx_res, res_mode=1 if dx_res is not None else 0, gate=dx_gate)
+        tail = dict(res=dx_res, res_mode=1 if dx_res is not None else 0, gate=dx_gate, **self._mk)
         if need_dx and self.same:
             dx = self._dgrad_conv()(g, N, H, W, **tail)
         elif need_dx and self.zero_insert:
@@ -1058,8 +1075,14 @@ class AdamW:
             self.state[i][0].copy_(e["exp_avg"])
             self.state[i][1].copy_(e["exp_avg_sq"])
 
-    def step(self, grads: Sequence[Optional[torch.Tensor]], lr_factor: float = 1.0):
-        """`grads[i]`: gradient of group i's tensor (None: no gradient this iteration, the tensor is skipped as torch does)."""
+    def step(self, grads: Sequence[Optional[torch.Tensor]], lr_factor: float = 1.0, inv_scale: Optional[Sequence[float]] = None,
+             found_inf: Optional[torch.Tensor] = None):
+        """`grads[i]`: gradient of group i's tensor (None: no gradient this iteration, the tensor is skipped as torch does).
+        `inv_scale[i]` (0 = off): the gradient is multiplied by it inside the launch, before the fold's chain rule and the clipping
+        (a loss scaler's unscale); `found_inf` (device int32 [1]): the launch leaves everything untouched when it is non-zero.  The
+        step COUNTS are advanced here either way: a caller that skips takes them back with `rewind(grads)`."""
+        if (inv_scale is not None or found_inf is not None) and not self.multi_tensor:
+            raise ValueError("inv_scale / found_inf ride on the multi-tensor launch (multi_tensor = True)")
         if self.multi_tensor:
             n = 0
             for i, (g, grad) in enumerate(zip(self.groups, grads)):
@@ -1080,6 +1103,8 @@ class AdamW:
                     d.grad_of_folded = 1 if g.get("grad_of_folded") else 0
                 else:
                     d.folded_out, d.row_scale, d.cols, d.ld_out, d.grad_of_folded = None, None, 0, 0, 0
+                d.inv_scale = 0.0 if inv_scale is None else float(inv_scale[i])
+                d.found_inf = _ptr(found_inf)
                 n += 1
             if n:
                 check(self.lib.eod_adamw_step_multi(self._descs, n, self.betas[0], self.betas[1], self.eps, self.clip_value, _stream()),
@@ -1101,6 +1126,78 @@ class AdamW:
                                           self.clip_value, _stream()), "eod_adamw_step")
             if g.get("fold") is not None:
                 g["fold"][0][:, :p.shape[1]].copy_(p * g["fold"][1].view(-1, 1))
+
+
+    def rewind(self, grads: Sequence[Optional[torch.Tensor]]) -> None:
+        """Takes back the step counts of a `step(grads, found_inf=...)` whose launch skipped itself (the flag was set)."""
+        for i, grad in enumerate(grads):
+            if grad is not None:
+                self.steps[i] -= 1
+
+    def nonfinite(self, grads: Sequence[Optional[torch.Tensor]], flag: torch.Tensor) -> None:
+        """The loss scaler's found-inf pass: `flag` (device int32 [1], zeroed by the caller) becomes 1 when any element of any
+        gradient is inf or NaN -- the check entries of `eod_adamw_step_multi`, ceil(n / 32) launches, nothing read back."""
+        live = [g for g in grads if g is not None]
+        if not live:
+            return
+        descs = (_lib.EodAdamWTensor * len(live))()
+        for d, g in zip(descs, live):
+            _need_cuda(g)
+            assert g.dtype == torch.float32 and g.is_contiguous()
+            d.grad, d.n, d.found_inf = g.data_ptr(), g.numel(), flag.data_ptr()
+        check(self.lib.eod_adamw_step_multi(descs, len(live), self.betas[0], self.betas[1], self.eps, 0.0, _stream()), "eod_adamw_step_multi[check]")
+
+
+class LossScaler:
+    """`torch.amp.GradScaler`'s scale schedule on the host (train_mp3d.py:577-578,628-631): the scale starts at `init_scale`, a step
+    whose gradients held an inf / NaN multiplies it by `backoff_factor` (and is skipped by the caller), `growth_interval` clean steps
+    in a row multiply it by `growth_factor`.  `state_dict` uses torch's key names, so the two load each other's."""
+
+    def __init__(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000,
+                 enabled: bool = True):
+        if growth_factor <= 1.0 or not (0.0 < backoff_factor < 1.0):
+            raise ValueError("growth_factor > 1 and 0 < backoff_factor < 1 (torch.amp.GradScaler)")
+        # fp32 like torch's device scalar: the products below round as `_amp_update_scale_` does
+        self._scale = float(np.float32(init_scale))
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self._growth_tracker = 0
+        self.enabled = bool(enabled)
+        self.skipped = 0                 # steps skipped so far (reporting)
+
+    def get_scale(self) -> float:
+        return self._scale if self.enabled else 1.0
+
+    def update(self, found_inf: bool) -> None:
+        """`scaler.update()` after a step whose found-inf pass returned `found_inf` (`_amp_update_scale_`)."""
+        if not self.enabled:
+            return
+        if found_inf:
+            self._scale = float(np.float32(self._scale) * np.float32(self.backoff_factor))
+            self._growth_tracker = 0
+            self.skipped += 1
+            return
+        self._growth_tracker += 1
+        if self._growth_tracker == self.growth_interval:
+            with np.errstate(over="ignore"):
+                grown = np.float32(self._scale) * np.float32(self.growth_factor)
+            if np.isfinite(grown):                      # torch keeps the old scale when the growth would overflow fp32
+                self._scale = float(grown)
+            self._growth_tracker = 0
+
+    def state_dict(self) -> Dict:
+        if not self.enabled:
+            return {}
+        return {"scale": self._scale, "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": self._growth_tracker}
+
+    def load_state_dict(self, sd: Dict) -> None:
+        if not self.enabled:
+            return
+        if not sd:
+            raise RuntimeError("the loss scaler's state is empty (saved by a disabled scaler)")
+        self._scale = float(np.float32(sd["scale"]))
+        self.growth_factor, self.backoff_factor = float(sd["growth_factor"]), float(sd["backoff_factor"])
+        self.growth_interval, self._growth_tracker = int(sd["growth_interval"]), int(sd["_growth_tracker"])
 
 
 class MemoryWriter:

@@ -94,7 +94,7 @@ def do_train(cfg, args, rank: int, world: int):
     from . import build_model
     from .checkpoint import fill_missing, load_checkpoint, synthetic_state_dict
     from .engine import train_loop
-    from .modeling.training import Trainer
+    from .modeling.training import build_trainer
     if world > 1:
         raise NotImplementedError("the MP3D training loader runs on one process (train_mp3d.py:552-553: world_size = 1)")
     num_classes = int(cfg.MODEL.ROI_HEADS.NUM_CLASSES)
@@ -112,7 +112,7 @@ def do_train(cfg, args, rank: int, world: int):
     else:
         sd = synthetic_state_dict(0, num_classes, cfg.MODEL.ROI_BOX_HEAD.ZEROSHOT_WEIGHT_PATH)
     model = build_model(cfg, sd)
-    trainer = Trainer(model, sd)
+    trainer = build_trainer(model, sd)              # FP16: True (the shipped yaml) -> AmpTrainer, else the fp32 Trainer
     data_root = str(cfg.MODEL.TRAIN_DATA_PATH)
     ims = max(int(cfg.SOLVER.IMS_PER_BATCH) // world, 1)
     if os.path.isdir(os.path.join(data_root, "memory_data")) and os.path.isdir(os.path.join(data_root, "sensor_data")):

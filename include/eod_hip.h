@@ -125,6 +125,12 @@ typedef struct EodConvDesc {
   /* optional: the same weights rounded to binary16 for the f16 kernels (eod_conv_half_weights), Cout * Kpad * 2 bytes; the f16
    * kernels copy it instead of fetching and rounding w per tile (same values either way); ignored by every other kernel */
   const void* w_half;
+  /* arithmetic of THIS call when force_tile == 0: 0 = the process-wide mode (eod_set_conv_math / EOD_CONV_MATH) as before, else
+   * EOD_MATH_* + 1 (1 fp32, 2 bf16x3, 3 f16): the AMP training step runs the backbone's forward and input-gradient launches in f16
+   * arithmetic beside fp32 heads without touching the process-wide mode.  A gated launch (`gate`) of an f16 call runs the f16
+   * 64x64 tile with the gated epilogue (split-K slabs keep the fp32 gated reduce); in the process-wide f16 mode and in bf16x3
+   * arithmetic gated launches stay on the fp32 kernel as before. */
+  int32_t math;
 } EodConvDesc;
 int eod_conv2d(const EodConvDesc* d, eod_stream_t stream);
 int eod_conv2d_gn_fused(const EodConvDesc* d); /* 1 when this layer can carry gn_partial (its plan has a slab reduce), else 0 */
@@ -527,6 +533,13 @@ int eod_conv2d_backward_weights(const float* x, const float* g, int N, int H, in
 size_t eod_conv2d_backward_weights_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride);
 int eod_conv2d_backward_weights_ws(const float* x, const float* g, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad,
                                    int stride, float* dw, float* db, void* workspace, size_t workspace_bytes, eod_stream_t stream);
+/* f16 arithmetic for eod_conv2d_backward_weights_ws (the AMP training step): pass `stride | EOD_WGRAD_F16`.  Both
+ * operands are rounded to binary16 (IEEE round-to-nearest-even, |v| > 65504 -> inf, nothing clamped) as they are staged, the exact
+ * products summed in fp32 on v_mfma_f32_32x32x16_f16:  dW[co][(ky,kx,ci)] = sum_pos half(G)[pos][co] * half(X)[pos'][ci];  db is the
+ * fp32 sum of the UNROUNDED G.  Same position ranges, workspace size and range-order reduce as the fp32 form: deterministic.  Cin and
+ * Cout multiples of 32 (the 4-channel stem has no f16 form: EOD_ERR_BAD_DIMS), x and g 16-byte aligned.  A flag on an argument
+ * rather than an entry point of its own, like force_tile's variants: the table of entry points stays as it is. */
+#define EOD_WGRAD_F16 512
 /* Pyramid mode (the weight gradient of a level-shared layer, centernet_head.py:141-161, in one launch): x [rows, Cin] / g [rows, Cout]
  * are row lists, rows [level_off[l], level_off[l+1]) an level_h[l] x level_w[l] image (levels <= 8); stride 1, pad = (KH - 1) / 2;
  * dW / db are summed over the levels.  The workspace (optional, as above) holds the position ranges' partial results. */
@@ -590,6 +603,15 @@ typedef struct EodAdamWTensor {
   /* 1: `grad` is the gradient of the FOLDED weights; the master's = grad x row_scale[row] (chain rule of the fold), applied before the
    * clipping.  Needs row_scale and cols. */
   int32_t grad_of_folded;
+  /* 0 = off, else the gradient is multiplied by it first (before the fold's chain rule and the clipping): the unscale of a loss
+   * scaler, 1 / scale, for the tensors whose gradients were computed on the scaled loss */
+  float inv_scale;
+  /* loss scaler's found-inf flag, a device int32 (NULL = off; the same pointer in every tensor of a call).
+   *   check entries (param == NULL; all tensors of a call or none): nothing is stepped; *found_inf is set to 1 when any element of
+   *     any `grad` is inf or NaN and left alone otherwise (the caller zeroes it) -- ceil(count / 32) launches;
+   *   step entries: the whole update is skipped ON THE DEVICE when *found_inf != 0 (parameters, moments and folded_out untouched:
+   *     GradScaler.step), so the host may read the flag back after it has enqueued the step instead of before. */
+  int32_t* found_inf;
 } EodAdamWTensor;
 int eod_adamw_step_multi(const EodAdamWTensor* tensors, int count, double beta1, double beta2, double eps, double clip_value,
                          eod_stream_t stream);

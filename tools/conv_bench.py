@@ -77,7 +77,52 @@ def modes(name, N, H, W, Cin, Cout, k, stride, pad, iters=30):
           f" x{cols[0][1] / us16:.2f} of fp32, x{cols[1][1] / us16:.2f} of bf16x3", flush=True)
 
 
+def backward(name, N, H, W, Cin, Cout, k, stride, pad, iters=20):
+    """One backbone layer's backward in fp32 and in f16 arithmetic (`ops.ConvBackward(conv, math=)`): the weight-gradient launch alone
+    (reduce of the position ranges included) and the gated + residual input-gradient launch alone."""
+    conv = ops.Conv(torch.randn((Cout, Cin, k, k), generator=g) * 0.05, torch.zeros(Cout), stride=stride, pad=pad, device=dev)
+    OH, OW = conv.out_hw(H, W)
+    x = torch.relu(torch.randn((N, H, W, Cin), generator=g)).to(dev)
+    gr = torch.randn((N, OH, OW, Cout), generator=g).to(dev)
+    res = torch.randn((N, H, W, Cin), generator=g).to(dev)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters * 1e3
+    t = {}
+    for math in (None, "f16"):
+        bw = ops.ConvBackward(conv, math=math)
+        both = timed(lambda: bw(x, None, gr, dx_res=res, dx_gate=x))
+        wg = timed(lambda: bw(x, None, gr, need_dx=False))
+        t[math] = (wg, both - wg, bw._flipped.plan())
+    p32, p16 = t[None][2], t["f16"][2]
+    kern = lambda p: ("f16 " if p["glds"] == 3 else "") + (f"wave-K {p['wavek']}" if p["wavek"] else f"{p['bm']}x{p['bn']}") + (f" sk{p['splitk']}" if p["splitk"] > 1 else "")
+    print(f"{name:26s} wgrad fp32 {t[None][0]:7.1f} us  f16 {t['f16'][0]:7.1f} us  x{t[None][0] / t['f16'][0]:.2f} | gated dgrad fp32 {t[None][1]:7.1f} us "
+          f"({kern(p32)})  f16 {t['f16'][1]:7.1f} us ({kern(p16)})  x{t[None][1] / t['f16'][1]:.2f}", flush=True)
+
+
 which = sys.argv[1] if len(sys.argv) > 1 else "all"
+if which == "backward":
+    # the backbone's layers of one 640x640 training step: weight gradient and gated input gradient, fp32 against f16 arithmetic
+    for sh in [("l1 conv1 1x1 256->64", 1, 160, 160, 256, 64, 1, 1, 0), ("l1 conv2 3x3 64->64", 1, 160, 160, 64, 64, 3, 1, 1),
+               ("l1 conv3 1x1 64->256", 1, 160, 160, 64, 256, 1, 1, 0), ("l2 conv1 1x1 512->128", 1, 80, 80, 512, 128, 1, 1, 0),
+               ("l2 conv2 3x3 128->128", 1, 80, 80, 128, 128, 3, 1, 1), ("l2 conv2 3x3 s2 (block 0)", 1, 160, 160, 128, 128, 3, 2, 1),
+               ("l2 conv3 1x1 128->512", 1, 80, 80, 128, 512, 1, 1, 0), ("l2 downsample 1x1 s2", 1, 160, 160, 256, 512, 1, 2, 0),
+               ("l3 conv1 1x1 1024->256", 1, 40, 40, 1024, 256, 1, 1, 0), ("l3 conv2 3x3 256->256", 1, 40, 40, 256, 256, 3, 1, 1),
+               ("l3 conv3 1x1 256->1024", 1, 40, 40, 256, 1024, 1, 1, 0), ("l4 conv1 1x1 2048->512", 1, 20, 20, 2048, 512, 1, 1, 0),
+               ("l4 conv2 3x3 512->512", 1, 20, 20, 512, 512, 3, 1, 1), ("l4 conv3 1x1 512->2048", 1, 20, 20, 512, 2048, 1, 1, 0),
+               ("fpn lateral3 1x1 512->256", 1, 80, 80, 512, 256, 1, 1, 0), ("fpn out3 3x3 256 80x80", 1, 80, 80, 256, 256, 3, 1, 1),
+               ("fpn out5 3x3 256 20x20", 1, 20, 20, 256, 256, 3, 1, 1), ("p6 3x3 s2 256 20x20", 1, 20, 20, 256, 256, 3, 2, 1)]:
+        backward(*sh)
+    sys.exit(0)
 if which == "modes":
     # the layers of one 640x640 frame (ResNet-50 trunk, FPN, tower, box and mask heads) in fp32 / bf16x3 / f16 arithmetic
     for sh in [("l1 conv1 1x1 256->64", 1, 160, 160, 256, 64, 1, 1, 0), ("l1 conv2 3x3 64->64", 1, 160, 160, 64, 64, 3, 1, 1),
