@@ -178,6 +178,141 @@ __global__ __launch_bounds__(256) void zs_classify_kernel(const float* __restric
   if (lane < C1) mem_scores[(size_t)row * C1 + lane] = (p < 1.0f) ? sqrtf(eod_sigmoid_precise(logit) * p) : 0.0f;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Wide vocabularies (EOD_ZS_WIDE, 25 <= C1 <= 2048): the class matrix no longer fits LDS, the classifier is a small GEMM
+// [rows, 512] x [512, C1] on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products and sums).
+// ------------------------------------------------------------------------------------------------------
+// One workgroup per tile of 32 rows x 32 classes (LVIS, 256 rows: 8 x 38 workgroups), its four waves split K = 512 into quarters and
+// the partial tiles are summed through LDS in wave order.  Lane l = (i = l & 31, h = l >> 5) of wave w owns channels
+// k(s) = 128 w + 64 h + s, s = 0..63: the A operand is 64 consecutive floats of row i (16 loads of 16 bytes, normalised in registers),
+// the B operand zs[k(s)][c0 + i] is read as the matrix lies (32 consecutive floats per channel: coalesced, no transpose, no padding).
+// The prologue is the narrow kernel's, instruction for instruction (one wave per row, 8 channels per lane, butterfly): the
+// denominators and feat_norm_out are bitwise the narrow kernel's.  Workgroups blockIdx.y == gridDim.y - 1 are the stage's BoxTail
+// (box_tail_row, the narrow kernel's own code: same bits) when there is one, so the tail costs no launch and no classifier tile waits
+// for it.
+// mode 0: classifier epilogue (sigmoid, accumulate, final fusion); 1: memory re-score of raw features; 2: memory re-score of
+// already normalised features (eod_memory_scores).
+constexpr int ZS_WIDE_MAX_C1 = 2048;
+
+__global__ __launch_bounds__(256) void zs_wide_kernel(const float* __restrict__ feat, const float* __restrict__ zs, float* __restrict__ out,
+                                                       int accumulate, float* __restrict__ featn_out, const int* __restrict__ count,
+                                                       int R_cap, int C1, float temp, const float* __restrict__ prop_scores,
+                                                       float final_inv_stages, int batch, int mode, int class_tiles, BoxTail tail) {
+  EOD_CHAIN_PRIO();
+  __shared__ float sh_den[32];                  // denominator of the tile's rows; < 0: the row holds no work
+  __shared__ float red[4][32 * 32];             // the four K-quarters' partial tiles
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.x * 32;
+  const int rows_all = R_cap * batch;
+  {
+    const int r = row0 + (lane & 31);
+    if (__ballot(r < rows_all && row_has_work(count, R_cap, r)) == 0ull) return;      // whole tile beyond its lists' counts
+  }
+  if ((int)blockIdx.y >= class_tiles) {          // the BoxTail workgroups: one wave per row, eight rows per wave
+    if (!tail.hb) return;
+    for (int j = 0; j < 8; ++j) {
+      const int row = row0 + wave * 8 + j;
+      if (row < rows_all && row_has_work(count, R_cap, row)) box_tail_row(tail, row, lane);
+    }
+    return;
+  }
+  const int c0 = blockIdx.y * 32;
+  // ---- prologue: the rows' denominators (and feat_norm_out, by the first class tile)
+  for (int j = 0; j < 8; ++j) {
+    const int row = row0 + wave * 8 + j;
+    const bool active = row < rows_all && row_has_work(count, R_cap, row);     // wave-uniform
+    float denom = -1.0f;
+    if (active) {
+      denom = 1.0f;
+      if (mode != 2) {
+        float x[8];
+        float ss = 0.f;
+        {
+          const f32x4 a = *reinterpret_cast<const f32x4*>(feat + (size_t)row * 512 + lane * 8);
+          const f32x4 b = *reinterpret_cast<const f32x4*>(feat + (size_t)row * 512 + lane * 8 + 4);
+          x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) ss += x[q] * x[q];
+        ss = wave_reduce_sum(ss);
+        denom = fmaxf(sqrtf(ss), 1e-12f);
+        if (featn_out && blockIdx.y == 0) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) x[q] = temp * (x[q] / denom);
+          *reinterpret_cast<f32x4*>(featn_out + (size_t)row * 512 + lane * 8) = f32x4{x[0], x[1], x[2], x[3]};
+          *reinterpret_cast<f32x4*>(featn_out + (size_t)row * 512 + lane * 8 + 4) = f32x4{x[4], x[5], x[6], x[7]};
+        }
+      }
+    }
+    if (lane == 0) sh_den[wave * 8 + j] = denom;
+  }
+  __syncthreads();
+  // ---- operands
+  const int i = lane & 31, h = lane >> 5;
+  const int kbase = wave * 128 + h * 64;
+  const float den = sh_den[i];
+  float xa[64];
+  if (den >= 0.f) {
+    const float* src = feat + (size_t)(row0 + i) * 512 + kbase;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * q);
+      xa[4 * q + 0] = v.x; xa[4 * q + 1] = v.y; xa[4 * q + 2] = v.z; xa[4 * q + 3] = v.w;
+    }
+    if (mode != 2) {
+#pragma unroll
+      for (int s = 0; s < 64; ++s) xa[s] = temp * (xa[s] / den);
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < 64; ++s) xa[s] = 0.f;
+  }
+  const int cb = c0 + i;                         // this lane's class column of the B operand
+  const bool cok = cb < C1;
+  const float* zb = zs + (size_t)kbase * C1 + (cok ? cb : 0);
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+#pragma unroll
+  for (int s0 = 0; s0 < 64; s0 += 16) {
+    float bv[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) bv[s] = cok ? zb[(size_t)(s0 + s) * C1] : 0.f;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[s0 + s], bv[s], acc, 0, 0, 0);
+  }
+  // ---- the quarters' sum, in wave order: C/D layout col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+  for (int q = 0; q < 16; ++q) red[wave][((q & 3) + 8 * (q >> 2) + 4 * h) * 32 + i] = acc[q];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = tid + 256 * q;
+    const int ri = e >> 5, c = c0 + (e & 31);
+    const int row = row0 + ri;
+    if (sh_den[ri] < 0.f || c >= C1) continue;
+    const float logit = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+    float* o = out + (size_t)row * C1 + c;
+    if (mode == 0) {
+      const float p = eod_sigmoid_precise(logit);
+      float v = accumulate ? (*o + p) : p;
+      if (final_inv_stages > 0.f) v = sqrtf(v * final_inv_stages * prop_scores[row]);      // cascade score fusion
+      *o = v;
+    } else {
+      const float p = prop_scores[row];
+      *o = (p < 1.0f) ? sqrtf(eod_sigmoid_precise(logit) * p) : 0.0f;
+    }
+  }
+}
+
+static void launch_zs_wide(hipStream_t s, const float* feat, const float* zs, float* out, int accumulate, float* featn_out, const int* count,
+                           int R_cap, int C1, float temp, const float* prop_scores, float final_inv_stages, int nb, int mode,
+                           const BoxTail& tail) {
+  const int class_tiles = (C1 + 31) / 32;
+  hipLaunchKernelGGL(zs_wide_kernel, dim3((R_cap * nb + 31) / 32, class_tiles + (tail.hb ? 1 : 0)), dim3(256), 0, s, feat, zs, out,
+                     accumulate, featn_out, count, R_cap, C1, temp, prop_scores, final_inv_stages, nb, mode, class_tiles, tail);
+}
+
 __global__ void apply_deltas_kernel(const float* __restrict__ deltas, int ld, const float* __restrict__ boxes, float* __restrict__ out,
                                     const int* __restrict__ count, int R_cap, float wx, float wy, float ww, float wh, int clip,
                                     float img_w, float img_h, int batch) {
@@ -345,11 +480,21 @@ extern "C" int eod_zs_classify(const float* feat, const float* zs, float* prob_a
   // the class matrix is staged in 48 KB of LDS: vocabularies of more than ZS_MAX_C - 1 classes (RESET_CLS_TESTS) are refused here
   // with a capacity error that ops.zs_classify words out
   if (D != 512 || C1 < 2 || R_cap <= 0) return EOD_ERR_BAD_DIMS;
-  if (C1 > ZS_MAX_C) return EOD_ERR_CAPACITY;
+  // wider vocabularies run the matrix-core kernel, for the caller that asks for it (EOD_ZS_WIDE)
+  const bool wide = (accumulate & EOD_ZS_WIDE) != 0;
+  accumulate &= 1;
+  if (C1 > ZS_MAX_C && (!wide || C1 > ZS_WIDE_MAX_C1)) return EOD_ERR_CAPACITY;
   if (!eod_aligned16(feat) || (feat_norm_out && !eod_aligned16(feat_norm_out)) || !eod_aligned16(zs) || (zs_mem && !eod_aligned16(zs_mem)))
     return EOD_ERR_ALIGN;
   if (batch > 1 && (batch > EOD_MAX_BATCH || R_cap % 4 != 0)) return EOD_ERR_BAD_DIMS;
   const int nb = batch > 1 ? batch : 1;
+  if (C1 > ZS_MAX_C) {
+    launch_zs_wide((hipStream_t)stream, feat, zs, prob_acc, accumulate, feat_norm_out, count, R_cap, C1, temp, prop_scores, final_inv_stages,
+                   nb, 0, BoxTail{});
+    if (zs_mem)      // the memory re-score with a matrix of the same width: a second launch of the same kernel
+      launch_zs_wide((hipStream_t)stream, feat, zs_mem, mem_scores_out, 0, nullptr, count, R_cap, C1, temp, prop_scores, 0.f, nb, 1, BoxTail{});
+    return eod_launch_status();
+  }
   hipLaunchKernelGGL(zs_classify_kernel, dim3((R_cap * nb + 3) / 4), dim3(256), 0, (hipStream_t)stream, feat, zs, prob_acc, accumulate,
                      feat_norm_out, count, R_cap, D, C1, temp, zs_mem, prop_scores, mem_scores_out, final_inv_stages, nb, BoxTail{});
   return eod_launch_status();
@@ -361,7 +506,9 @@ extern "C" int eod_cascade_stage_tail(const EodStageTailDesc* d, eod_stream_t st
   if (d->final_inv_stages > 0.f && !d->prop_scores) return EOD_ERR_NULL;
   if (d->D != 512 || d->C1 < 2 || d->R_cap <= 0 || d->hb_dim <= 0 || d->hb_dim % 16 != 0 || d->w2_ld < d->hb_dim || d->w2_ld % 4 != 0)
     return EOD_ERR_BAD_DIMS;
-  if (d->C1 > ZS_MAX_C) return EOD_ERR_CAPACITY;
+  const bool wide = (d->accumulate & EOD_ZS_WIDE) != 0;
+  const int accumulate = d->accumulate & 1;
+  if (d->C1 > ZS_MAX_C && (!wide || d->C1 > ZS_WIDE_MAX_C1)) return EOD_ERR_CAPACITY;
   if (!eod_aligned16(d->feat) || (d->feat_norm_out && !eod_aligned16(d->feat_norm_out)) || !eod_aligned16(d->zs) ||
       (d->zs_mem && !eod_aligned16(d->zs_mem)) || !eod_aligned16(d->hb) || !eod_aligned16(d->w2))
     return EOD_ERR_ALIGN;
@@ -369,8 +516,16 @@ extern "C" int eod_cascade_stage_tail(const EodStageTailDesc* d, eod_stream_t st
   const int nb = d->batch > 1 ? d->batch : 1;
   BoxTail t{d->hb, d->w2, d->b2, d->hb_dim, d->w2_ld, d->boxes_in, d->boxes_out, d->deltas_out, d->wx, d->wy, d->ww, d->wh,
             d->clip, d->img_w, d->img_h};
+  if (d->C1 > ZS_MAX_C) {
+    launch_zs_wide((hipStream_t)stream, d->feat, d->zs, d->prob_acc, accumulate, d->feat_norm_out, d->count, d->R_cap, d->C1, d->temp,
+                   d->prop_scores, d->final_inv_stages, nb, 0, t);
+    if (d->zs_mem)
+      launch_zs_wide((hipStream_t)stream, d->feat, d->zs_mem, d->mem_scores_out, 0, nullptr, d->count, d->R_cap, d->C1, d->temp,
+                     d->prop_scores, 0.f, nb, 1, BoxTail{});
+    return eod_launch_status();
+  }
   hipLaunchKernelGGL(zs_classify_kernel, dim3((d->R_cap * nb + 3) / 4), dim3(256), 0, (hipStream_t)stream, d->feat, d->zs, d->prob_acc,
-                     d->accumulate, d->feat_norm_out, d->count, d->R_cap, d->D, d->C1, d->temp, d->zs_mem, d->prop_scores,
+                     accumulate, d->feat_norm_out, d->count, d->R_cap, d->D, d->C1, d->temp, d->zs_mem, d->prop_scores,
                      d->mem_scores_out, d->final_inv_stages, nb, t);
   return eod_launch_status();
 }
@@ -398,6 +553,12 @@ extern "C" int eod_memory_scores(const float* featn, const float* zs, const floa
                                  int R_cap, int D, int C1, eod_stream_t stream) {
   if (!featn || !zs || !prop_scores || !scores) return EOD_ERR_NULL;
   if (D != 512 || C1 < 2 || R_cap <= 0) return EOD_ERR_BAD_DIMS;
+  if (C1 > ZS_MAX_C) {      // wide memory matrix (the default configuration's is LVIS): the matrix-core kernel on the normalised rows
+    if (C1 > ZS_WIDE_MAX_C1) return EOD_ERR_CAPACITY;
+    if (!eod_aligned16(featn)) return EOD_ERR_ALIGN;
+    launch_zs_wide((hipStream_t)stream, featn, zs, scores, 0, nullptr, count, R_cap, C1, 1.0f, prop_scores, 0.f, 1, 2, BoxTail{});
+    return eod_launch_status();
+  }
   hipLaunchKernelGGL(memory_scores_kernel, dim3((R_cap + 3) / 4), dim3(256), 0, (hipStream_t)stream, featn, zs, prop_scores, scores,
                      count, R_cap, D, C1);
   return eod_launch_status();

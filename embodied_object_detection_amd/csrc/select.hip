@@ -1286,6 +1286,535 @@ __global__ __launch_bounds__(256) void concat_lists_kernel(const int* __restrict
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
+// ------------------------------------------------------------------------------------------------------
+// fast_rcnn_inference for wide vocabularies (more than DET_MAX_C classes or more than 8192 slots): three launches
+// ------------------------------------------------------------------------------------------------------
+// The [R, C1] score matrix (LVIS: 256 x 1204) no longer fits one workgroup's registers and C suppressed-row sets no longer fit
+// LDS.  The pieces of det_select_kernel carry over -- 64-bit (score, slot) keys, the histogram cut on the score bits, the in-LDS
+// sort, the R x R row-IoU bit matrix that turns per-class NMS into bit tests -- in this shape:
+//   (a) detw_hist_kernel, two rows per workgroup over the whole chip: finite-row flags, threshold, the scene's histogram of the
+//       candidates' score bins (workspace), and the scene's suppressed-row sets cleared;
+//   (b) detw_compact_kernel, same grid: every workgroup derives the same cut from the histogram -- the lowest bin whose suffix
+//       holds at most DETW_BATCH candidates -- and appends its rows' keys of the bins above the cut to the scene's list;
+//   (c) detw_tail_kernel, one workgroup per scene: sorts the list (a prefix of the fully sorted candidates), runs the per-class greedy
+//       NMS on it, ranks the kept entries and takes the first topk.  If the list is not full and candidates are left it fetches the
+//       NEXT DETW_BATCH keys below the last one itself -- a radix select over the 64-bit keys by re-scanning the score matrix, up to
+//       six histogram scans and one collecting scan: slow, rare, and exactly the greedy NMS over the fully sorted list -- and goes
+//       on, with the suppressed-row sets of the classes kept in the workspace between batches.
+// The hand-over between (a), (b) and (c) is the kernel boundary.  (c) leaves the histogram and the list's counter zeroed: the
+// workspace has to be zero before the first call only (ops.DetectionSelector allocates it so); no memset per call.
+// NMS inside a batch: a second sort by (class, position in the batch) makes every class's entries a contiguous run in score order;
+// one LANE per run walks it with the class's suppressed-row set in 8 registers (test bit r, OR row r of the IoU matrix when kept).
+#define DETW_MAX_C 2047
+#define DETW_BATCH 4096            // keys per sorted batch
+#define DETW_WANT 2048             // the first cut aims at this many candidates (and takes up to DETW_BATCH)
+
+struct DetwWs {
+  int* hist;           // [nb][4096]
+  int* cand_cnt;       // [nb]
+  unsigned char* row_ok;   // [nb][DET_MAX_R]
+  u64* cand;           // [nb][DETW_BATCH]
+  u64* supp;           // [nb][C][DET_WORDS]
+  size_t bytes;
+};
+
+DetwWs carve_detw(void* base, int C, int nb) {
+  DetwWs w{};
+  size_t off = 0;
+  char* b = static_cast<char*>(base);
+  auto take = [&](size_t bytes) {
+    char* p = b ? b + off : nullptr;
+    off += align_up(bytes);
+    return p;
+  };
+  w.hist = reinterpret_cast<int*>(take((size_t)nb * 4096 * sizeof(int)));
+  w.cand_cnt = reinterpret_cast<int*>(take((size_t)EOD_MAX_BATCH * sizeof(int)));
+  w.row_ok = reinterpret_cast<unsigned char*>(take((size_t)nb * DET_MAX_R));
+  w.cand = reinterpret_cast<u64*>(take((size_t)nb * DETW_BATCH * sizeof(u64)));
+  w.supp = reinterpret_cast<u64*>(take((size_t)nb * C * DET_WORDS * sizeof(u64)));
+  w.bytes = off;
+  return w;
+}
+
+__device__ __forceinline__ int detw_rows(const int* count, int scene, int R_cap) {
+  int R = R_cap;
+  if (count) {
+    const int c = count[scene];
+    R = c < R ? (c < 0 ? 0 : c) : R;
+  }
+  return R;
+}
+
+// (a): grid (ceil(R_cap / 2), scenes), 256 threads; a thread holds up to 8 scores of the workgroup's current row
+__global__ __launch_bounds__(256) void detw_hist_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                         const int* __restrict__ count, int R_cap, int C1, float thr, DetwWs ws) {
+  EOD_CHAIN_PRIO();
+  const int scene = blockIdx.y, tid = threadIdx.x;
+  const int C = C1 - 1;
+  const int R = detw_rows(count, scene, R_cap);
+  boxes += (size_t)scene * R_cap * 4;
+  scores += (size_t)scene * R_cap * C1;
+  // this workgroup's share of the scene's suppressed-row sets (read by (c) only when a selection needs a second batch)
+  {
+    u64* supp = ws.supp + (size_t)scene * C * DET_WORDS;
+    const int n = C * DET_WORDS;
+    for (int i = blockIdx.x * 256 + tid; i < n; i += gridDim.x * 256) supp[i] = 0ull;
+  }
+  __shared__ int sh_fin;
+  for (int rr = 0; rr < 2; ++rr) {
+    const int r = blockIdx.x * 2 + rr;
+    if (r >= R_cap) break;                                   // workgroup-uniform
+    if (tid == 0) sh_fin = 1;
+    __syncthreads();
+    float sc[8];
+    bool fin = true;
+    if (r < R) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = tid + 256 * e;
+        sc[e] = c < C1 ? scores[(size_t)r * C1 + c] : 0.f;
+        fin = fin & (bool)isfinite(sc[e]);
+      }
+      if (tid < 4) fin = fin & (bool)isfinite(boxes[r * 4 + tid]);
+    } else {
+      fin = false;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sc[e] = 0.f;
+    }
+    if (!fin) sh_fin = 0;
+    __syncthreads();
+    const bool ok = sh_fin != 0;                             // the box and ALL scores of the row are finite
+    if (tid == 0) ws.row_ok[(size_t)scene * DET_MAX_R + r] = ok ? 1 : 0;
+    if (ok) {
+      int* hist = ws.hist + (size_t)scene * 4096;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = tid + 256 * e;
+        if (c < C && sc[e] > thr) atomicAdd(&hist[score_bin(__float_as_uint(sc[e]))], 1);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the cut of a scene: the lowest bin whose suffix holds at most DETW_BATCH candidates, going down until DETW_WANT are covered.
+// 256 threads, 16 bins each; every workgroup of (b) and the tail workgroup compute the same value from the same histogram.
+// Returns the cut (0..4096; 4096 = no bin fits) and the scene's candidate count through *total.
+__device__ __forceinline__ int detw_cut(const int* __restrict__ hist, int* sh_wsum /*[4]*/, int* sh_out /*[1]*/, int* total) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int h[16], mine = 0;
+  if (tid < 256) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      h[j] = hist[tid * 16 + j];
+      mine += h[j];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) h[j] = 0;
+  }
+  int inc = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_down(inc, off, 64);
+    if (lane + off < 64) inc += t;
+  }
+  if (tid == 0) *sh_out = 4096;
+  if (lane == 0 && wave < 4) sh_wsum[wave] = inc;
+  __syncthreads();
+  int after = 0;
+  for (int w = wave + 1; w < 4; ++w) after += sh_wsum[w];
+  *total = sh_wsum[0] + sh_wsum[1] + sh_wsum[2] + sh_wsum[3];
+  if (tid < 256) {
+    // suffix counts of this thread's bins; a bin b is "takeable" iff suffix(b) <= DETW_BATCH; the cut is the lowest takeable bin
+    // that is still needed: suffix(b + 1) < DETW_WANT
+    int suf = after + inc - mine;                            // candidates in the bins above this thread's
+    int best = 4096;
+#pragma unroll
+    for (int j = 15; j >= 0; --j) {
+      const int above = suf;
+      suf += h[j];
+      if (suf <= DETW_BATCH && above < DETW_WANT && h[j] > 0) best = tid * 16 + j;
+    }
+    if (best < 4096) atomicMin(sh_out, best);
+  }
+  __syncthreads();
+  return *sh_out;
+}
+
+// (b): same grid as (a)
+__global__ __launch_bounds__(256) void detw_compact_kernel(const float* __restrict__ scores, const int* __restrict__ count, int R_cap,
+                                                            int C1, float thr, DetwWs ws) {
+  EOD_CHAIN_PRIO();
+  const int scene = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int C = C1 - 1;
+  __shared__ int sh_wsum[4], sh_out;
+  int total;
+  const int cut = detw_cut(ws.hist + (size_t)scene * 4096, sh_wsum, &sh_out, &total);
+  if (cut >= 4096) return;                                   // nothing to take on the fast path
+  scores += (size_t)scene * R_cap * C1;
+  u64* cand = ws.cand + (size_t)scene * DETW_BATCH;
+  for (int rr = 0; rr < 2; ++rr) {
+    const int r = blockIdx.x * 2 + rr;
+    if (r >= R_cap || !ws.row_ok[(size_t)scene * DET_MAX_R + r]) continue;      // workgroup-uniform
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = tid + 256 * e;
+      float v = -1.f;
+      if (c < C) v = scores[(size_t)r * C1 + c];
+      const bool in = c < C && v > thr && score_bin(__float_as_uint(v)) >= cut;
+      const u64 bal = __ballot(in);
+      if (!bal) continue;
+      int base = 0;
+      if (lane == 0) base = atomicAdd(&ws.cand_cnt[scene], __popcll(bal));
+      base = __shfl(base, 0, 64);
+      const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+      if (in && pos >= 0 && pos < DETW_BATCH) cand[pos] = make_key(v, (unsigned)(r * C + c));
+    }
+  }
+}
+
+// One scan of the scene's score matrix by the tail workgroup: calls f(key) for every candidate (finite row, score > thr).
+template <typename F>
+__device__ __forceinline__ void detw_scan(const float* __restrict__ scores, const unsigned char* row_ok, int R, int C, int C1, float thr, F f) {
+  for (int r = 0; r < R; ++r) {
+    if (!row_ok[r]) continue;
+    for (int c = threadIdx.x; c < C; c += 1024) {
+      const float v = scores[(size_t)r * C1 + c];
+      if (v > thr) f(make_key(v, (unsigned)(r * C + c)));
+    }
+  }
+}
+
+// (c): one workgroup per scene
+__global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, const float* scores, const int* count, int R_cap, int C1,
+                                                          float img_w, float img_h, float thr, float nms_thresh, int topk, DetwWs ws,
+                                                          ScanOut o) {
+  EOD_CHAIN_PRIO();
+  const int scene = blockIdx.x;
+  boxes += (size_t)scene * R_cap * 4;
+  scores += (size_t)scene * R_cap * C1;
+  o = scene_outputs(o, scene);
+  int* g_hist = ws.hist + (size_t)scene * 4096;
+  const u64* g_cand = ws.cand + (size_t)scene * DETW_BATCH;
+  const int C = C1 - 1;
+  u64* g_supp = ws.supp + (size_t)scene * C * DET_WORDS;
+  __shared__ u64 buf[DETW_BATCH];                  // the batch's keys, sorted descending
+  __shared__ u64 comp[DETW_BATCH];                 // the batch's entries ordered by (class, position)
+  __shared__ u64 Mx[DET_MAX_R * DET_WORDS];        // IoU bit matrix of the rows
+  __shared__ float cbx[DET_MAX_R * 4];             // clipped boxes
+  __shared__ int hist[4096];
+  __shared__ int segstart[DETW_MAX_C + 1];
+  __shared__ u64 kept_key[NMS_KEPT_MAX];
+  __shared__ int flag[NMS_KEPT_MAX];
+  __shared__ u64 keptbits[DETW_BATCH / 64];
+  __shared__ int wordpre[DETW_BATCH / 64];
+  __shared__ int wsum[16];
+  __shared__ unsigned char row_ok[DET_MAX_R];
+  __shared__ int sh_wsum[4], sh_out, sh_n2, sh_nseg, sh_total, sh_done, sh_kept_all;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int R = detw_rows(count, scene, R_cap);
+  const int W = (R + 63) >> 6;
+  int n_all;
+  const int cut = detw_cut(g_hist, sh_wsum, &sh_out, &n_all);
+  (void)cut;
+  __syncthreads();
+  // the list (b) left, and the workspace as the next call expects it
+  int n2 = ws.cand_cnt[scene];
+  n2 = n2 < 0 ? 0 : (n2 > DETW_BATCH ? DETW_BATCH : n2);
+  for (int i = tid; i < n2; i += 1024) buf[i] = g_cand[i];
+  for (int i = tid; i < 4096; i += 1024) g_hist[i] = 0;
+  for (int r = tid; r < DET_MAX_R; r += 1024) {
+    const bool in = r < R;
+    row_ok[r] = in ? ws.row_ok[(size_t)scene * DET_MAX_R + r] : 0;
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+    if (in) {
+      b0 = boxes[r * 4 + 0]; b1 = boxes[r * 4 + 1]; b2 = boxes[r * 4 + 2]; b3 = boxes[r * 4 + 3];
+    }
+    cbx[r * 4 + 0] = fminf(fmaxf(b0, 0.f), img_w);
+    cbx[r * 4 + 1] = fminf(fmaxf(b1, 0.f), img_h);
+    cbx[r * 4 + 2] = fminf(fmaxf(b2, 0.f), img_w);
+    cbx[r * 4 + 3] = fminf(fmaxf(b3, 0.f), img_h);
+  }
+  if (tid == 0) {
+    sh_total = 0;
+    sh_done = 0;
+  }
+  __syncthreads();
+  if (tid == 0) ws.cand_cnt[scene] = 0;
+  // IoU bit matrix: all DET_WORDS words of a row are written (zero beyond the rows in use)
+  for (int idx = tid; idx < R * DET_WORDS; idx += 1024) {
+    const int r = idx / DET_WORDS, w = idx - r * DET_WORDS;
+    u64 bits = 0;
+    if (w < W) {
+      const float x1 = cbx[r * 4 + 0], y1 = cbx[r * 4 + 1], x2 = cbx[r * 4 + 2], y2 = cbx[r * 4 + 3];
+      const float area = (x2 - x1) * (y2 - y1);
+      for (int b = 0; b < 64; ++b) {
+        const int r2 = w * 64 + b;
+        if (r2 < R && r2 != r &&
+            iou_over(x1, y1, x2, y2, area, cbx[r2 * 4 + 0], cbx[r2 * 4 + 1], cbx[r2 * 4 + 2], cbx[r2 * 4 + 3], nms_thresh))
+          bits |= 1ull << b;
+      }
+    }
+    Mx[idx] = bits;
+  }
+  __syncthreads();
+  int processed = 0;                 // candidates of the batches walked so far
+  u64 bound = ~0ull;                 // every key of the batches walked so far is >= bound; the next batch lies below it
+  for (int round = 0;; ++round) {
+    if (round > 0 || n2 == 0) {
+      // ---- the next DETW_BATCH keys below `bound`: radix select by re-scanning the score matrix
+      if (processed >= n_all) break;                         // uniform
+      u64 lo = 0;                    // the interval searched is [lo, lo + 2^(s + w)), below `bound`
+      int acc = 0;                   // keys accepted so far: those of the interval's upper neighbours below `bound`
+      u64 T = 0;
+      int sft = 52, wid = 12;
+      for (int level = 0; level < 6; ++level) {
+        for (int i = tid; i < 4096; i += 1024) hist[i] = 0;
+        __syncthreads();
+        const int top = sft + wid;
+        detw_scan(scores, row_ok, R, C, C1, thr, [=](u64 k) {
+          if (k < bound && (top >= 64 || (k >> top) == (lo >> top))) atomicAdd(&hist[(int)((k >> sft) & ((1u << wid) - 1u))], 1);
+        });
+        __syncthreads();
+        // the smallest digit d with acc + suffix(d) <= DETW_BATCH (4096 = none of this interval)
+        if (tid == 0) sh_out = 4096;
+        int h4[4], mine = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          h4[j] = hist[tid * 4 + j];
+          mine += h4[j];
+        }
+        int inc = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const int t = __shfl_down(inc, off, 64);
+          if (lane + off < 64) inc += t;
+        }
+        if (lane == 0) wsum[wave] = inc;
+        __syncthreads();
+        int suf = inc - mine;
+        for (int w = wave + 1; w < 16; ++w) suf += wsum[w];
+        int best = 4096;
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+          suf += h4[j];
+          if (acc + suf <= DETW_BATCH) best = tid * 4 + j;
+        }
+        if (best < 4096) atomicMin(&sh_out, best);
+        __syncthreads();
+        const int d = sh_out;
+        // suffix(d): every thread sums the bins it owns that are >= d, then the workgroup total
+        int part = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (tid * 4 + j >= d) part += h4[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+        __syncthreads();
+        if (lane == 0) wsum[wave] = part;
+        __syncthreads();
+        int sufd = 0;
+        for (int w = 0; w < 16; ++w) sufd += wsum[w];
+        __syncthreads();
+        acc += sufd;
+        T = (d >= 4096 && top >= 64) ? ~0ull : lo + ((u64)d << sft);        // (no bin of the whole key range fits: nothing)
+        if (d == 0 || acc >= 1024 || sft == 0) break;        // uniform
+        lo += (u64)(d - 1) << sft;                           // descend into the bin that did not fit as a whole
+        if (sft >= 16) {
+          sft -= 12;
+        } else {
+          sft = 0;
+          wid = 4;
+        }
+      }
+      // collect T <= key < bound
+      if (tid == 0) sh_n2 = 0;
+      __syncthreads();
+      detw_scan(scores, row_ok, R, C, C1, thr, [=](u64 k) {
+        if (k < bound && k >= T) {
+          const int pos = atomicAdd(&sh_n2, 1);
+          if (pos < DETW_BATCH) buf[pos] = k;
+        }
+      });
+      __syncthreads();
+      n2 = sh_n2 < DETW_BATCH ? sh_n2 : DETW_BATCH;
+      __syncthreads();
+      if (n2 == 0) break;                                    // cannot happen while candidates are left; never spin
+    }
+    if (n2 <= 1024) sort_in_place<1>(buf, n2);
+    else if (n2 <= 2048) sort_in_place<2>(buf, n2);
+    else sort_in_place<4>(buf, n2);
+    // ---- entries by (class ascending, position ascending): descending sort of ((2047 - class) << 16 | (0xFFFF - position))
+    for (int q = tid; q < n2; q += 1024) {
+      const int slot = (int)key_index(buf[q]);
+      const int r = slot / C, cl = slot - r * C;
+      comp[q] = ((u64)(2047 - cl) << 16) | (u64)(0xFFFF - q);
+    }
+    for (int i = tid; i < DETW_BATCH / 64; i += 1024) keptbits[i] = 0;
+    if (tid == 0) sh_nseg = 0;
+    __syncthreads();
+    if (n2 <= 1024) sort_in_place<1>(comp, n2);
+    else if (n2 <= 2048) sort_in_place<2>(comp, n2);
+    else sort_in_place<4>(comp, n2);
+    for (int q = tid; q < n2; q += 1024) {
+      if (q == 0 || (comp[q] >> 16) != (comp[q - 1] >> 16)) {
+        const int pos = atomicAdd(&sh_nseg, 1);
+        if (pos <= DETW_MAX_C) segstart[pos] = q;
+      }
+    }
+    __syncthreads();
+    const int nseg = sh_nseg <= DETW_MAX_C ? sh_nseg : DETW_MAX_C;
+    // ---- per-class greedy NMS: one lane per class run (the order of the runs does not matter, classes are independent)
+    for (int sgi = tid; sgi < nseg; sgi += 1024) {
+      const int q0 = segstart[sgi];
+      const u64 ctag = comp[q0] >> 16;
+      int cl = 2047 - (int)ctag;
+      cl = cl < 0 ? 0 : (cl >= C ? C - 1 : cl);
+      u64 w[DET_WORDS];
+#pragma unroll
+      for (int j = 0; j < DET_WORDS; ++j) w[j] = g_supp[(size_t)cl * DET_WORDS + j];         // cleared by (a), carried from batch to batch
+      for (int p = q0; p < n2; ++p) {
+        const u64 ce = comp[p];
+        if ((ce >> 16) != ctag) break;
+        int q = 0xFFFF - (int)(ce & 0xFFFFull);
+        q = q < 0 ? 0 : (q >= n2 ? n2 - 1 : q);
+        int r = (int)key_index(buf[q]) / C;
+        r = r < 0 ? 0 : (r >= DET_MAX_R ? DET_MAX_R - 1 : r);
+        u64 word = 0;
+#pragma unroll
+        for (int j = 0; j < DET_WORDS; ++j) word = (j == (r >> 6)) ? w[j] : word;
+        if (!((word >> (r & 63)) & 1ull)) {
+          atomicOr(&keptbits[q >> 6], 1ull << (q & 63));
+#pragma unroll
+          for (int j = 0; j < DET_WORDS; ++j)
+            if (j < W) w[j] |= Mx[r * DET_WORDS + j];       // (the words beyond W are zero; the guard keeps the loads few)
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < DET_WORDS; ++j) g_supp[(size_t)cl * DET_WORDS + j] = w[j];
+    }
+    __syncthreads();
+    // ---- rank of every kept entry in list order; the first (topk - total) of them are taken
+    {
+      const int nwords = (n2 + 63) >> 6;                     // <= 64: one wave
+      if (tid < 64) {
+        const int pc = tid < nwords ? __popcll(keptbits[tid]) : 0;
+        int inc = pc;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const int t = __shfl_up(inc, off, 64);
+          if (lane >= off) inc += t;
+        }
+        wordpre[tid] = inc - pc;
+        if (lane == 63) sh_kept_all = inc;
+      }
+      __syncthreads();
+      const int total0 = sh_total;
+      for (int q = tid; q < n2; q += 1024) {
+        const u64 wbits = keptbits[q >> 6];
+        if ((wbits >> (q & 63)) & 1ull) {
+          const int pos = total0 + wordpre[q >> 6] + __popcll(wbits & ((1ull << (q & 63)) - 1ull));
+          if (pos < topk && pos < NMS_KEPT_MAX) kept_key[pos] = buf[q];
+        }
+      }
+      __syncthreads();
+      if (tid == 0) {
+        int total = total0 + sh_kept_all;
+        const bool full = total >= topk;
+        if (full) total = topk;
+        sh_total = total;
+        sh_done = (full || processed + n2 >= n_all) ? 1 : 0;
+      }
+    }
+    const u64 last = buf[n2 - 1];
+    __syncthreads();
+    if (sh_done) break;
+    processed += n2;
+    bound = last;
+  }
+  __syncthreads();
+  int total = sh_total;
+  if (total > o.cap) total = o.cap;
+  if (total > NMS_KEPT_MAX) total = NMS_KEPT_MAX;
+  if (tid == 0 && o.out_count) *o.out_count = total;
+  int my_row = -1;
+  if (tid < total) {
+    const u64 k = kept_key[tid];
+    const int slot = (int)key_index(k);
+    int r = slot / C;
+    const int cl = slot - r * C;
+    r = r < 0 ? 0 : (r >= DET_MAX_R ? DET_MAX_R - 1 : r);
+    my_row = r;
+    if (o.out_boxes) {
+      o.out_boxes[tid * 4 + 0] = cbx[r * 4 + 0];
+      o.out_boxes[tid * 4 + 1] = cbx[r * 4 + 1];
+      o.out_boxes[tid * 4 + 2] = cbx[r * 4 + 2];
+      o.out_boxes[tid * 4 + 3] = cbx[r * 4 + 3];
+    }
+    if (o.out_scores) o.out_scores[tid] = key_score(k);
+    if (o.out_labels) o.out_labels[tid] = cl;
+    if (o.out_rows) o.out_rows[tid] = r;
+  }
+  if (o.rep_of) {
+    // entries of one source row carry the same box: the first of them represents the group (the mask head is class agnostic)
+    if (tid < NMS_KEPT_MAX) flag[tid] = 0x7FFFFFFF;
+    __syncthreads();
+    if (tid < total && my_row >= 0 && my_row < NMS_KEPT_MAX) atomicMin(&flag[my_row], tid);
+    __syncthreads();
+    int is_rep = 0;
+    if (tid < total) {
+      const int rep = (my_row >= 0 && my_row < NMS_KEPT_MAX) ? flag[my_row] : tid;
+      o.rep_of[tid] = rep;
+      is_rep = rep == tid;
+    }
+    u64 rb = 0;
+    if (tid < NMS_KEPT_MAX) {
+      rb = __ballot(is_rep != 0);
+      if (lane == 0) wsum[wave] = __popcll(rb);
+    }
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
+      const int cw = wsum[w];
+      if (w < wave) before += cw;
+      all += cw;
+    }
+    if (tid < NMS_KEPT_MAX && is_rep) o.rep_list[before + __popcll(rb & ((1ull << lane) - 1ull))] = tid;
+    if (tid == 0) *o.rep_count = all;
+    __syncthreads();
+  }
+  if (o.uniq_rows) {
+    // torch.unique of the kept rows: flags over the row ids (< NMS_KEPT_MAX), ballot compaction, ascending
+    if (tid < NMS_KEPT_MAX) flag[tid] = 0;
+    __syncthreads();
+    if (tid < total && my_row >= 0 && my_row < NMS_KEPT_MAX) flag[my_row] = 1;
+    __syncthreads();
+    int f = 0;
+    u64 fb = 0;
+    if (tid < NMS_KEPT_MAX) {
+      f = flag[tid];
+      fb = __ballot(f != 0);
+      if (lane == 0) wsum[wave] = __popcll(fb);
+    }
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
+      const int cw = wsum[w];
+      if (w < wave) before += cw;
+      all += cw;
+    }
+    if (tid < NMS_KEPT_MAX && f) {
+      const int pos = before + __popcll(fb & ((1ull << lane) - 1ull));
+      if (pos < o.uniq_cap) o.uniq_rows[pos] = tid;
+    }
+    if (tid == 0 && o.uniq_count) *o.uniq_count = all < o.uniq_cap ? all : o.uniq_cap;
+  }
+}
+
+
 struct SelWs {
   float* sorted_boxes;
   float* sorted_scores;
@@ -1440,7 +1969,12 @@ extern "C" int eod_centernet_proposals(const EodProposalDesc* d, eod_stream_t st
   return eod_launch_status();
 }
 
+// the wide path takes over beyond the single-workgroup kernel's classes or slots
+static bool det_is_wide(int R_cap, int C1) { return C1 - 1 > DET_MAX_C || (long long)R_cap * (C1 - 1) > 8192; }
+
 extern "C" size_t eod_detections_workspace_bytes(int R_cap, int C1) {
+  if (R_cap <= 0 || R_cap > DET_MAX_R || C1 < 2 || C1 - 1 > DETW_MAX_C) return 0;
+  if (det_is_wide(R_cap, C1)) return carve_detw(nullptr, C1 - 1, EOD_MAX_BATCH).bytes;
   const int slots = R_cap * (C1 - 1);
   return carve(nullptr, slots, slots, 0).bytes;
 }
@@ -1449,10 +1983,27 @@ extern "C" int eod_fast_rcnn_inference(const EodDetDesc* d, eod_stream_t stream)
   if (!d || !d->boxes || !d->scores || !d->out_boxes || !d->out_scores || !d->out_classes || !d->out_rows || !d->out_count ||
       !d->workspace)
     return EOD_ERR_NULL;
-  if (d->R_cap <= 0 || d->R_cap > DET_MAX_R || d->C1 < 2 || d->C1 - 1 > DET_MAX_C || d->topk <= 0 || d->topk > NMS_KEPT_MAX)
+  if (d->R_cap <= 0 || d->R_cap > DET_MAX_R || d->C1 < 2 || d->C1 - 1 > DETW_MAX_C || d->topk <= 0 || d->topk > NMS_KEPT_MAX)
     return EOD_ERR_BAD_DIMS;
+  if (det_is_wide(d->R_cap, d->C1)) {
+    const int nb = d->batch > 1 ? d->batch : 1;
+    if (nb > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
+    const DetwWs w = carve_detw(d->workspace, d->C1 - 1, EOD_MAX_BATCH);
+    if (d->workspace_bytes < w.bytes) return EOD_ERR_CAPACITY;
+    if (d->out_unique_rows && (!d->out_unique_count || d->unique_cap <= 0)) return EOD_ERR_BAD_DIMS;
+    if (d->out_rep_of && (!d->out_rep_list || !d->out_rep_count)) return EOD_ERR_BAD_DIMS;
+    if (!eod_aligned16(d->workspace)) return EOD_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    ScanOut o{d->out_boxes, d->out_scores, d->out_classes, d->out_rows, d->out_count, d->topk, d->out_unique_rows, d->out_unique_count,
+              d->unique_cap, d->out_rep_of, d->out_rep_list, d->out_rep_count};
+    const dim3 grid((d->R_cap + 1) / 2, nb);
+    hipLaunchKernelGGL(detw_hist_kernel, grid, dim3(256), 0, s, d->boxes, d->scores, d->count, d->R_cap, d->C1, d->score_thresh, w);
+    hipLaunchKernelGGL(detw_compact_kernel, grid, dim3(256), 0, s, d->scores, d->count, d->R_cap, d->C1, d->score_thresh, w);
+    hipLaunchKernelGGL(detw_tail_kernel, dim3(nb), dim3(1024), 0, s, d->boxes, d->scores, d->count, d->R_cap, d->C1, d->img_w, d->img_h,
+                       d->score_thresh, d->nms_thresh, d->topk, w, o);
+    return eod_launch_status();
+  }
   const int slots = d->R_cap * (d->C1 - 1);
-  if (slots > 8192) return EOD_ERR_CAPACITY;
   const SelWs w = carve(d->workspace, slots, slots, 0);
   if (d->workspace_bytes < w.bytes) return EOD_ERR_CAPACITY;
   hipStream_t s = (hipStream_t)stream;

@@ -15,11 +15,51 @@ import numpy as np
 import torch
 
 
+# `--vocabulary` of the reference's predictor (predictor.py:33-37): CLIP text matrices under datasets/metadata/
+BUILDIN_CLASSIFIER = {
+    "lvis": "datasets/metadata/lvis_v1_clip_a+cname.npy",
+    "objects365": "datasets/metadata/o365_clip_a+cnamefix.npy",
+    "openimages": "datasets/metadata/oid_clip_a+cname.npy",
+    "coco": "datasets/metadata/coco_clip_a+cname.npy",
+    "mp3d": "datasets/metadata/mp3d_clip.npy",
+}
+
+
+def resolve_vocabulary(vocabulary: str) -> str:
+    """File of a built-in vocabulary: the reference's relative path if it exists from the working directory, else the copy under the
+    package's `metadata/` (as `setup_cfg` resolves ZEROSHOT_WEIGHT_PATH).  Only `mp3d_clip.npy` ships with the package."""
+    import os
+    if vocabulary == "custom":
+        raise ValueError("vocabulary='custom' needs classifier=<[C, 512] .npy path or [512, C] tensor>: computing CLIP text embeddings "
+                         "from class names needs the downloaded CLIP weights and is out of scope here")
+    if vocabulary not in BUILDIN_CLASSIFIER:
+        raise ValueError(f"vocabulary {vocabulary!r}: expected one of {sorted(BUILDIN_CLASSIFIER)} or 'custom'")
+    rel = BUILDIN_CLASSIFIER[vocabulary]
+    if os.path.exists(rel):
+        return rel
+    cand = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "metadata", os.path.basename(rel))
+    if os.path.exists(cand):
+        return cand
+    raise FileNotFoundError(f"vocabulary {vocabulary!r}: neither {rel} nor {cand} exists")
+
+
 class EmbodiedPredictor:
-    def __init__(self, cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None):
+    def __init__(self, cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, vocabulary: Optional[str] = None, classifier=None):
+        """`vocabulary`: lvis / objects365 / openimages / coco / mp3d (predictor.py:183-231); `classifier`: a `[C, 512]` .npy path
+        or a `[512, C]` tensor (what the reference calls `custom`).  Either one swaps the heads' classifier of the built model
+        (`reset_cls_test`); neither keeps the configuration's."""
         from .. import build_model
         self.cfg = cfg
+        if vocabulary is not None and classifier is None:
+            classifier = resolve_vocabulary(vocabulary)
         self.model = build_model(cfg, state_dict)          # loads cfg.MODEL.WEIGHTS like DetectionCheckpointer (:399-400)
+        if classifier is not None:
+            from ..modeling.utils import reset_cls_test
+            if isinstance(classifier, torch.Tensor):
+                num_classes = int(classifier.shape[1])
+            else:
+                num_classes = int(np.load(classifier, mmap_mode="r").shape[0])
+            reset_cls_test(self.model, classifier, num_classes)
         self.input_format = cfg.INPUT.FORMAT
         assert self.input_format in ("RGB", "BGR"), self.input_format
         self.max_size = int(cfg.INPUT.MAX_SIZE_TEST)

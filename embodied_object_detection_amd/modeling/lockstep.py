@@ -101,8 +101,9 @@ class LockstepScenes:
         self.host_profile = {"frames": 0, "enqueue_s": 0.0, "materialize_s": 0.0, "wait_s": 0.0}
         if bool(cfg.MODEL.TEST_SAVE_SEMMAP):
             raise NotImplementedError("MODEL.TEST_SAVE_SEMMAP is served by the single-scene model (custom_rcnn.py:518-530)")
-        R, C1, dev, B = m.proposal_generator.cap, m.C1, self.device, self.B
+        R, dev, B = m.proposal_generator.cap, self.device, self.B
         rh = m.roi_heads
+        C1 = rh.C1                                    # the heads' vocabulary; the memory's matrix (m.C1 columns) may differ
         f32 = dict(dtype=torch.float32, device=dev)
         self.R, self.D = R, rh.topk
         # cascade buffers, B x the single-scene ones
@@ -116,9 +117,9 @@ class LockstepScenes:
         self.deltas = torch.empty((B * R, 1, 1, 4), **f32)
         self.prob = torch.zeros((B * R, C1), **f32)
         self.boxes = [torch.zeros((B * R, 4), **f32) for _ in range(rh.num_stages + 1)]
-        self.mem_scores = torch.zeros((B * R, C1), **f32)
+        self.mem_scores = torch.zeros((B * R, m.C1), **f32)
         self.selectors = [ops.DetectionSelector(R, C1, rh.topk, dev, groups=True, batch=B) for _ in range(RESULT_SETS)]
-        self.mem_selector = ops.DetectionSelector(R, C1, 100, dev, unique=True, batch=B)
+        self.mem_selector = ops.DetectionSelector(R, m.C1, 100, dev, unique=True, batch=B)
         # mask passes over the concatenated lists of all scenes
         self.Pcap = min(R, 128)                       # memory instances per scene: <= 100 unique rows
         i32 = dict(dtype=torch.int32, device=dev)
@@ -267,6 +268,14 @@ class LockstepScenes:
         self._prefetched = tuple(id(f["image"]) for f in frames)
 
     # ---- one step: one frame of every scene ----------------------------------------------------------------------------------
+    def set_classifier_width(self) -> None:
+        """The heads' class matrix changed width (`reset_cls_test`): the batch's score buffer and detection selectors follow it.
+        The memory side (`mem_scores`, `mem_selector`, the tables) is not touched."""
+        rh, B = self.model.roi_heads, self.B
+        torch.cuda.synchronize(self.device)           # results of earlier steps still read the old selectors' buffers
+        self.prob = torch.zeros((B * self.R, rh.C1), dtype=torch.float32, device=self.device)
+        self.selectors = [ops.DetectionSelector(self.R, rh.C1, rh.topk, self.device, groups=True, batch=B) for _ in range(RESULT_SETS)]
+
     def _step(self, frames: List[dict], active: List[bool], refresh: bool, next_frames: Optional[List[dict]], trailing: bool):
         m, B, dev = self.model, self.B, self.device
         bb, pg, rh = m.backbone, m.proposal_generator, m.roi_heads
@@ -278,7 +287,9 @@ class LockstepScenes:
         n_cells = self.implicit_memory.shape[1]
         d = self._frame_buffers(H, W, n_cells)
         cur = torch.cuda.current_stream(dev)
-        R, D, C1 = self.R, self.D, m.C1
+        R, D, C1 = self.R, self.D, rh.C1
+        if self.prob.shape[1] != C1:                  # `reset_cls_test` on the model since the last step: follow the heads' width
+            self.set_classifier_width()
         self._step_no += 1
         self._mark("start")
         for b, f in enumerate(frames):
@@ -352,20 +363,22 @@ class LockstepScenes:
             feat = self.feat0 if s_i == 0 else self.feat
             st["cls_bb0"](self.h2, B * R, 1, 1, relu=True, out=feat, split=(512, self.hb), **seg)
             last = s_i == rh.num_stages - 1
-            rescore = s_i == 0      # the memory update's CLIP re-score: for every MEMORY_TYPE, as in the reference (custom_rcnn.py:515,573)
+            # the memory update's CLIP re-score: for every MEMORY_TYPE, as in the reference (custom_rcnn.py:515,573); in stage 0's
+            # launch when both class matrices are narrow and equally wide, else a launch per scene behind the cascade
+            rescore = s_i == 0 and rh.fuses_mem_rescore(m.zs_weight)
             if rh.fuse_stage_tail and not rh.fold_deltas:
                 # classifier tail + bbox_pred.2 + apply_deltas in one launch, as the single-scene model runs them (roi_heads._cascade)
                 ops.cascade_stage_tail(feat, st["zs"], self.prob, s_i > 0, self.featn0 if s_i == 0 else None, prop_count, R, C1, rh.norm_temp,
                                        self.hb, st["bb2"], boxes, self.boxes[s_i + 1], rh.cascade_weights[s_i], not last, float(W), float(H),
                                        zs_mem=m.zs_weight if rescore else None, prop_scores=prop_scores if (last or rescore) else None,
                                        mem_scores_out=self.mem_scores if rescore else None,
-                                       final_inv_stages=1.0 / rh.num_stages if last else 0.0, deltas_out=self.deltas, batch=B)
+                                       final_inv_stages=1.0 / rh.num_stages if last else 0.0, deltas_out=self.deltas, batch=B, wide=True)
                 boxes = self.boxes[s_i + 1]
                 continue
             ops.zs_classify(feat, st["zs"], self.prob, s_i > 0, self.featn0 if s_i == 0 else None, prop_count, R, C1, rh.norm_temp,
                             zs_mem=m.zs_weight if rescore else None, prop_scores=prop_scores if (last or rescore) else None,
                             mem_scores_out=self.mem_scores if rescore else None,
-                            final_inv_stages=1.0 / rh.num_stages if last else 0.0, batch=B)
+                            final_inv_stages=1.0 / rh.num_stages if last else 0.0, batch=B, wide=True)
             st["bb2"](self.hb, B * R, 1, 1, out=self.deltas, **seg)
             if rh.fold_deltas and not last:
                 pending = rh.cascade_weights[s_i]
@@ -373,6 +386,10 @@ class LockstepScenes:
                 ops.apply_deltas(self.deltas, 4, boxes, self.boxes[s_i + 1], prop_count, R, rh.cascade_weights[s_i], not last, float(W),
                                  float(H), batch=B)
                 boxes = self.boxes[s_i + 1]
+        if not rh.fuses_mem_rescore(m.zs_weight):
+            for b in range(B):
+                ops.memory_scores(self.featn0[b * R:(b + 1) * R], m.zs_weight, prop_scores[b * R:(b + 1) * R],
+                                  self.mem_scores[b * R:(b + 1) * R], prop_count[b:b + 1], R, m.C1)
         # memory selection first: the step's critical chain waits for it (custom_rcnn.py:825-875)
         msel = self.mem_selector
         _, _, _, mem_rows, mem_cnt = msel(prop_boxes, self.mem_scores, prop_count, float(W), float(H), m.cls_score_thresh, 0.5)

@@ -443,7 +443,8 @@ class CustomRCNNRecurrent:
         views, shapes, props = self._front(frame, pre, proj, mem_f16)
         if start_batch:
             self._enqueue_trunk(start_batch, self._ev_start, first_ahead)
-        self._mem_scores_frame = self._frame_no          # `mem_scores`: written by stage 0 of this frame's cascade
+        if self.roi_heads.fuses_mem_rescore(self.zs_weight):
+            self._mem_scores_frame = self._frame_no      # `mem_scores`: written by stage 0 of this frame's cascade
         if self.overlap_branches:
             self._frame_pipelined(frame, (H, W), views, shapes, props, proj, trailing_detection_pass)
         else:

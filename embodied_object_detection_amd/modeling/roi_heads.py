@@ -28,9 +28,14 @@ class DeticCascadeROIHeads:
             raise NotImplementedError("unsupported ROI head geometry")
         if not cfg.MODEL.ROI_MASK_HEAD.CLS_AGNOSTIC_MASK or cfg.MODEL.ROI_MASK_HEAD.NUM_CONV != 4:
             raise NotImplementedError("unsupported mask head")
-        self.num_classes = int(cfg.MODEL.ROI_HEADS.NUM_CLASSES)
-        self.C1 = self.num_classes + 1
+        # the class count is the classifier matrix's (RESET_CLS_TESTS / TEST_NUM_CLASSES swap it before construction, `reset_cls_test`
+        # after it), not cfg.MODEL.ROI_HEADS.NUM_CLASSES: utils.py:32-50 sets roi_heads.num_classes the same way
+        self.C1 = int(sd["roi_heads.box_predictor.0.cls_score.zs_weight"].shape[1])
+        self.num_classes = self.C1 - 1
+        if not 1 <= self.num_classes <= ops.ZS_WIDE_MAX_C1 - 1:
+            raise NotImplementedError(f"{self.num_classes} classes: the HIP path covers 1 to {ops.ZS_WIDE_MAX_C1 - 1}")
         self.norm_temp = float(rb.NORM_TEMP)
+        self.norm_weight = bool(rb.NORM_WEIGHT)
         self.cascade_weights = [tuple(float(v) for v in w) for w in cfg.MODEL.ROI_BOX_CASCADE_HEAD.BBOX_REG_WEIGHTS]
         self.num_stages = len(self.cascade_weights)
         self.score_thresh = float(cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST)
@@ -62,7 +67,7 @@ class DeticCascadeROIHeads:
             st["cls_bb0"] = ops.Conv(torch.cat([sd[f"{p}.cls_score.linear.weight"], sd[f"{p}.bbox_pred.0.weight"]], dim=0)[:, :, None, None],
                                      torch.cat([sd[f"{p}.cls_score.linear.bias"], sd[f"{p}.bbox_pred.0.bias"]], dim=0), device=device,
                                      name=f"box_predictor.{k}.cls_score.linear+bbox_pred.0")
-            assert st["zs"].shape[1] == self.C1, (st["zs"].shape, self.C1)
+            assert st["zs"].shape == (512, self.C1), (st["zs"].shape, self.C1)
             self.stages.append(st)
         m = "roi_heads.mask_head"
         self.mask_convs = [ops.Conv(sd[f"{m}.mask_fcn{i}.weight"], sd[f"{m}.mask_fcn{i}.bias"], pad=1, device=device, name=f"mask_fcn{i}")
@@ -120,6 +125,22 @@ class DeticCascadeROIHeads:
         self.selectors = [ops.DetectionSelector(R, self.C1, self.topk, device, groups=True) for _ in range(3)]
         self.selector = self.selectors[0]
 
+    def set_classifier(self, zs: torch.Tensor) -> None:
+        """`reset_cls_test` on the built heads: `zs` [512, C + 1] (background column included) replaces the three stages' class
+        matrices; the score buffer and the selectors follow its width.  Everything else (weights, activations, boxes) stays."""
+        zs = zs.to(dtype=torch.float32).contiguous().to(self.device)
+        if zs.dim() != 2 or zs.shape[0] != 512 or not 2 <= zs.shape[1] <= ops.ZS_WIDE_MAX_C1:
+            raise ValueError(f"classifier matrix {tuple(zs.shape)}: expected [512, C + 1] with 1 <= C <= {ops.ZS_WIDE_MAX_C1 - 1}")
+        for st in self.stages:
+            st["zs"] = zs
+        if zs.shape[1] != self.C1:
+            self.C1 = int(zs.shape[1])
+            self.num_classes = self.C1 - 1
+            self.prob = torch.zeros((self.R, self.C1), dtype=torch.float32, device=self.device)
+            self.selectors = [ops.DetectionSelector(self.R, self.C1, self.topk, self.device, groups=True) for _ in range(3)]
+            self.selector = self.selectors[0]
+        self._graphs = {}
+
     # ---- cascade box heads ------------------------------------------------------------------------
     def forward_box(self, views: List[torch.Tensor], shapes, prop_boxes: torch.Tensor, prop_scores: torch.Tensor, count: torch.Tensor,
                     image_hw: Tuple[int, int], sel: int = 0, mem_rescore=None, after_cascade=None):
@@ -150,11 +171,18 @@ class DeticCascadeROIHeads:
         self.last_selector = self.selectors[sel]
         return self.selectors[sel](boxes, self.prob, count, float(W), float(H), self.score_thresh, self.nms_thresh)
 
+    def fuses_mem_rescore(self, zs_mem: torch.Tensor) -> bool:
+        """Stage 0's classifier launch writes the memory's CLIP re-score as well only when both class matrices are narrow and
+        equally wide (the narrow kernel stages one after the other in the same LDS); otherwise `ops.memory_scores` runs."""
+        return self.C1 <= ops.ZS_MAX_C1 and int(zs_mem.shape[1]) == self.C1
+
     def _cascade(self, views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore):
         """The three cascade stages (detic_roi_heads.py:88-175) -> the final boxes buffer; scores land in `self.prob`."""
         h3, w3 = shapes[0]
         H, W = image_hw
         R = self.R
+        if mem_rescore is not None and not self.fuses_mem_rescore(mem_rescore[0]):
+            mem_rescore = None
         boxes = prop_boxes
         pending = None      # `fold_deltas`: regression weights of the deltas that the next ROIAlign applies to `boxes` on load
         for k, st in enumerate(self.stages):
@@ -183,7 +211,7 @@ class DeticCascadeROIHeads:
                                        zs_mem=mem_rescore[0] if (k == 0 and mem_rescore is not None) else None,
                                        prop_scores=prop_scores if (last or (k == 0 and mem_rescore is not None)) else None,
                                        mem_scores_out=mem_rescore[1] if (k == 0 and mem_rescore is not None) else None,
-                                       final_inv_stages=1.0 / self.num_stages if last else 0.0, deltas_out=self.deltas)
+                                       final_inv_stages=1.0 / self.num_stages if last else 0.0, deltas_out=self.deltas, wide=True)
                 boxes = self.boxes[k + 1]
                 continue
             # the last stage's launch also fuses the cascade's scores: sqrt(mean_k(prob) * proposal score) (detic_roi_heads.py:164-173)
@@ -191,7 +219,7 @@ class DeticCascadeROIHeads:
                             zs_mem=mem_rescore[0] if (k == 0 and mem_rescore is not None) else None,
                             prop_scores=prop_scores if (last or (k == 0 and mem_rescore is not None)) else None,
                             mem_scores_out=mem_rescore[1] if (k == 0 and mem_rescore is not None) else None,
-                            final_inv_stages=1.0 / self.num_stages if last else 0.0)
+                            final_inv_stages=1.0 / self.num_stages if last else 0.0, wide=True)
             if not self.merge_cls_bb0:
                 st["bb0"](self.h2, R, 1, 1, relu=True, m_count=count, m_unit=1, out=self.hb)
             st["bb2"](self.hb, R, 1, 1, m_count=count, m_unit=1, out=self.deltas)

@@ -416,7 +416,10 @@ class DetectionSelector:
         self.lib = _lib.load()
         self.R_cap, self.C1, self.topk, self.batch = R_cap, C1, topk, batch
         nbytes = self.lib.eod_detections_workspace_bytes(R_cap, C1)
-        self.ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        if nbytes == 0:
+            raise _lib.EodError(f"eod_fast_rcnn_inference: {R_cap} rows x {C1 - 1} classes are not supported (at most 512 rows, 2047 classes)")
+        # zeroed: the wide path (more than 24 classes) keeps a histogram here that every call leaves cleared for the next one
+        self.ws = torch.zeros((nbytes,), dtype=torch.uint8, device=device)
         B = batch
         self.boxes = torch.zeros((B * topk, 4), dtype=torch.float32, device=device)
         self.scores = torch.zeros((B * topk,), dtype=torch.float32, device=device)
@@ -450,26 +453,40 @@ class DetectionSelector:
         return self.boxes, self.scores, self.classes, self.rows, self.count
 
 
+ZS_WIDE = 2          # EOD_ZS_WIDE: the flag bit on `accumulate` that asks for the wide-vocabulary classifier kernel
+ZS_MAX_C1 = 24       # columns the narrow (LDS-staged) classifier kernel holds
+ZS_WIDE_MAX_C1 = 2048
+
+
+def _zs_refusal(name: str, C1: int, wide: bool) -> str:
+    if wide:
+        return (f"{name}: {C1 - 1} classes + background exceed the wide classifier kernel's {ZS_WIDE_MAX_C1} columns "
+                f"(at most {ZS_WIDE_MAX_C1 - 1} classes on the HIP path)")
+    return (f"{name}: {C1 - 1} classes + background do not fit the narrow kernel's LDS-staged class matrix (at most {ZS_MAX_C1 - 1} "
+            f"classes); pass wide=True for a RESET_CLS_TESTS / TEST_NUM_CLASSES vocabulary of up to {ZS_WIDE_MAX_C1 - 1} classes")
+
+
 def zs_classify(feat, zs, prob_acc, accumulate: bool, featn_out, count, R_cap: int, C1: int, temp: float = 50.0, zs_mem=None,
-                prop_scores=None, mem_scores_out=None, final_inv_stages: float = 0.0, batch: int = 1):
+                prop_scores=None, mem_scores_out=None, final_inv_stages: float = 0.0, batch: int = 1, wide: bool = False):
     """`zs_mem` + `prop_scores` + `mem_scores_out`: also the memory update's CLIP re-score (what `memory_scores` computes) in the same
-    launch; `final_inv_stages` > 0 (last cascade stage): also the cascade score fusion (what `cascade_scores` does)."""
-    st = _lib.load().eod_zs_classify(feat.data_ptr(), zs.data_ptr(), prob_acc.data_ptr(), int(accumulate), _ptr(featn_out), _ptr(count),
-                                     R_cap, 512, C1, temp, _ptr(zs_mem), _ptr(prop_scores), _ptr(mem_scores_out),
-                                     float(final_inv_stages), batch, _stream())
+    launch; `final_inv_stages` > 0 (last cascade stage): also the cascade score fusion (what `cascade_scores` does).
+    `wide=True` (EOD_ZS_WIDE): vocabularies of 24 to 2047 classes run the matrix-core kernel; up to 23 classes it changes nothing."""
+    st = _lib.load().eod_zs_classify(feat.data_ptr(), zs.data_ptr(), prob_acc.data_ptr(), int(bool(accumulate)) | (ZS_WIDE if wide else 0),
+                                     _ptr(featn_out), _ptr(count), R_cap, 512, C1, temp, _ptr(zs_mem), _ptr(prop_scores),
+                                     _ptr(mem_scores_out), float(final_inv_stages), batch, _stream())
     if st == -5:
-        raise _lib.EodError(f"eod_zs_classify: {C1 - 1} classes + background do not fit the kernel's LDS-staged class matrix (at most 23 "
-                            "classes): a RESET_CLS_TESTS / TEST_NUM_CLASSES vocabulary of this size is not supported on the HIP path")
+        raise _lib.EodError(_zs_refusal("eod_zs_classify", C1, wide))
     check(st, "eod_zs_classify")
 
 
 def cascade_stage_tail(feat, zs, prob_acc, accumulate: bool, featn_out, count, R_cap: int, C1: int, temp: float, hb, bb2: "Conv", boxes_in,
                        boxes_out, weights, clip: bool, img_w: float, img_h: float, zs_mem=None, prop_scores=None, mem_scores_out=None,
-                       final_inv_stages: float = 0.0, deltas_out=None, batch: int = 1):
+                       final_inv_stages: float = 0.0, deltas_out=None, batch: int = 1, wide: bool = False):
     """`zs_classify` + bbox_pred.2 + apply_deltas of one cascade stage in ONE launch (`eod_cascade_stage_tail`); `bb2` is the stage's
-    1024 -> 4 layer (its packed weight rows and bias are read in place)."""
+    1024 -> 4 layer (its packed weight rows and bias are read in place).  `wide`: as in `zs_classify`."""
     d = _lib.EodStageTailDesc()
-    d.feat, d.zs, d.prob_acc, d.accumulate, d.feat_norm_out, d.count = feat.data_ptr(), zs.data_ptr(), prob_acc.data_ptr(), int(accumulate), _ptr(featn_out), _ptr(count)
+    d.feat, d.zs, d.prob_acc, d.feat_norm_out, d.count = feat.data_ptr(), zs.data_ptr(), prob_acc.data_ptr(), _ptr(featn_out), _ptr(count)
+    d.accumulate = int(bool(accumulate)) | (ZS_WIDE if wide else 0)
     d.R_cap, d.D, d.C1, d.temp = R_cap, 512, C1, temp
     d.zs_mem, d.prop_scores, d.mem_scores_out, d.final_inv_stages, d.batch = _ptr(zs_mem), _ptr(prop_scores), _ptr(mem_scores_out), float(final_inv_stages), batch
     d.hb, d.w2, d.b2, d.hb_dim, d.w2_ld = hb.data_ptr(), bb2.w.data_ptr(), bb2.bias.data_ptr(), bb2.Cin, bb2.Kpad
@@ -478,7 +495,7 @@ def cascade_stage_tail(feat, zs, prob_acc, accumulate: bool, featn_out, count, R
     d.clip, d.img_w, d.img_h = int(clip), img_w, img_h
     st = _lib.load().eod_cascade_stage_tail(C.byref(d), _stream())
     if st == -5:
-        raise _lib.EodError(f"eod_cascade_stage_tail: {C1 - 1} classes exceed the classifier kernel's capacity")
+        raise _lib.EodError(_zs_refusal("eod_cascade_stage_tail", C1, wide))
     check(st, "eod_cascade_stage_tail")
 
 
@@ -494,6 +511,7 @@ def cascade_scores(prob_acc, prop_scores, count, R_cap: int, C1: int, inv_stages
 
 
 def memory_scores(featn, zs, prop_scores, scores_out, count, R_cap: int, C1: int):
+    """Dispatches on `C1` by itself: up to 24 columns the wave-per-row kernel, up to 2048 the matrix-core kernel."""
     check(_lib.load().eod_memory_scores(featn.data_ptr(), zs.data_ptr(), prop_scores.data_ptr(), scores_out.data_ptr(), _ptr(count),
                                         R_cap, 512, C1, _stream()), "eod_memory_scores")
 

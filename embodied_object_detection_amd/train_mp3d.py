@@ -80,7 +80,8 @@ def do_test(cfg, model, args, rank: int, world: int):
     buf = gather_records(res["records"], rank, world, model.device)
     out = None
     if rank == 0:
-        out = evaluate_gathered(buf, int(cfg.MODEL.ROI_HEADS.NUM_CLASSES))
+        # the heads' vocabulary: RESET_CLS_TESTS / TEST_NUM_CLASSES may have replaced NUM_CLASSES (train_mp3d.py:383-387)
+        out = evaluate_gathered(buf, int(getattr(getattr(model, "roi_heads", None), "num_classes", cfg.MODEL.ROI_HEADS.NUM_CLASSES)))
         for name, r in out.items():
             print(f"[eval] {name}: AP {r['AP']:.3f} AP50 {r['AP50']:.3f} AP75 {r['AP75']:.3f} ({r['num_images']} images)")
     print(f"[rank {rank}] {res['frames']} frames in {res['seconds']:.2f} s = {res['frames'] / max(res['seconds'], 1e-9):.1f} frames/s")

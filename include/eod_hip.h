@@ -363,7 +363,16 @@ int eod_centernet_proposals(const EodProposalDesc* d, eod_stream_t stream);
  *     feature this launch holds in registers: sqrt(sigmoid(featn . zs_mem) * prop_score), 0 for prop_score >= 1
  *     (inference_with_proposals, custom_rcnn.py:838-861) -- what eod_memory_scores computes from feat_norm_out;
  *   final_inv_stages > 0 (last cascade stage, with prop_scores): prob_acc = sqrt(prob_acc * final_inv_stages * prop_score)
- *     (detic_roi_heads.py:164-173) -- what eod_cascade_scores does in place. */
+ *     (detic_roi_heads.py:164-173) -- what eod_cascade_scores does in place.
+ * Class count.  C1 <= 24 (up to 23 classes + background): the class matrix is staged in LDS, one wave per row -- the kernel of the
+ * frame's critical chain.  Wider vocabularies (reset_cls_test, RESET_CLS_TESTS: COCO 81, Objects365 366, LVIS 1204 columns) run a
+ * second kernel, a [rows,512] x [512,C1] GEMM on the fp32 matrix cores, and the caller asks for it: pass `accumulate | EOD_ZS_WIDE`
+ * (bit 0 keeps its meaning; the same bit on EodStageTailDesc.accumulate).  Without the bit C1 > 24 returns EOD_ERR_CAPACITY; with it
+ * C1 <= 24 runs the narrow kernel (same bits as without it) and 25 <= C1 <= 2048 the wide one: feat_norm_out, boxes_out and
+ * deltas_out are bitwise what the narrow kernel writes for the same rows, the probabilities agree to fp32 summation order; zs
+ * needs no padding or alignment beyond 16 bytes of its base.  zs_mem, when given to a wide call, has the same C1 and costs a second
+ * launch.  C1 > 2048 returns EOD_ERR_CAPACITY.  eod_memory_scores dispatches on C1 by itself (same limit). */
+#define EOD_ZS_WIDE 2
 /* eod_zs_classify + the rest of the stage's predictor in the SAME launch: bbox_pred.2 (Linear hb_dim -> 4 on `hb`, the ReLU'd
  * bbox_pred.0 output; detic_fast_rcnn.py:109-116) and Box2BoxTransform.apply_deltas onto the stage's boxes with the stage's
  * weights, clipped to the image when `clip` (detic_roi_heads.py:121-122,314): three launches of the cascade's chain become one.
@@ -408,6 +417,12 @@ int eod_cascade_scores(float* prob_acc, const float* prop_scores, const int32_t*
 /* d2 fast_rcnn_inference, single image (detic_roi_heads.py:214-221, custom_rcnn.py:862-869): threshold, sort, per-class NMS,
  * top-k and the gather of the kept rows in ONE launch (one workgroup: the sort is followed by a chunked greedy NMS that stops
  * once topk boxes are kept).  topk <= 512. */
+/* Wide inputs (more than 24 classes or more than 8192 slots R_cap * (C1 - 1); R_cap <= 512, C1 <= 2048, topk <= 512, every optional
+ * output supported) run three launches instead: a whole-chip pass (finite-row flags, threshold, the scene's histogram of score bins),
+ * a whole-chip compaction of the keys above the histogram's cut, and one workgroup per scene for sort + per-class NMS + top-k +
+ * unique + groups, which fetches further score bands by re-scanning the score matrix when the first list does not fill topk: the
+ * result is detectron2's list for every input.  On this path the workspace must be ZERO before the first call; every call leaves
+ * it zeroed.  eod_detections_workspace_bytes returns 0 for sizes no path supports. */
 typedef struct EodDetDesc {
   const float* boxes;     /* [R,4] class agnostic */
   const float* scores;    /* [R,C1] (last column = background) */
