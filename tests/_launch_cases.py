@@ -1,0 +1,291 @@
+"""CPU side of test_training_launches_gpu.py: the recorder of the non-convolution entry points and the references of ROIAlign written
+out in torch at a chosen precision (float64 = reference, float32 = yardstick).  Nothing here touches a GPU by itself."""
+from typing import Dict, List, Sequence, Tuple
+
+import torch
+
+from _conv_cases import SENTINEL    # noqa: F401  (re-exported: one sentinel for the launch modules)
+
+U = 2.0 ** -24                      # fp32 unit round-off
+
+
+# ------------------------------------------------------------------------------------------------
+# recording: which entry point was called with which arguments
+# ------------------------------------------------------------------------------------------------
+class Recorder:
+    """Wraps the Python-level entry points of `ops` and three ctypes-level ones of the loaded library for the duration of a `with`
+    block.  `calls[family][key]` = payload of the first call with those arguments (`key`: shapes, counts, flags, which optional
+    pointers were given); ROIAlign payloads collect the host copies of the first box lists they met (the cascade's three stages)."""
+    KEEP_BOXES = 3
+
+    def __init__(self):
+        self.calls: Dict[str, Dict[tuple, dict]] = {}
+        self._undo = []
+
+    def note(self, family: str, key: tuple, **payload) -> dict:
+        fam = self.calls.setdefault(family, {})
+        if key not in fam:
+            fam[key] = dict(payload, n=0)
+        fam[key]["n"] += 1
+        return fam[key]
+
+    def _patch(self, owner, name: str, make):
+        orig = getattr(owner, name)
+        setattr(owner, name, make(orig))
+        self._undo.append((owner, name, orig))
+
+    def __enter__(self):
+        from embodied_object_detection_amd import _lib, ops
+        rec = self
+
+        def roi_align(orig):
+            def f(p3, p4, p5, h3, w3, Cc, boxes, count, R_cap, S, out=None, box_rows=None, batch=1, boxes_per_image=0, refine=None):
+                r = orig(p3, p4, p5, h3, w3, Cc, boxes, count, R_cap, S, out=out, box_rows=box_rows, batch=batch,
+                         boxes_per_image=boxes_per_image, refine=refine)
+                e = rec.note("roi_align", (int(h3), int(w3), int(Cc), int(R_cap), int(S), count is not None, box_rows is not None, int(batch),
+                                           refine is not None), boxes=[])
+                if len(e["boxes"]) < rec.KEEP_BOXES and refine is None and box_rows is None:
+                    e["boxes"].append(boxes.detach().float().cpu().reshape(-1, 4)[:R_cap].clone())
+                return r
+            return f
+
+        def roi_align_backward(orig):
+            def f(dp3, dp4, dp5, h3, w3, Cc, boxes, count, R_cap, S, g):
+                e = rec.note("roi_align_backward", (int(h3), int(w3), int(Cc), int(R_cap), int(S), count is not None), boxes=[])
+                if len(e["boxes"]) < rec.KEEP_BOXES:
+                    e["boxes"].append(boxes.detach().float().cpu().reshape(-1, 4)[:R_cap].clone())
+                return orig(dp3, dp4, dp5, h3, w3, Cc, boxes, count, R_cap, S, g)
+            return f
+
+        def groupnorm_relu(orig):
+            def f(x, gamma, beta, level_off, Cc, stats, groups=32, eps=1e-5, out=None, partial_ready=False):
+                rec.note("groupnorm_relu", (tuple(int(o) for o in level_off), int(Cc), int(groups), float(eps), bool(partial_ready), out is not None))
+                return orig(x, gamma, beta, level_off, Cc, stats, groups=groups, eps=eps, out=out, partial_ready=partial_ready)
+            return f
+
+        def groupnorm_relu_backward(orig):
+            def f(x, y, dy, gamma, level_off, Cc, fwd_stats, groups=32, eps=1e-5):
+                rec.note("groupnorm_relu_backward", (tuple(int(o) for o in level_off), int(Cc), int(groups), float(eps)))
+                return orig(x, y, dy, gamma, level_off, Cc, fwd_stats, groups=groups, eps=eps)
+            return f
+
+        def projector_backward(orig):
+            def f(self, grads, pooled_f16, H, W, weight, need_input_grad=True):
+                rec.note("memory_projector_backward", (int(H), int(W), float(weight), bool(need_input_grad)))
+                return orig(self, grads, pooled_f16, H, W, weight, need_input_grad=need_input_grad)
+            return f
+
+        def memory_gather_pool(orig):
+            def f(mem_f16, proj, H, W, out=None, err=None, torch_order=False, batch=1):
+                rec.note("memory_gather_pool", (int(H), int(W), int(mem_f16.shape[-2]), int(mem_f16.shape[-1]), bool(torch_order), int(batch),
+                                                out is not None, err is not None))
+                return orig(mem_f16, proj, H, W, out=out, err=err, torch_order=torch_order, batch=batch)
+            return f
+
+        def zs_logits(orig):
+            def f(feat, zs, temp=50.0, ld=None, featn_out=None):
+                r = orig(feat, zs, temp, ld=ld, featn_out=featn_out)
+                rec.note("zs_logits", (int(feat.shape[0]), int(zs.shape[1]), int(r.shape[1]), float(temp), featn_out is not None))
+                return r
+            return f
+
+        def zs_logits_backward(orig):
+            def f(feat, zs, d_logits, temp=50.0):
+                rec.note("zs_logits_backward", (int(d_logits.shape[0]), int(zs.shape[1]), int(d_logits.shape[1]), float(temp)))
+                return orig(feat, zs, d_logits, temp)
+            return f
+
+        def nonfinite(orig):
+            def f(self, grads, flag):
+                rec.note("nonfinite", tuple(-1 if g is None else int(g.numel()) for g in grads))
+                return orig(self, grads, flag)
+            return f
+
+        for name, make in (("roi_align", roi_align), ("roi_align_backward", roi_align_backward), ("groupnorm_relu", groupnorm_relu),
+                           ("groupnorm_relu_backward", groupnorm_relu_backward), ("memory_gather_pool", memory_gather_pool),
+                           ("zs_logits", zs_logits), ("zs_logits_backward", zs_logits_backward)):
+            self._patch(ops, name, make)
+        self._patch(ops.MemoryProjectorBackward, "__call__", projector_backward)
+        self._patch(ops.AdamW, "nonfinite", nonfinite)
+
+        # ctypes level: an attribute on the loaded library object shadows the exported function for everybody who goes through it
+        lib = _lib.load()
+
+        def relu_backward(orig):
+            def f(g, y, out, n, stream):
+                rec.note("relu_backward", (int(n),))
+                return orig(g, y, out, n, stream)
+            return f
+
+        def upsample2_sum_backward(orig):
+            def f(g, out, N, h, w, Cc, accumulate, stream):
+                rec.note("upsample2_sum_backward", (int(N), int(h), int(w), int(Cc), int(accumulate)))
+                return orig(g, out, N, h, w, Cc, accumulate, stream)
+            return f
+
+        def maxpool_backward(orig):
+            def f(x, y, g, dx, N, H, W, Cc, OH, OW, stream):
+                rec.note("maxpool3x3s2_backward", (int(N), int(H), int(W), int(Cc), int(OH), int(OW)))
+                return orig(x, y, g, dx, N, H, W, Cc, OH, OW, stream)
+            return f
+
+        for name, make in (("eod_relu_backward", relu_backward), ("eod_upsample2_sum_backward", upsample2_sum_backward),
+                           ("eod_maxpool3x3s2_backward", maxpool_backward)):
+            self._patch(lib, name, make)
+        return self
+
+    def __exit__(self, *exc):
+        for owner, name, orig in reversed(self._undo):
+            setattr(owner, name, orig)
+        self._undo = []
+        return False
+
+
+# ------------------------------------------------------------------------------------------------
+# ROIAlignV2 (aligned, sampling_ratio 0) over P3..P5 at a chosen precision
+# ------------------------------------------------------------------------------------------------
+SCALES = (1.0 / 8, 1.0 / 16, 1.0 / 32)
+
+
+def roi_geometry(boxes: torch.Tensor, S: int):
+    """The DISCRETE decisions of the pooler, taken in fp32 as upstream takes them (they are part of the operation, not of its
+    rounding): level of every box (`assign_boxes_to_levels`) and its sampling grid (gh, gw) = ceil(roi extent / S) on the fp32
+    quotient.  -> (levels int64 [R], gh [R], gw [R]); gh or gw <= 0: the ROI pools zeros and has no gradient."""
+    from oracle import ops as OO
+    b = boxes.float()
+    # a box inverted along one axis has a negative area and no level (NaN); it pools zeros on whatever level: the finest here
+    inverted = ((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])) < 0
+    lv = OO.assign_boxes_to_levels(torch.where(inverted[:, None], torch.zeros_like(b), b))
+    sc = torch.tensor(SCALES, dtype=torch.float32)[lv]
+    bs = b * sc[:, None] - 0.5
+    gh = torch.ceil((bs[:, 3] - bs[:, 1]) / S)
+    gw = torch.ceil((bs[:, 2] - bs[:, 0]) / S)
+    bad = ~(torch.isfinite(gh) & torch.isfinite(gw))
+    gh[bad], gw[bad] = 0, 0
+    return lv, gh.long(), gw.long()
+
+
+def _axis(lo, bin_, g: int, S: int, extent: int, dtype) -> torch.Tensor:
+    """A [S, extent]: summed bilinear weight of the g samples of every bin on every feature index along one axis, with the
+    clamps and the validity rule of torchvision's bilinear_interpolate as oracle/ops.py `_bilinear` states them."""
+    ph = torch.arange(S, dtype=dtype)
+    i = torch.arange(g, dtype=dtype)
+    v = lo + ph[:, None] * bin_ + (i[None, :] + 0.5) * bin_ / g                      # [S, g]
+    valid = ~((v < -1.0) | (v > extent))
+    v = v.clamp(min=0)
+    low = v.to(torch.int64)
+    top = low >= extent - 1
+    high = torch.where(top, torch.full_like(low, extent - 1), low + 1)
+    low = torch.where(top, torch.full_like(low, extent - 1), low)
+    v = torch.where(top, low.to(dtype), v)
+    l = v - low.to(dtype)
+    h = 1.0 - l
+    A = torch.zeros((S, extent), dtype=dtype)
+    rows = torch.arange(S)[:, None].expand(S, g)
+    A.index_put_((rows[valid], low[valid]), h[valid], accumulate=True)
+    A.index_put_((rows[valid], high[valid]), l[valid], accumulate=True)
+    return A
+
+
+class RoiRef:
+    """ROIAlign of a box list at `dtype`: per ROI the two axis matrices (the bilinear weights of a sample are a product of a y and an
+    x weight, and a sample is dropped when EITHER coordinate is out of range, so the double sum over a bin's samples factors
+    exactly); `forward` and `adjoint` apply them.  test_roi_reference_is_the_oracles_roi_align ties both to oracle/ops.py."""
+
+    def __init__(self, boxes: torch.Tensor, S: int, shapes: Sequence[Tuple[int, int]], dtype):
+        self.S, self.shapes, self.dtype = S, list(shapes), dtype
+        self.lv, gh, gw = roi_geometry(boxes, S)
+        self.rois = []
+        for r in range(boxes.shape[0]):
+            l = int(self.lv[r])
+            H, W = self.shapes[l]
+            if gh[r] <= 0 or gw[r] <= 0:
+                self.rois.append(None)
+                continue
+            # fp32: the oracle's own arithmetic (box * scale - 0.5 in fp32); float64: the same formula on the fp32 boxes, unrounded
+            bs = boxes[r].to(dtype) * SCALES[l] - 0.5
+            Ay = _axis(bs[1], (bs[3] - bs[1]) / S, int(gh[r]), S, H, dtype)
+            Ax = _axis(bs[0], (bs[2] - bs[0]) / S, int(gw[r]), S, W, dtype)
+            ys, xs = Ay.any(0).nonzero().flatten(), Ax.any(0).nonzero().flatten()
+            if ys.numel() == 0 or xs.numel() == 0:
+                self.rois.append(None)
+                continue
+            y0, y1, x0, x1 = int(ys[0]), int(ys[-1]) + 1, int(xs[0]), int(xs[-1]) + 1
+            self.rois.append((l, y0, y1, x0, x1, Ay[:, y0:y1].contiguous(), Ax[:, x0:x1].contiguous(), float(int(gh[r]) * int(gw[r]))))
+
+    def forward(self, feats: Sequence[torch.Tensor], indicator: bool = False) -> torch.Tensor:
+        """feats[l] [h, w, C] -> [R, S, S, C].  `indicator`: every non-zero weight counted as 1 and no division by the sample count
+        (the sum of the cells a bin touches: the magnitude the bounds are scaled by)."""
+        C = feats[0].shape[-1]
+        out = torch.zeros((len(self.rois), self.S, self.S, C), dtype=self.dtype)
+        for r, roi in enumerate(self.rois):
+            if roi is None:
+                continue
+            l, y0, y1, x0, x1, Ay, Ax, cnt = roi
+            if indicator:
+                Ay, Ax, cnt = (Ay != 0).to(self.dtype), (Ax != 0).to(self.dtype), 1.0
+            out[r] = torch.einsum("py,qx,yxc->pqc", Ay, Ax, feats[l][y0:y1, x0:x1].to(self.dtype)) / cnt
+        return out
+
+    def adjoint(self, g: torch.Tensor, indicator: bool = False) -> List[torch.Tensor]:
+        """g [R, S, S, C] -> the gradient of every level [h, w, C] (the transpose of `forward`)."""
+        C = g.shape[-1]
+        d = [torch.zeros((h, w, C), dtype=self.dtype) for h, w in self.shapes]
+        for r, roi in enumerate(self.rois):
+            if roi is None:
+                continue
+            l, y0, y1, x0, x1, Ay, Ax, cnt = roi
+            if indicator:
+                Ay, Ax, cnt = (Ay != 0).to(self.dtype), (Ax != 0).to(self.dtype), 1.0
+            d[l][y0:y1, x0:x1] += torch.einsum("py,qx,pqc->yxc", Ay, Ax, g[r].to(self.dtype)) / cnt
+        return d
+
+    def reach(self) -> List[torch.Tensor]:
+        """Per level [h, w]: how many (ROI, bin) pairs add into the cell."""
+        n = [torch.zeros((h, w), dtype=torch.float64) for h, w in self.shapes]
+        for roi in self.rois:
+            if roi is not None:
+                l, y0, y1, x0, x1, Ay, Ax, _ = roi
+                n[l][y0:y1, x0:x1] += torch.outer((Ay != 0).sum(0).double(), (Ax != 0).sum(0).double())
+        return n
+
+
+def hostile_boxes(H: int, W: int, rows: int, seed: int) -> torch.Tensor:
+    """A box list built to hurt the footprint arithmetic of the ROIAlign kernels on an H x W image: boxes touching and crossing all
+    four borders, zero-width / zero-height / inverted boxes, boxes exactly on the level thresholds of `assign_boxes_to_levels`
+    (sqrt(area) = 224 and 448: exactly, and within an fp32 rounding of it), boxes of less than one cell of their level, one box over the whole image, and seeded boxes of 6 ..
+    400 px for the rest.  Coordinates are off the 1/8-pixel lattice where a sample could land exactly on -1 or on the extent, where
+    fp32 and float64 legitimately decide differently whether the sample counts."""
+    fx = [[0.0, 0.0, W, H],                                          # the whole image (level 5)
+          [0.0, 0.0, 37.3, 41.9], [W - 33.7, 0.0, W, 29.1], [0.0, H - 45.3, 51.7, H], [W - 61.1, H - 57.7, W, H],      # touching the corners
+          [-23.3, 50.3, 40.9, 122.7], [W - 48.1, 77.7, W + 31.3, 160.3], [91.3, -19.1, 170.7, 44.3], [203.1, H - 39.3, 290.9, H + 27.7],
+          [-150.3, -120.7, 160.9, 170.3], [W - 140.7, H - 170.1, W + 190.3, H + 130.9],                               # crossing two borders
+          [-60.3, -44.1, -10.7, -3.3], [W + 12.3, 40.1, W + 90.7, 133.3],                                              # wholly outside
+          [120.0, 80.0, 120.0, 160.0], [200.0, 150.0, 260.0, 150.0], [300.0, 300.0, 300.0, 300.0],                    # zero width / height / both
+          [180.3, 90.1, 150.7, 140.9], [240.1, 220.3, 300.7, 190.1], [0.0, 0.0, 0.0, 0.0],                             # inverted; the clip's corner
+          [32.0, 48.0, 256.0, 272.0], [16.0, 32.0, 464.0, 144.0], [17.1, 33.3, 17.1 + 448.0, 33.3 + 112.0],            # sqrt(area) = 224
+          [16.0, 16.0, 464.0, 464.0], [64.0, 40.0, 576.0, 432.0], [61.3, 40.7, 61.3 + 512.0, 40.7 + 392.0],            # sqrt(area) = 448
+          [100.3, 100.7, 103.1, 102.9], [301.7, 55.3, 302.9, 61.1], [415.1, 200.3, 421.3, 200.9],                      # less than one cell
+          [8.0, 8.0, 16.0, 16.0], [160.0, 160.0, 168.0, 168.0]]                                                       # exactly one cell
+    g = torch.Generator().manual_seed(seed)
+    n = rows - len(fx)
+    assert n >= 0
+    ctr = torch.rand((n, 2), generator=g) * torch.tensor([float(W), float(H)])
+    half = torch.exp(torch.rand((n, 2), generator=g) * 4.0 + 1.8)
+    rnd = torch.cat([ctr - half, ctr + half], dim=1)
+    rnd[::3] = torch.stack([rnd[::3, 0].clamp(0, W), rnd[::3, 1].clamp(0, H), rnd[::3, 2].clamp(0, W), rnd[::3, 3].clamp(0, H)], dim=1)
+    return torch.cat([torch.tensor(fx, dtype=torch.float32), rnd.float()]).contiguous()
+
+
+def fragments_to_rows(buf: torch.Tensor, H: int, W: int) -> List[torch.Tensor]:
+    """The pooled operand of the memory read ([level][32-row tile][k-step][hi][r][8], every level padded to whole tiles) -> the
+    row-major [P_l, 512] rows of the three levels."""
+    out, t0 = [], 0
+    flat = buf.reshape(-1)
+    for s in (8, 16, 32):
+        rows = (H // s) * (W // s)
+        tiles = (rows + 31) // 32
+        blk = flat[t0 * 32 * 512:(t0 + tiles) * 32 * 512].view(tiles, 32, 2, 32, 8)
+        out.append(blk.permute(0, 3, 1, 2, 4).reshape(tiles * 32, 512)[:rows])
+        t0 += tiles
+    return out
