@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import math
 import os
+import re
 from collections import OrderedDict
 from typing import Dict, Optional, Tuple
 
@@ -184,6 +185,9 @@ def synthetic_state_dict(seed: int = 0, num_classes: int = 20,
     return sd
 
 
+_FREQ_WEIGHT = re.compile(r"roi_heads\.box_predictor\.\d+\.freq_weight")
+
+
 def load_checkpoint(path: str, num_classes: int = 20, verbose: bool = True):
     """Read a d2 `.pth` and return (state_dict, report).
 
@@ -208,7 +212,11 @@ def load_checkpoint(path: str, num_classes: int = 20, verbose: bool = True):
             continue
         sd[name] = t
     for name in model:
-        if name not in shapes:
+        if _FREQ_WEIGHT.fullmatch(name):
+            # the stage predictors' class-frequency buffers (USE_FED_LOSS / IGNORE_ZERO_CATS checkpoints): kept as they are; the
+            # trainer reads the frequencies from CAT_FREQ_PATH as the reference's constructor does
+            sd[name] = torch.as_tensor(model[name]).detach().to(torch.float32).cpu().contiguous()
+        elif name not in shapes:
             report["unexpected"].append(name)
     if verbose:
         for k, v in report.items():
@@ -225,10 +233,11 @@ def reset_cls_test(sd: Dict[str, torch.Tensor], zs_weight_path: str, num_classes
         sd[f"roi_heads.box_predictor.{k}.cls_score.zs_weight"] = w.clone()
 
 
-def fill_missing(sd: Dict[str, torch.Tensor], seed: int = 0, num_classes: int = 20) -> Dict[str, torch.Tensor]:
+def fill_missing(sd: Dict[str, torch.Tensor], seed: int = 0, num_classes: int = 20,
+                 zs_weight_path: str = DEFAULT_ZS_WEIGHT) -> Dict[str, torch.Tensor]:
     """Complete a partially loaded checkpoint with synthetic tensors (e.g. `map_merge_projection*`
-    when starting from a plain Detic checkpoint)."""
-    syn = synthetic_state_dict(seed, num_classes)
+    when starting from a plain Detic checkpoint).  `zs_weight_path`: the class matrix of `num_classes` classes."""
+    syn = synthetic_state_dict(seed, num_classes, zs_weight_path if os.path.exists(str(zs_weight_path)) else DEFAULT_ZS_WEIGHT)
     out = OrderedDict()
     for name in expected_shapes(num_classes):
         out[name] = sd[name] if name in sd else syn[name]

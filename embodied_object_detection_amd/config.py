@@ -131,6 +131,7 @@ def get_cfg() -> CfgNode:
                 "MULT_PROPOSAL_SCORE": False, "USE_SIGMOID_CE": False, "PRIOR_PROB": 0.01, "ADD_FEATURE_TO_PROP": False,
                 "ADD_IMAGE_BOX": False, "IMAGE_BOX_SIZE": 1.0, "WS_NUM_PROPS": 128,
                 "SMOOTH_L1_BETA": 0.0, "BBOX_REG_LOSS_TYPE": "smooth_l1", "BBOX_REG_LOSS_WEIGHT": 1.0, "USE_FED_LOSS": False,
+                "CAT_FREQ_PATH": "datasets/metadata/lvis_v1_train_cat_info.json", "FED_LOSS_NUM_CAT": 50, "FED_LOSS_FREQ_WEIGHT": 0.5,
             },
             "ROI_BOX_CASCADE_HEAD": {
                 "BBOX_REG_WEIGHTS": ((10.0, 10.0, 5.0, 5.0), (20.0, 20.0, 10.0, 10.0), (30.0, 30.0, 15.0, 15.0)),

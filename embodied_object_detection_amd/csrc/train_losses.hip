@@ -6,6 +6,8 @@
 // centernet_head.py:141-161).  Two launches: a dense pass over the P positions (negative term, regression term, their gradients;
 // per-workgroup partial sums in double) and one workgroup over the positive locations that also adds the partials in a fixed order.
 // Elementwise + reductions: HBM-bound, P x (stride + 5) floats read, P x stride written.
+#include <stdlib.h>
+
 #include "eod_common.h"
 #include "../../include/eod_hip.h"
 
@@ -238,6 +240,61 @@ __global__ __launch_bounds__(64) void fast_rcnn_loss_sum_kernel(BoxLossArgs a) {
   a.losses[1] = (float)(reg / (double)a.B);
 }
 
+// The federated loss's class choice (get_fed_loss_inds, detic/modeling/utils.py:16-28) as a 0 / 1 weight per class, one workgroup.
+// `appeared` = the distinct labels of the stage's rows, the background label C included (torch.unique(gt_classes) keeps it);
+// when fewer than num_sample_cats appeared, the missing ones are drawn among the classes c < C that did not appear and have
+// prob[c] > 0, as the largest prob[c] / q[c] (ties to the lower index): with q ~ Exp(1) that IS torch.multinomial without
+// replacement.  Fewer eligible classes than asked for: all of them.  Rank by counting over keys kept in LDS (C <= 2047).
+constexpr int FED_MAX_C = 2047;
+struct FedArgs {
+  const int* gt; int B; int C;
+  const int* hdr;                  // [4]: num_sample_cats, has prob, has zero-mask source, 0
+  const float* q; const float* prob; const float* mask_src;
+  float* cw;                       // [C]
+};
+
+__global__ __launch_bounds__(1024) void fed_loss_weight_kernel(FedArgs a) {
+  __shared__ float key[FED_MAX_C + 1];
+  __shared__ unsigned char app[FED_MAX_C + 1];
+  __shared__ int n_app;
+  const int tid = threadIdx.x, C = a.C;
+  for (int c = tid; c <= C; c += 1024) app[c] = 0;
+  if (tid == 0) n_app = 0;
+  __syncthreads();
+  for (int r = tid; r < a.B; r += 1024) {
+    const int g = a.gt[r];
+    if (g >= 0 && g <= C) app[g] = 1;            // rows marked -1 are no rows
+  }
+  __syncthreads();
+  const bool has_prob = a.hdr[1] != 0, has_mask = a.hdr[2] != 0;
+  int cnt = 0;
+  for (int c = tid; c <= C; c += 1024) {
+    cnt += app[c];
+    if (c < C) {
+      const float p = has_prob ? a.prob[c] : 1.f;
+      key[c] = (!app[c] && p > 0.f) ? p / a.q[c] : -1.f;      // < 0: not eligible
+    }
+  }
+  if (cnt) atomicAdd(&n_app, cnt);
+  __syncthreads();
+  const int need = a.hdr[0] - n_app;
+  for (int c = tid; c < C; c += 1024) {
+    bool on = app[c] != 0;
+    const float kc = key[c];
+    if (!on && need > 0 && kc >= 0.f) {
+      int rank = 0;
+      for (int j = 0; j < C; ++j) {
+        const float kj = key[j];
+        rank += (kj > kc || (kj == kc && j < c)) ? 1 : 0;
+      }
+      on = rank < need;
+    }
+    float w = on ? 1.f : 0.f;
+    if (has_mask) w *= a.mask_src[c] > 1e-4f ? 1.f : 0.f;      // IGNORE_ZERO_CATS (detic_fast_rcnn.py:223-225)
+    a.cw[c] = w;
+  }
+}
+
 // CenterNet target assignment for ONLY_PROPOSAL, one image (centernet.py:342-479).  Every comparison below decides a target, so the
 // arithmetic follows the reference's fp32 operations one by one (no fused multiply-add: `fp contract(off)`).
 struct CnTargetArgs {
@@ -383,7 +440,23 @@ extern "C" int eod_fast_rcnn_loss(const float* scores, int ld, const float* delt
                                   float ww, float wh, float smooth_l1_beta, float* d_scores, float* d_deltas, float* losses,
                                   void* workspace, size_t workspace_bytes, eod_stream_t stream) {
   if (!scores || !deltas || !proposal_boxes || !gt_boxes || !gt_classes || !d_scores || !d_deltas || !losses || !workspace) return EOD_ERR_NULL;
+  // EOD_LOSS_FED: the federated loss's class choice fills `class_weight` first, from the parameter block at the head of the workspace
+  const bool fed = num_classes > 0 && (num_classes & EOD_LOSS_FED) != 0;
+  if (fed) num_classes &= ~EOD_LOSS_FED;
   if (B <= 0 || num_classes <= 0 || ld < num_classes + 1 || !(smooth_l1_beta >= 0.f)) return EOD_ERR_BAD_DIMS;
+  if (fed) {
+    if (!class_weight) return EOD_ERR_NULL;
+    if (num_classes > FED_MAX_C) return EOD_ERR_CAPACITY;
+    const size_t head = EOD_FED_LOSS_PARAM_BYTES(num_classes);
+    if (workspace_bytes < head + eod_fast_rcnn_loss_workspace_bytes(B)) return EOD_ERR_CAPACITY;
+    if (!eod_aligned16(workspace)) return EOD_ERR_ALIGN;
+    const float* blk = static_cast<const float*>(workspace) + 4;
+    FedArgs f{gt_classes, B, num_classes, static_cast<const int*>(workspace), blk, blk + num_classes, blk + 2 * (size_t)num_classes,
+              const_cast<float*>(class_weight)};
+    hipLaunchKernelGGL(fed_loss_weight_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, f);
+    workspace = static_cast<char*>(workspace) + head;
+    workspace_bytes -= head;
+  }
   if (workspace_bytes < eod_fast_rcnn_loss_workspace_bytes(B)) return EOD_ERR_CAPACITY;
   BoxLossArgs a{};
   a.scores = scores; a.ld = ld; a.deltas = deltas; a.prop = proposal_boxes; a.gtb = gt_boxes; a.gt = gt_classes; a.cw = class_weight;
@@ -729,6 +802,173 @@ __global__ __launch_bounds__(256) void zs_logits_backward_kernel(const float* __
   for (int q = 0; q < 8; ++q) d_feat[(size_t)row * D + lane * 8 + q] = (clamped ? g[q] : g[q] - u[q] * dot) / denom;
 }
 
+
+// ------------------------------------------------------------------------------------------------------
+// Wide vocabularies (C1 > ZS_TRAIN_MAX_C, up to 2048 columns): the two products are GEMMs on the fp32 matrix cores
+// (v_mfma_f32_32x32x2_f32: exact fp32 products and sums), no atomics, fixed summation order, every row independent of the others.
+// ------------------------------------------------------------------------------------------------------
+constexpr int ZS_TRAIN_MAX_C = 24;          // the inference path's ZS_MAX_C: up to here the one-wave-per-row kernels above
+constexpr int ZS_TRAIN_WIDE_MAX_C1 = 2048;
+
+inline int zs_train_wide_env() {            // experiment knob: EOD_ZS_TRAIN_WIDE=0 keeps the one-wave-per-row kernels at every width
+  static const int v = [] {
+    const char* e = getenv("EOD_ZS_TRAIN_WIDE");
+    return e ? atoi(e) : 1;
+  }();
+  return v;
+}
+
+// Forward: the scheme of zs_wide_kernel (heads.hip) with the raw logit as its epilogue.  One workgroup per tile of 32 rows x 32
+// classes; its four waves split K = 512 into quarters, the partial tiles are summed through LDS in wave order.  Lane l = (i = l & 31,
+// h = l >> 5) of wave w owns channels 128 w + 64 h + s, s = 0..63: the A operand is 64 consecutive floats of row i, normalised in
+// registers, the B operand zs[k][c0 + i] is read as the matrix lies (dword loads: no alignment asked of C1).  The prologue is
+// zs_logits_kernel's, instruction for instruction: featn_out is bitwise that kernel's.  Columns [C1, ld) are not written.
+__global__ __launch_bounds__(256) void zs_logits_wide_kernel(const float* __restrict__ feat, const float* __restrict__ zs, int B, int C1,
+                                                              float temp, float* __restrict__ logits, int ld,
+                                                              float* __restrict__ featn_out) {
+  __shared__ float sh_den[32];                  // denominator of the tile's rows; < 0: no such row
+  __shared__ float red[4][32 * 32];             // the four K-quarters' partial tiles
+  const int D = 512;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  for (int j = 0; j < 8; ++j) {
+    const int row = row0 + wave * 8 + j;        // wave-uniform
+    float denom = -1.0f;
+    if (row < B) {
+      float x[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) x[q] = feat[(size_t)row * D + lane * 8 + q];
+      float ss = 0.f;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) ss += x[q] * x[q];
+      ss = wave_reduce_sum(ss);
+      denom = fmaxf(sqrtf(ss), 1e-12f);                            // F.normalize eps
+      if (featn_out && blockIdx.y == 0) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = temp * (x[q] / denom);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) featn_out[(size_t)row * D + lane * 8 + q] = x[q];
+      }
+    }
+    if (lane == 0) sh_den[wave * 8 + j] = denom;
+  }
+  __syncthreads();
+  const int i = lane & 31, h = lane >> 5;
+  const int kbase = wave * 128 + h * 64;
+  const float den = sh_den[i];
+  float xa[64];
+  if (den >= 0.f) {
+    const float* src = feat + (size_t)(row0 + i) * D + kbase;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * q);
+      xa[4 * q + 0] = v.x; xa[4 * q + 1] = v.y; xa[4 * q + 2] = v.z; xa[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int s = 0; s < 64; ++s) xa[s] = temp * (xa[s] / den);
+  } else {
+#pragma unroll
+    for (int s = 0; s < 64; ++s) xa[s] = 0.f;
+  }
+  const int cb = c0 + i;                         // this lane's class column of the B operand
+  const bool cok = cb < C1;
+  const float* zb = zs + (size_t)kbase * C1 + (cok ? cb : 0);
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+#pragma unroll
+  for (int s0 = 0; s0 < 64; s0 += 16) {
+    float bv[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) bv[s] = cok ? zb[(size_t)(s0 + s) * C1] : 0.f;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[s0 + s], bv[s], acc, 0, 0, 0);
+  }
+  // the quarters' sum, in wave order: C/D layout col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+  for (int q = 0; q < 16; ++q) red[wave][((q & 3) + 8 * (q >> 2) + 4 * h) * 32 + i] = acc[q];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = tid + 256 * q;
+    const int ri = e >> 5, c = c0 + (e & 31);
+    if (row0 + ri >= B || c >= C1) continue;
+    logits[(size_t)(row0 + ri) * ld + c] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+  }
+}
+
+// Backward, first launch: g[B,512] = temp * d_logits[B, :C1] . zs^T into d_feat.  One workgroup per tile of 32 rows x 32 channels,
+// the contraction runs over the classes: the four waves take quarters of the class range (Q classes each, Q even), the two lane
+// halves the halves of a quarter, so that lane (i, h) walks Q / 2 consecutive classes of ITS row of each operand --
+// d_logits[row0 + i][c] and zs[k0 + i][c] are both contiguous along c; no transposed class matrix.  Classes >= C1 contribute
+// zeros and are never read (d_logits holds garbage there by contract).  Partial tiles summed through LDS in wave order.
+__global__ __launch_bounds__(256) void zs_logits_backward_wide_kernel(const float* __restrict__ zs, const float* __restrict__ d_logits,
+                                                                       int ld, int B, int C1, float temp, float* __restrict__ g_out) {
+  __shared__ float red[4][32 * 32];
+  const int D = 512;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
+  const int i = lane & 31, h = lane >> 5;
+  const int Qh = (C1 + 7) / 8;                   // classes per lane half; a wave's quarter is 2 Qh
+  const int cbeg = (wave * 2 + h) * Qh;
+  const int cend = min(cbeg + Qh, C1);           // may be <= cbeg: this half has nothing
+  const bool rok = row0 + i < B;
+  const float* pa = d_logits + (size_t)(rok ? row0 + i : 0) * ld;
+  const float* pb = zs + (size_t)(k0 + i) * C1;
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+  for (int s0 = 0; s0 < Qh; s0 += 16) {          // wave-uniform trip count
+    float av[16], bv[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const int c = cbeg + s0 + s;
+      const bool ok = c < cend;
+      av[s] = (ok && rok) ? pa[c] : 0.f;
+      bv[s] = ok ? pb[c] : 0.f;
+    }
+#pragma unroll
+    for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int q = 0; q < 16; ++q) red[wave][((q & 3) + 8 * (q >> 2) + 4 * h) * 32 + i] = acc[q];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = tid + 256 * q;
+    const int ri = e >> 5;
+    if (row0 + ri >= B) continue;
+    g_out[(size_t)(row0 + ri) * D + k0 + (e & 31)] = (((red[0][e] + red[1][e]) + red[2][e]) + red[3][e]) * temp;
+  }
+}
+
+// Backward, second launch: the normalisation's Jacobian on the rows of g, in place; zs_logits_backward_kernel's own row / lane
+// ownership and arithmetic from `g` on.
+__global__ __launch_bounds__(256) void zs_logits_backward_finish_kernel(const float* __restrict__ feat, int B, float* __restrict__ d_feat) {
+  const int D = 512;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= B) return;
+  float u[8], g[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) { u[q] = feat[(size_t)row * D + lane * 8 + q]; g[q] = d_feat[(size_t)row * D + lane * 8 + q]; }
+  float ss = 0.f;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) ss += u[q] * u[q];
+  ss = wave_reduce_sum(ss);
+  const float norm = sqrtf(ss);
+  const float denom = fmaxf(norm, 1e-12f);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) u[q] = u[q] / denom;
+  float dot = 0.f;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) dot += g[q] * u[q];
+  dot = wave_reduce_sum(dot);
+  const bool clamped = !(norm > 1e-12f);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) d_feat[(size_t)row * D + lane * 8 + q] = (clamped ? g[q] : g[q] - u[q] * dot) / denom;
+}
+
 }  // namespace
 
 extern "C" int eod_match_label(const float* boxes, int R, const float* gt_boxes, const int32_t* gt_classes, int G, float iou_thresh,
@@ -773,6 +1013,11 @@ extern "C" int eod_zs_logits(const float* feat, const float* zs_weight, int B, i
                              float* featn_out, eod_stream_t stream) {
   if (!feat || !zs_weight || !logits) return EOD_ERR_NULL;
   if (B <= 0 || D != 512 || C1 < 1 || ld < C1) return EOD_ERR_BAD_DIMS;
+  if (C1 > ZS_TRAIN_MAX_C && C1 <= ZS_TRAIN_WIDE_MAX_C1 && zs_train_wide_env()) {
+    hipLaunchKernelGGL(zs_logits_wide_kernel, dim3((B + 31) / 32, (C1 + 31) / 32), dim3(256), 0, (hipStream_t)stream, feat, zs_weight, B,
+                       C1, temp, logits, ld, featn_out);
+    return eod_launch_status();
+  }
   hipLaunchKernelGGL(zs_logits_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, feat, zs_weight, B, C1, temp, logits, ld,
                      featn_out);
   return eod_launch_status();
@@ -782,6 +1027,12 @@ extern "C" int eod_zs_logits_backward(const float* feat, const float* zs_weight,
                                       float temp, float* d_feat, eod_stream_t stream) {
   if (!feat || !zs_weight || !d_logits || !d_feat) return EOD_ERR_NULL;
   if (B <= 0 || D != 512 || C1 < 1 || ld < C1) return EOD_ERR_BAD_DIMS;
+  if (C1 > ZS_TRAIN_MAX_C && C1 <= ZS_TRAIN_WIDE_MAX_C1 && zs_train_wide_env()) {
+    hipLaunchKernelGGL(zs_logits_backward_wide_kernel, dim3((B + 31) / 32, 512 / 32), dim3(256), 0, (hipStream_t)stream, zs_weight,
+                       d_logits, ld, B, C1, temp, d_feat);
+    hipLaunchKernelGGL(zs_logits_backward_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, feat, B, d_feat);
+    return eod_launch_status();
+  }
   hipLaunchKernelGGL(zs_logits_backward_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, feat, zs_weight, d_logits, ld, B, C1,
                      temp, d_feat);
   return eod_launch_status();

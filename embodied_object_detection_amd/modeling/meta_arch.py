@@ -154,7 +154,7 @@ class CustomRCNNRecurrent:
         if state_dict is None:
             if cfg.MODEL.WEIGHTS and str(cfg.MODEL.WEIGHTS).endswith((".pth", ".pkl")) and __import__("os").path.exists(cfg.MODEL.WEIGHTS):
                 sd, _ = load_checkpoint(cfg.MODEL.WEIGHTS, num_classes)
-                state_dict = fill_missing(sd, 0, num_classes)
+                state_dict = fill_missing(sd, 0, num_classes, cfg.MODEL.ROI_BOX_HEAD.ZEROSHOT_WEIGHT_PATH)
             else:
                 state_dict = synthetic_state_dict(0, num_classes, cfg.MODEL.ROI_BOX_HEAD.ZEROSHOT_WEIGHT_PATH)
         if cfg.MODEL.RESET_CLS_TESTS and cfg.MODEL.TEST_CLASSIFIERS:

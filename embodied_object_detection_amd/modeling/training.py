@@ -14,6 +14,7 @@ import torch
 
 from .. import ops
 from .backward import BackboneBackward
+from .fed_loss import FREQ_KEY, class_freq_from_cfg
 
 
 class ProposalTraining:
@@ -401,7 +402,12 @@ class ProposalTrainer:
         """The stepped parameters in the reference's names and layouts, on top of `base_sd` (the state dict the model was built from):
         what `DetectionCheckpointer` would save (`checkpoint.save_checkpoint` writes it; `load_checkpoint` + `build_model` read it)."""
         from .. import checkpoint
-        return checkpoint.export_state_dict(self.entries, base_sd, self.model.roi_heads.num_classes)
+        out = checkpoint.export_state_dict(self.entries, base_sd, self.model.roi_heads.num_classes)
+        fw = self.fm.det.freq_weight if self.fm is not None else None
+        if fw is not None:                     # the reference's state dicts carry the stage predictors' `freq_weight` buffers
+            for k in range(self.model.roi_heads.num_stages):
+                out[FREQ_KEY.format(k)] = fw.clone()
+        return out
 
     def optimizer_state(self) -> Dict:
         """The optimizer's moments and step counts by reference parameter name (the 'optimizer' entry of a checkpoint)."""
@@ -449,8 +455,6 @@ class DetectorTraining:
         if len(self.ious) != self.rh.num_stages or self.ious[0] != float(rhc.IOU_THRESHOLDS[0]):
             raise ValueError("ROI_BOX_CASCADE_HEAD.IOUS: one IoU per stage, the first equal to ROI_HEADS.IOU_THRESHOLDS[0] "
                              "(detectron2 CascadeROIHeads.from_config)")
-        if bool(rb.USE_FED_LOSS) or bool(rb.IGNORE_ZERO_CATS):
-            raise NotImplementedError("federated loss / zero-frequency categories need the LVIS frequency file (not on the MP3D path)")
         if str(rb.BBOX_REG_LOSS_TYPE) != "smooth_l1":
             raise NotImplementedError("ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE: smooth_l1 (the recurrent yaml)")
         self.batch, self.frac = int(rhc.BATCH_SIZE_PER_IMAGE), float(rhc.POSITIVE_FRACTION)
@@ -458,6 +462,18 @@ class DetectorTraining:
         self.beta, self.box_w = float(rb.SMOOTH_L1_BETA), float(rb.BBOX_REG_LOSS_WEIGHT)
         self.C = self.rh.num_classes
         self.last = None
+        # USE_FED_LOSS / IGNORE_ZERO_CATS (detic_fast_rcnn.py:85-96,213-225): the class frequencies (the reference's `freq_weight`
+        # buffer) are the federated draw's probabilities and the source of the zero-frequency mask.  The federated choice is made
+        # on the device, per stage and frame, from a `q` drawn from the step's generator; the zero mask alone is a constant weight
+        self.freq_weight = class_freq_from_cfg(cfg, self.C)
+        self.fed: Optional[List[ops.FedLossParams]] = None
+        self.class_weight: Optional[torch.Tensor] = None
+        if bool(rb.USE_FED_LOSS):
+            zero = self.freq_weight if bool(rb.IGNORE_ZERO_CATS) else None
+            self.fed = [ops.FedLossParams(self.C, int(rb.FED_LOSS_NUM_CAT), self.freq_weight, zero, self.dev)
+                        for _ in range(self.rh.num_stages)]
+        elif bool(rb.IGNORE_ZERO_CATS):
+            self.class_weight = (self.freq_weight > 1e-4).float().to(self.dev)
         # optimistic assumptions about data-dependent sizes instead of host round trips in the middle of the step (see
         # `label_and_sample`, `losses`): device-side booleans, True = the assumption did NOT hold; `ForwardModelTraining` reads them
         # once, after the whole step has been enqueued, and repeats the frame on the exact path if one is set
@@ -539,7 +555,16 @@ class DetectorTraining:
                     raise RuntimeError(f"cascade stage {k}: every refined box is empty")
                 _, _, cls, gtb = ops.match_label(boxes, gt_boxes, gt_classes, self.ious[k], self.C)
             rec = self.run_stage(P, boxes, k)
-            l, ds, dd = ops.fast_rcnn_loss(rec["logits"], rec["deltas"], boxes, gtb, cls, self.C, self.rh.cascade_weights[k], None, self.beta)
+            if self.fed is not None:
+                fed = self.fed[k]
+                fed.draw_q(generator)                                                    # stage order 0, 1, 2; nothing is read back
+                l, ds, dd, cw = ops.fast_rcnn_loss(rec["logits"], rec["deltas"], boxes, gtb, cls, self.C, self.rh.cascade_weights[k], None,
+                                                   self.beta, fed=fed)
+                rec.update(class_weight=cw, fed_q=fed.q.clone())
+            else:
+                l, ds, dd = ops.fast_rcnn_loss(rec["logits"], rec["deltas"], boxes, gtb, cls, self.C, self.rh.cascade_weights[k],
+                                               self.class_weight, self.beta)
+                rec.update(class_weight=self.class_weight)
             rec.update(classes=cls, gt_boxes=gtb, d_logits=ds, d_deltas=dd)
             stages.append(rec)
             out[f"loss_cls_stage{k}"] = l[0]

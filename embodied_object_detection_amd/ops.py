@@ -952,24 +952,110 @@ class CenterNetLoss:
         return self.losses, out
 
 
+EOD_LOSS_FED = 1 << 30          # include/eod_hip.h
+FED_MAX_C = 2047
+
+
+def fed_loss_param_bytes(num_classes: int) -> int:
+    """EOD_FED_LOSS_PARAM_BYTES of include/eod_hip.h."""
+    return (16 + 12 * num_classes + 15) & ~15
+
+
+class FedLossParams:
+    """The federated loss's inputs as `eod_fast_rcnn_loss` reads them (`num_classes | EOD_LOSS_FED`): the parameter block at the head
+    of a workspace this object owns.  `num_sample_cats`, `prob` [C] (None = ones: a uniform draw) and `zero_mask_src` [C] (None = no
+    IGNORE_ZERO_CATS mask) are written once; `q` is the block's own [C] view, to be refilled in place before every call
+    (`draw_q`: q ~ Exp(1), which makes the choice `torch.multinomial(prob, n, replacement=False)`)."""
+
+    def __init__(self, num_classes: int, num_sample_cats: int, prob: Optional[torch.Tensor], zero_mask_src: Optional[torch.Tensor],
+                 device):
+        C = int(num_classes)
+        if not 1 <= C <= FED_MAX_C:
+            raise ValueError(f"federated loss: 1 .. {FED_MAX_C} classes, got {C}")
+        if int(num_sample_cats) < 0:
+            raise ValueError("FED_LOSS_NUM_CAT must not be negative")
+        for name, t in (("prob", prob), ("zero_mask_src", zero_mask_src)):
+            if t is not None and tuple(t.shape) != (C,):
+                raise ValueError(f"federated loss: {name} must have one entry per class ({C}), got {tuple(t.shape)}")
+        self.C, self.num_sample_cats, self.device = C, int(num_sample_cats), torch.device(device)
+        self.head = fed_loss_param_bytes(C)
+        self._rows = 0
+        self._host = torch.zeros((self.head // 4,), dtype=torch.float32)
+        self._host[:4].view(torch.int32).copy_(torch.tensor([self.num_sample_cats, int(prob is not None), int(zero_mask_src is not None), 0],
+                                                            dtype=torch.int32))
+        self._host[4:4 + C] = 1.0
+        if prob is not None:
+            self._host[4 + C:4 + 2 * C] = prob.detach().float().cpu()
+        if zero_mask_src is not None:
+            self._host[4 + 2 * C:4 + 3 * C] = zero_mask_src.detach().float().cpu()
+        self.ws = None
+        self.reserve(512)
+
+    def reserve(self, B: int) -> None:
+        """Room for the loss's own workspace of B rows behind the block."""
+        if self.ws is not None and B <= self._rows:
+            return
+        n = self.head + int(_lib.load().eod_fast_rcnn_loss_workspace_bytes(B))
+        q = None if self.ws is None else self.q.clone()
+        self.ws = torch.empty((n // 4,), dtype=torch.float32, device=self.device)
+        self.ws[:self.head // 4].copy_(self._host)
+        self.q = self.ws[4:4 + self.C]
+        if q is not None:
+            self.q.copy_(q)
+        self._rows = B
+
+    def draw_q(self, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        return self.q.exponential_(1.0, generator=generator)
+
+    def set_q(self, q: torch.Tensor) -> None:
+        self.q.copy_(q.to(self.device, torch.float32).view(self.C))
+
+
 def fast_rcnn_loss(scores: torch.Tensor, deltas: torch.Tensor, proposal_boxes: torch.Tensor, gt_boxes: torch.Tensor,
                    gt_classes: torch.Tensor, num_classes: int, box_weights: Sequence[float], class_weight: Optional[torch.Tensor] = None,
-                   smooth_l1_beta: float = 0.0):
+                   smooth_l1_beta: float = 0.0, fed: Optional[FedLossParams] = None):
     """One cascade stage's `DeticFastRCNNOutputLayers.losses` (sigmoid CE + class-agnostic smooth-L1, detic_fast_rcnn.py:157-303) on the
-    device -> (losses [2] = loss_cls, loss_box_reg; dL/d(scores) [B, ld]; dL/d(deltas) [B,4]).  gt_classes int32, background = C."""
+    device -> (losses [2] = loss_cls, loss_box_reg; dL/d(scores) [B, ld]; dL/d(deltas) [B,4]).  gt_classes int32, background = C.
+
+    `fed`: the federated loss (USE_FED_LOSS): the class weight is chosen on the device from `fed`'s block (its `q` as it stands)
+    by one more launch in front of the loss, and returned as a fourth value ([C], 0 / 1)."""
     _need_cuda(scores, deltas, proposal_boxes, gt_boxes, gt_classes, class_weight)
     B, ld = scores.shape
     assert scores.is_contiguous() and tuple(deltas.shape) == (B, 4) and deltas.is_contiguous() and gt_classes.dtype == torch.int32
     lib = _lib.load()
-    nbytes = lib.eod_fast_rcnn_loss_workspace_bytes(B)
-    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=scores.device)
     losses = torch.empty((2,), dtype=torch.float32, device=scores.device)
     ds, dd = torch.empty_like(scores), torch.empty_like(deltas)
     wx, wy, ww, wh = box_weights
+    if fed is not None:
+        if class_weight is not None or fed.C != num_classes:
+            raise ValueError("fast_rcnn_loss: `fed` chooses the class weight itself, for its own number of classes")
+        fed.reserve(B)
+        class_weight = torch.empty((num_classes,), dtype=torch.float32, device=scores.device)
+        ws, nbytes, flag = fed.ws, fed.ws.numel() * 4, EOD_LOSS_FED
+    else:
+        nbytes, flag = lib.eod_fast_rcnn_loss_workspace_bytes(B), 0
+        ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=scores.device)
     check(lib.eod_fast_rcnn_loss(scores.data_ptr(), ld, deltas.data_ptr(), proposal_boxes.data_ptr(), gt_boxes.data_ptr(),
-                                 gt_classes.data_ptr(), _ptr(class_weight), B, num_classes, wx, wy, ww, wh, smooth_l1_beta, ds.data_ptr(),
-                                 dd.data_ptr(), losses.data_ptr(), ws.data_ptr(), nbytes, _stream()), "eod_fast_rcnn_loss")
+                                 gt_classes.data_ptr(), _ptr(class_weight), B, num_classes | flag, wx, wy, ww, wh, smooth_l1_beta,
+                                 ds.data_ptr(), dd.data_ptr(), losses.data_ptr(), ws.data_ptr(), nbytes, _stream()), "eod_fast_rcnn_loss")
+    if fed is not None:
+        return losses, ds, dd, class_weight
     return losses, ds, dd
+
+
+def fed_loss_weight(gt_classes: torch.Tensor, num_classes: int, q: torch.Tensor, num_sample_cats: int,
+                    prob: Optional[torch.Tensor] = None, zero_mask_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The federated loss's class weight alone ([C] of 0 / 1) for labels int32 [B] (background = C, -1 = no row) and the caller's
+    `q` [C]: the launch lives on `eod_fast_rcnn_loss`, which is run here on zero scores.  Deterministic in its inputs; when fewer
+    classes are eligible (not appeared, prob > 0) than are missing, all of them are taken (torch's CPU multinomial raises there)."""
+    _need_cuda(gt_classes, q)
+    B, dev = int(gt_classes.numel()), gt_classes.device
+    fed = FedLossParams(num_classes, num_sample_cats, prob, zero_mask_src, dev)
+    fed.set_q(q)
+    z = torch.zeros((B, num_classes + 1), dtype=torch.float32, device=dev)
+    box = torch.tensor([0.0, 0.0, 1.0, 1.0], device=dev).repeat(B, 1)
+    return fast_rcnn_loss(z, torch.zeros((B, 4), device=dev), box, box, gt_classes.to(torch.int32).contiguous(), num_classes,
+                          (1.0, 1.0, 1.0, 1.0), fed=fed)[3]
 
 
 def match_label(boxes: torch.Tensor, gt_boxes: torch.Tensor, gt_classes: torch.Tensor, iou_thresh: float, num_classes: int):

@@ -109,7 +109,7 @@ def do_train(cfg, args, rank: int, world: int):
         resume_state = load_training_state(weights)
         print(f"[train] resuming from {weights} (iteration {resume_state['iteration']})")
     if weights and os.path.exists(weights):
-        sd = fill_missing(load_checkpoint(weights, num_classes)[0], 0, num_classes)
+        sd = fill_missing(load_checkpoint(weights, num_classes)[0], 0, num_classes, cfg.MODEL.ROI_BOX_HEAD.ZEROSHOT_WEIGHT_PATH)
     else:
         sd = synthetic_state_dict(0, num_classes, cfg.MODEL.ROI_BOX_HEAD.ZEROSHOT_WEIGHT_PATH)
     model = build_model(cfg, sd)

@@ -287,7 +287,22 @@ int eod_centernet_targets(const EodCenterNetTargetDesc* d, eod_stream_t stream);
  * CLS_AGNOSTIC_BBOX_REG (detic_fast_rcnn.py:157-197): sigmoid_cross_entropy_loss (:200-233; class_weight [C] = federated-loss mask x
  * zero-frequency mask, or NULL) and box_reg_loss (:270-303, smooth_l1; beta 0 = L1) against Box2BoxTransform.get_deltas(proposal, gt)
  * with the stage's weights.  scores [B, ld] logits (columns 0..C, C = background), gt_classes [B] in [0, C]; every column of d_scores
- * is written (background and padding: 0).  losses [2] = loss_cls, loss_box_reg.  The sampled / matched proposals are inputs. */
+ * is written (background and padding: 0).  losses [2] = loss_cls, loss_box_reg.  The sampled / matched proposals are inputs.
+ *
+ * Federated loss (USE_FED_LOSS, get_fed_loss_inds of detic/modeling/utils.py:16-28): pass `num_classes | EOD_LOSS_FED` (C <= 2047).
+ * One more launch, in front of the loss, then WRITES class_weight [C] (0 / 1) and the loss reads it: weight 1 for the distinct
+ * labels of gt_classes (rows of -1 ignored; the background label C counts as a label that appeared, as torch.unique does there)
+ * and, when fewer than num_sample_cats labels appeared, for the missing number of classes drawn among those c < C that did not
+ * appear and have prob[c] > 0: the largest prob[c] / q[c], ties to the lower index -- with q ~ Exp(1) drawn by the caller this is
+ * torch.multinomial(prob, n, replacement=False), and the result is a function of the inputs.  Fewer such classes than asked for:
+ * all of them.  With a zero-mask source the weight is also multiplied by (src[c] > 1e-4) (IGNORE_ZERO_CATS).  The inputs are a
+ * parameter block of EOD_FED_LOSS_PARAM_BYTES(C) bytes at the head of the workspace (device memory, 16-byte aligned), the loss's
+ * own eod_fast_rcnn_loss_workspace_bytes(B) bytes follow it:
+ *   int32 [4]  num_sample_cats, prob present (0 / 1: 0 = ones), zero-mask source present (0 / 1), 0
+ *   float [C]  q;   float [C]  prob;   float [C]  zero-mask source   (all three always have their place in the block)
+ * Without the flag the call is what it always was. */
+#define EOD_LOSS_FED (1 << 30)
+#define EOD_FED_LOSS_PARAM_BYTES(C) ((16 + 12 * (size_t)(C) + 15) & ~(size_t)15)
 size_t eod_fast_rcnn_loss_workspace_bytes(int B);
 int eod_fast_rcnn_loss(const float* scores, int ld, const float* deltas /*[B,4]*/, const float* proposal_boxes, const float* gt_boxes,
                        const int32_t* gt_classes, const float* class_weight, int B, int num_classes, float wx, float wy, float ww,
@@ -319,12 +334,15 @@ int eod_sample_proposals(const int32_t* classes, const float* keys /*[R] uniform
                          int batch_size_per_image, float positive_fraction, int32_t* sampled_idx, int32_t* counts, eod_stream_t stream);
 /* eod_zs_logits: the scores DeticFastRCNNOutputLayers.forward returns in training (detic_fast_rcnn.py:437-466 with
  * zero_shot_classifier.py:71-111, NORM_WEIGHT, no bias): logits [B, ld] (columns 0..C1-1) = temp * normalize(feat [B,512]) . zs_weight
- * [512, C1]; featn_out [B,512] (optional) = the normalised, scaled feature.  Any C1. */
+ * [512, C1]; featn_out [B,512] (optional) = the normalised, scaled feature.  Any C1: up to 24 columns one wave per row (the
+ * summation order of eod_zs_classify), 25 .. 2048 columns a GEMM on the fp32 matrix cores (fixed order, a row's result independent
+ * of B, featn_out bitwise the narrow kernel's); columns [C1, ld) are not written. */
 int eod_zs_logits(const float* feat, const float* zs_weight, int B, int D /*512*/, int C1, float temp, float* logits, int ld,
                   float* featn_out, eod_stream_t stream);
 
 /* eod_zs_logits_backward: d feat [B,512] of eod_zs_logits given d_logits [B, ld] (F.normalize's and torch.mm's autograd; the class
- * matrix is a buffer, zero_shot_classifier.py:54). */
+ * matrix is a buffer, zero_shot_classifier.py:54).  Columns >= C1 of d_logits are never read.  25 .. 2048 columns: two launches
+ * (the product on the fp32 matrix cores into d_feat, then the normalisation's Jacobian in place). */
 int eod_zs_logits_backward(const float* feat, const float* zs_weight, const float* d_logits, int ld, int B, int D /*512*/, int C1,
                            float temp, float* d_feat, eod_stream_t stream);
 

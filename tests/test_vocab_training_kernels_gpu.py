@@ -1,0 +1,242 @@
+"""Training on wide vocabularies, the kernels: the logits and their backward as GEMMs on the fp32 matrix cores (C1 > 24) against
+float64, the dispatch boundary at 24 / 25 columns, the federated loss's class choice against its restatement, and the loss with a
+0 / 1 class weight at 1203 classes.
+
+The bounds are those of tests/test_training_launches_gpu.py (U = 2^-24, the number of roundings, the magnitudes they act on); the
+error of the same computation in CPU fp32 is printed beside each."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from _fed_loss_ref import fed_loss_weight_ref
+from oracle import losses as OL
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -24
+SENTINEL = 7.0e30
+TEMP = 50.0
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    from embodied_object_detection_amd import _lib
+    _lib.load()
+    return torch.device("cuda:0")
+
+
+def _inputs(B, C1, ld, seed):
+    g = torch.Generator().manual_seed(seed)
+    zs = F.normalize(torch.randn((512, C1), generator=g), p=2, dim=0)
+    zs[:, -1] = 0                                                                          # the background column
+    feat = torch.randn((B, 512), generator=g) * torch.exp(torch.randn((B, 1), generator=g))     # norms over two decades
+    dl = torch.randn((B, ld), generator=g) / C1
+    dl[:, C1:] = SENTINEL                                                                  # garbage by contract: never read
+    return zs.contiguous(), feat.contiguous(), dl.contiguous()
+
+
+def _reference(feat, zs, dl, C1, dtype):
+    f = feat.to(dtype).requires_grad_()
+    fn = TEMP * F.normalize(f, p=2, dim=1)
+    lg = fn @ zs.to(dtype)
+    (lg * dl[:, :C1].to(dtype)).sum().backward()
+    return lg.detach(), fn.detach(), f.grad
+
+
+def _bounds(feat, zs, dl, C1, fn):
+    lb = (512 + 16) * U * (fn.abs() @ zs.double().abs())
+    fb = 2.0 * (512 + 16) / 2 * U * fn.abs()
+    A = dl[:, :C1].double().abs() @ zs.double().abs().t()
+    unit = (fn / TEMP).abs()
+    scale = TEMP / feat.double().norm(dim=1, keepdim=True)
+    db = 2.0 * (C1 + 512 + 16) * U * scale * (A + unit * (unit * A).sum(dim=1, keepdim=True))
+    return lb, fb, db
+
+
+def _share(err, bound):
+    return float((err.detach() / bound.detach().clamp(min=1e-300)).max())
+
+
+@pytest.mark.parametrize("C1", [25, 41, 366, 501, 1204, 2048])
+@pytest.mark.parametrize("B", [1, 31, 512, 536])
+def test_wide_logits_and_backward_against_float64(dev, B, C1):
+    from embodied_object_detection_amd import ops
+    for ld in (C1, C1 + 12):
+        zs, feat, dl = _inputs(B, C1, ld, 1000 * C1 + B)
+        zd, fd, dd = zs.to(dev), feat.to(dev), dl.to(dev)
+        featn = torch.full((B + 1, 512), SENTINEL, device=dev)
+        logits = ops.zs_logits(fd, zd, TEMP, ld=ld, featn_out=featn[:B])
+        d_feat = ops.zs_logits_backward(fd, zd, dd, TEMP)
+        lg, fn, df = _reference(feat, zs, dl, C1, torch.float64)
+        lg32, fn32, df32 = _reference(feat, zs, dl, C1, torch.float32)
+        lb, fb, db = _bounds(feat, zs, dl, C1, fn)
+        le, fe, de = (logits[:, :C1].cpu().double() - lg).abs(), (featn[:B].cpu().double() - fn).abs(), (d_feat.cpu().double() - df).abs()
+        print(f"\nB {B} C1 {C1} ld {ld}: logits {_share(le, lb):.3f} of the bound (cpu fp32 {_share((lg32.double() - lg).abs(), lb):.3f}), "
+              f"featn {_share(fe, fb):.3f} ({_share((fn32.double() - fn).abs(), fb):.3f}), "
+              f"d_feat {_share(de, db):.3f} ({_share((df32.double() - df).abs(), db):.3f})")
+        assert bool((le <= lb).all()), (ld, float(le.max()))
+        assert bool((fe <= fb).all()) and bool((featn[B:] == SENTINEL).all()), ld
+        assert bool(torch.isfinite(d_feat).all()) and bool((de <= db).all()), (ld, float(de.max()))     # a read of the sentinel shows here
+        if ld > C1:
+            assert bool((logits[:, C1:] == 0).all()), "columns [C1, ld) must stay the zeros the wrapper allocated"
+        # featn is the narrow kernel's, bit for bit (the same rows through a 24-column slice of the same matrix)
+        featn24 = torch.empty((B, 512), device=dev)
+        ops.zs_logits(fd, zd[:, :24].contiguous(), TEMP, featn_out=featn24)
+        assert torch.equal(featn[:B], featn24)
+        # fixed order: a second run is the same bits
+        featn2 = torch.empty((B, 512), device=dev)
+        assert torch.equal(ops.zs_logits(fd, zd, TEMP, ld=ld, featn_out=featn2), logits) and torch.equal(featn2, featn[:B])
+        assert torch.equal(ops.zs_logits_backward(fd, zd, dd, TEMP), d_feat)
+        # a row's results do not depend on B
+        for r in sorted({0, B // 2, B - 1}):
+            l1 = ops.zs_logits(fd[r:r + 1].contiguous(), zd, TEMP, ld=ld)
+            d1 = ops.zs_logits_backward(fd[r:r + 1].contiguous(), zd, dd[r:r + 1].contiguous(), TEMP)
+            assert torch.equal(l1[0], logits[r]) and torch.equal(d1[0], d_feat[r]), r
+
+
+def test_the_normalisation_clamp_row(dev):
+    """A zero feature row (F.normalize's eps): logits 0, d_feat = g / eps as autograd gives it, in both kernels' ranges."""
+    from embodied_object_detection_amd import ops
+    for C1 in (21, 366):
+        zs, feat, dl = _inputs(5, C1, C1, 77)
+        feat[2] = 0
+        logits = ops.zs_logits(feat.to(dev), zs.to(dev), TEMP)
+        d_feat = ops.zs_logits_backward(feat.to(dev), zs.to(dev), dl.to(dev), TEMP)
+        _, _, df = _reference(feat, zs, dl, C1, torch.float64)
+        assert float(logits[2].abs().max()) == 0.0
+        assert bool(torch.isfinite(d_feat).all())
+        assert float((d_feat[2].cpu().double() - df[2]).abs().max()) <= 1e-5 * float(df[2].abs().max())
+
+
+@pytest.mark.parametrize("B", [1, 77, 512])
+def test_dispatch_boundary_24_and_25_columns(dev, B):
+    """A 25-column matrix (matrix cores) and its 24-column prefix (one wave per row): two kernels, two summation orders, one result."""
+    from embodied_object_detection_amd import ops
+    zs, feat, dl = _inputs(B, 25, 25, 4242 + B)
+    dl[:, 24] = 0
+    zd, fd = zs.to(dev), feat.to(dev)
+    fn25, fn24 = torch.empty((B, 512), device=dev), torch.empty((B, 512), device=dev)
+    l25 = ops.zs_logits(fd, zd, TEMP, featn_out=fn25)
+    l24 = ops.zs_logits(fd, zd[:, :24].contiguous(), TEMP, featn_out=fn24)
+    d25 = ops.zs_logits_backward(fd, zd, dl.to(dev), TEMP)
+    d24 = ops.zs_logits_backward(fd, zd[:, :24].contiguous(), dl[:, :24].contiguous().to(dev), TEMP)
+    lg, fn, df = _reference(feat, zs, dl, 25, torch.float64)
+    lb, _, db = _bounds(feat, zs, dl, 25, fn)
+    assert torch.equal(fn25, fn24)
+    for got in (l25[:, :24], l24):
+        assert bool(((got.cpu().double() - lg[:, :24]).abs() <= lb[:, :24]).all())
+    for got in (d25, d24):
+        assert bool(((got.cpu().double() - df).abs() <= db).all())
+    print(f"\nB {B}: 24 vs 25 columns differ by {float((l25[:, :24] - l24).abs().max()):.3e} (logits), {float((d25 - d24).abs().max()):.3e} (d_feat)")
+
+
+def _labels(g, C, n_fg, with_bg, rows=512):
+    fg = torch.randperm(C, generator=g)[:n_fg]
+    gt = fg[torch.randint(0, max(n_fg, 1), (rows,), generator=g)] if n_fg else torch.zeros((0,), dtype=torch.long)
+    parts = [fg, gt]                                                     # every one of the n_fg labels at least once
+    if with_bg:
+        parts.append(torch.full((rows // 2,), C))
+    parts.append(torch.full((9,), -1))                                   # rows that are no rows
+    gt = torch.cat(parts)
+    return gt[torch.randperm(gt.numel(), generator=g)].int()
+
+
+@pytest.mark.parametrize("C", [20, 365, 1203, 2047])
+def test_fed_loss_class_choice_against_the_restatement(dev, C):
+    from embodied_object_detection_amd import ops
+    n = 50 if C > 50 else 8
+    g = torch.Generator().manual_seed(C)
+    freq = torch.rand((C,), generator=g) ** 2 * 40
+    freq[torch.randperm(C, generator=g)[:C // 4]] = 0.0
+    cases = 0
+    for with_prob in (False, True):
+        for with_bg in (False, True):
+            for n_fg in (0, 1, n // 2, n - 1, n, min(C, n + 7)):         # |appeared| below / equal / above num_sample_cats
+                if n_fg == 0 and not with_bg:
+                    continue
+                for mask in (False, True):
+                    gt = _labels(g, C, n_fg, with_bg)
+                    q = torch.empty((C,)).exponential_(1, generator=g)
+                    prob = freq if with_prob else None
+                    w = ops.fed_loss_weight(gt.to(dev), C, q.to(dev), n, None if prob is None else prob.to(dev),
+                                            freq.to(dev) if mask else None).cpu()
+                    ref = fed_loss_weight_ref(gt, C, q, n, prob, freq if mask else None)
+                    assert torch.equal(w, ref), (C, with_prob, with_bg, n_fg, mask, (w != ref).nonzero().flatten().tolist()[:8])
+                    if not mask:
+                        appeared = n_fg + int(with_bg)
+                        assert int(w.sum()) == max(n, appeared) - int(with_bg)
+                        if with_prob:
+                            drawn = w.clone()
+                            drawn[gt[(gt >= 0) & (gt < C)].long()] = 0
+                            assert float((drawn * (freq == 0)).sum()) == 0.0, "a zero-probability class was drawn"
+                    cases += 1
+    assert cases == 44
+
+
+def test_fed_loss_class_choice_ties_and_too_few_eligible(dev):
+    from embodied_object_detection_amd import ops
+    C = 365
+    # all keys equal: the lower class index wins
+    gt = torch.tensor([300, 7, 7, C], dtype=torch.int32)
+    w = ops.fed_loss_weight(gt.to(dev), C, torch.ones(C, device=dev), 10).cpu()
+    assert w.nonzero().flatten().tolist() == [0, 1, 2, 3, 4, 5, 6, 7, 300] and torch.equal(w, fed_loss_weight_ref(gt, C, torch.ones(C), 10))
+    # blocks of equal keys under a real prob
+    prob = torch.tensor([float(1 + (c % 3)) for c in range(C)])
+    q = torch.tensor([float(1 + (c % 2)) for c in range(C)])
+    w = ops.fed_loss_weight(gt.to(dev), C, q.to(dev), 40, prob.to(dev)).cpu()
+    assert torch.equal(w, fed_loss_weight_ref(gt, C, q, 40, prob)) and int(w.sum()) == 39
+    # fewer eligible classes than asked for: all of them, and nothing else
+    prob = torch.zeros(C)
+    prob[[3, 100, 364]] = 2.0
+    w = ops.fed_loss_weight(gt.to(dev), C, q.to(dev), 40, prob.to(dev)).cpu()
+    assert w.nonzero().flatten().tolist() == [3, 7, 100, 300, 364]
+    # deterministic: twice the same bits
+    g = torch.Generator().manual_seed(3)
+    q = torch.empty((C,)).exponential_(1, generator=g).to(dev)
+    a, b = ops.fed_loss_weight(gt.to(dev), C, q, 50), ops.fed_loss_weight(gt.to(dev), C, q, 50)
+    assert torch.equal(a, b) and int(a.sum()) == 49
+    with pytest.raises(ValueError):
+        ops.fed_loss_weight(gt.to(dev), 2048, torch.ones(2048, device=dev), 50)
+
+
+@pytest.mark.parametrize("C,fed", [(1203, False), (1203, True), (2047, False)])
+def test_loss_with_a_zero_one_class_weight_matches_the_oracle(dev, C, fed):
+    """`eod_fast_rcnn_loss` at LVIS width with a 0 / 1 class weight (given, or chosen by the call itself) against the oracle's
+    sigmoid_cross_entropy_loss in float64 under autograd."""
+    from embodied_object_detection_amd import ops
+    B, ld = 512, C + 1
+    g = torch.Generator().manual_seed(C + int(fed))
+    logits = torch.randn((B, ld), generator=g) * 4
+    gt = torch.cat([torch.randint(0, C, (90,), generator=g), torch.full((B - 90,), C)]).int()
+    box = torch.tensor([[10.0, 10.0, 50.0, 60.0]]).repeat(B, 1)
+    deltas = torch.zeros((B, 4))
+    q = torch.empty((C,)).exponential_(1, generator=g)
+    freq = torch.rand((C,), generator=g)
+    if fed:
+        params = ops.FedLossParams(C, 50, freq, None, dev)
+        params.set_q(q)
+        losses, ds, _, cw = ops.fast_rcnn_loss(logits.to(dev), deltas.to(dev), box.to(dev), box.to(dev), gt.to(dev), C, (10.0, 10.0, 5.0, 5.0),
+                                               None, 0.0, fed=params)
+        cw = cw.cpu()
+        assert torch.equal(cw, fed_loss_weight_ref(gt, C, q, 50, freq))
+    else:
+        cw = (torch.rand((C,), generator=g) < 0.05).float()
+        losses, ds, _ = ops.fast_rcnn_loss(logits.to(dev), deltas.to(dev), box.to(dev), box.to(dev), gt.to(dev), C, (10.0, 10.0, 5.0, 5.0),
+                                           cw.to(dev), 0.0)
+    x = logits.double().requires_grad_()
+    ref = OL.sigmoid_cross_entropy_loss(x, gt.long(), cw.double())
+    ref.backward()
+    x32 = logits.clone().requires_grad_()
+    ref32 = OL.sigmoid_cross_entropy_loss(x32, gt.long(), cw)
+    ref32.backward()
+    terms = float(cw.sum()) * B
+    bound = (terms / B) * 4 * U * 20.0 + 4 * U * abs(float(ref))        # per-term rounding of values <= ~20, summed in double, /B
+    err = abs(float(losses[0]) - float(ref))
+    gerr = (ds.cpu().double() - x.grad).abs()
+    gbound = 8 * U / B * torch.ones_like(gerr)                           # sigmoid (expf + divide) and two products, values <= 1 / B
+    print(f"\nC {C} fed {fed}: loss {float(ref):.6f} err {err:.3e} (cpu fp32 {abs(float(ref32) - float(ref)):.3e}, bound {bound:.3e}); "
+          f"d_scores err {float(gerr.max()):.3e} (cpu fp32 {float((x32.grad.double() - x.grad).abs().max()):.3e}, bound {float(gbound.max()):.3e})")
+    assert err <= bound and bool((gerr <= gbound).all())
+    assert float(ds[:, C:].abs().max()) == 0.0 and float(ds.cpu()[:, :C][:, cw == 0].abs().max()) == 0.0
+    assert float(losses[1]) == 0.0

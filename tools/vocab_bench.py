@@ -3,6 +3,12 @@
 `memory_scores` and of both selections, launch alone, at each width.
 
     python tools/vocab_bench.py [--out profiles/vocab_bench.txt] [--frames 40]
+
+`train`: the two logits launches of the training step alone (`eod_zs_logits`, `eod_zs_logits_backward`, B = 512) at 25 to 2048
+columns, the one-wave-per-row kernels against the matrix-core ones, and the federated loss's class choice + loss launches.  The
+kernels are chosen by EOD_ZS_TRAIN_WIDE, read once when the library loads, so each side is timed in a child process of its own.
+
+    python tools/vocab_bench.py train [--out profiles/vocab_train_bench.txt]
 """
 from __future__ import annotations
 
@@ -40,11 +46,75 @@ def timed_us(fn, iters: int = 50, warm: int = 5) -> float:
     return float(np.median(ts))
 
 
+TRAIN_WIDTHS = (25, 41, 366, 1204, 2048)
+
+
+def train_child() -> None:
+    """One JSON line: microseconds per launch at every width, with the kernels this process's environment selects."""
+    import json
+    from embodied_object_detection_amd import ops
+    dev = torch.device("cuda:0")
+    B = 512
+    g = torch.Generator().manual_seed(2)
+    feat = torch.randn((B, 512), generator=g).to(dev)
+    out = {}
+    for C1 in TRAIN_WIDTHS:
+        zs = F.normalize(torch.randn((512, C1), generator=g), p=2, dim=0).contiguous().to(dev)
+        dl = (torch.randn((B, C1), generator=g) / C1).to(dev)
+        featn = torch.empty((B, 512), device=dev)
+        fw = timed_us(lambda: ops.zs_logits(feat, zs, 50.0, featn_out=featn))
+        alloc = timed_us(lambda: torch.zeros((B, C1), device=dev))                 # the wrapper's own zero-filled output
+        bw = timed_us(lambda: ops.zs_logits_backward(feat, zs, dl, 50.0))
+        out[C1] = [round(fw - alloc, 1), round(bw, 1)]
+    for C in (20, 365, 1203, 2047):
+        gt = torch.cat([torch.randint(0, C, (128,), generator=g), torch.full((384,), C)]).int().to(dev)
+        fed = ops.FedLossParams(C, 50, torch.rand((C,), generator=g) + 0.1, None, dev)
+        fed.draw_q()
+        scores, box = torch.randn((B, C + 1), generator=g).to(dev), torch.tensor([0.0, 0.0, 8.0, 8.0], device=dev).repeat(B, 1)
+        deltas = torch.zeros((B, 4), device=dev)
+        cw = torch.ones((C,), device=dev)
+        plain = timed_us(lambda: ops.fast_rcnn_loss(scores, deltas, box, box, gt, C, (10.0, 10.0, 5.0, 5.0), cw))
+        with_choice = timed_us(lambda: ops.fast_rcnn_loss(scores, deltas, box, box, gt, C, (10.0, 10.0, 5.0, 5.0), fed=fed))
+        out[f"fed{C}"] = [round(plain, 1), round(with_choice, 1)]
+    print("TRAIN_BENCH " + json.dumps(out), flush=True)
+
+
+def train_parent(out_path) -> None:
+    import json
+    import subprocess
+    res = {}
+    for wide in ("0", "1"):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "train", "--child"], env=dict(os.environ, EOD_ZS_TRAIN_WIDE=wide),
+                           capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            raise SystemExit(f"child with EOD_ZS_TRAIN_WIDE={wide} failed ({r.returncode}):\n{r.stdout[-2000:]}{r.stderr[-2000:]}")
+        res[wide] = json.loads([l for l in r.stdout.splitlines() if l.startswith("TRAIN_BENCH ")][-1][len("TRAIN_BENCH "):])
+    lines = ["B = 512, event-timed median of 50 single launches, microseconds (forward without the wrapper's zero fill)",
+             "columns  forward one-wave-per-row  forward matrix cores  backward one-wave-per-row  backward matrix cores (2 launches)"]
+    for C1 in TRAIN_WIDTHS:
+        o, n = res["0"][str(C1)], res["1"][str(C1)]
+        lines.append(f"{C1:7d}  {o[0]:24.1f}  {n[0]:20.1f}  {o[1]:25.1f}  {n[1]:21.1f}")
+    lines.append("classes  loss launches with a given weight  with the federated class choice in front (3 launches)")
+    for C in (20, 365, 1203, 2047):
+        v = res["1"][f"fed{C}"]
+        lines.append(f"{C:7d}  {v[0]:35.1f}  {v[1]:40.1f}")
+    text = "\n".join(lines) + "\n"
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    print(text)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("mode", nargs="?", default="frames", choices=["frames", "train"])
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=None)
     ap.add_argument("--frames", type=int, default=40)
     args = ap.parse_args()
+    if args.mode == "train":
+        return train_child() if args.child else train_parent(args.out)
     from embodied_object_detection_amd import build_model, ops, setup_cfg
     from embodied_object_detection_amd.checkpoint import synthetic_state_dict
     from embodied_object_detection_amd.data.synthetic import SyntheticSequence
