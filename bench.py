@@ -10,6 +10,12 @@ post-process -> memory write), inputs (u8 image, int32 proj_indices) already res
 independent scenes per rank (weak scaling, no data-path collective); after the timed region the ranks exchange their
 per-rank detection records with ONE RCCL all-reduce (fixed-shape buffer, each rank fills its slice) for the aggregate
 AP50, as the north star asks.  Rank 0 prints one JSON line.
+
+A plain run does what the headline needs and nothing more: set up, warm up, time the K steps, write `--dump-outputs`, print the
+line (metric, value, ms_per_step, the static configuration).  `--full` goes on, after the same timed region, with everything
+else the line can carry: the untimed replay for the per-frame counts, the rooflines of the dominant kernel and of the HBM-bound
+class, the sibling and variant timings (host inputs, enqueue only, mask work as the reference issues it, bf16x3, lock-step,
+configs[4] at 960x960, the training iteration), the AP50 collective and the CPU baseline.  The `--no-*` switches trim a `--full` run.
 """
 from __future__ import annotations
 
@@ -43,6 +49,9 @@ def parse():
     ap.add_argument("--grid", type=int, nargs=2, default=[200, 200], metavar=("MAP_W", "MAP_H"))
     ap.add_argument("--cell", type=float, default=0.2)
     ap.add_argument("--memory-thresh", type=float, default=0.3, help="MODEL.MEMORY_CLS_SCORE_THRESH (0.0 = worst-case write path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: per-frame counts (untimed "
+                         "replay), rooflines, variants, the AP50 collective, the CPU baseline; the --no-* switches below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=240.0, help="stop the CPU baseline after this many seconds of frames")
     ap.add_argument("--cpu-frames", type=int, default=20, help="timed CPU frames (SURVEY 8d: >= 20)")
@@ -689,7 +698,8 @@ def main():
 
     # ---- headline: through the boundary, inputs resident in HBM -------------------------------------------------------------
     # The timed region carries NO device-side instrumentation launches: HIP events around the mask-conv launches only (tagged
-    # (pass, frame) on the host); the frames' counters come from an untimed replay of the same frames below.
+    # (pass, frame) on the host); the frames' counters come from an untimed replay of the same frames below.  A plain run records
+    # the same events and only --full reads them: the timed region is the same launches, event records included, in both.
     if not args.no_kernel_events:
         for conv in model.roi_heads.mask_convs:
             conv.event_log = ev
@@ -714,6 +724,52 @@ def main():
     ev = ev[ev_mark[0]:] if ev_mark else ev
     for conv in model.roi_heads.mask_convs:
         conv.event_log = None
+
+    lazy = bool(model.lazy_proposal_masks)
+    dedup = bool(model.dedup_detection_masks)
+    total_frames = args.steps * world
+
+    def headline_line(mask_counts, frame_counts):
+        """The result line of a plain run; --full passes the per-frame means of its replay's counters and adds its own keys."""
+        return {
+            "metric": "frames/sec (640x640, implicit_memory); frames/sec/GPU = value / n_gpus",
+            "value": round(total_frames / elapsed, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32" if headline_math == "fp32" else "f32 emulated as 3 x bf16 on the bf16 MFMA pipe, fp32 accumulate", "data": "synthetic",
+            "config": {"workload": f"recurrent per-frame inference, MEMORY_TYPE implicit_memory, MAP_FEAT_FUSION sum, "
+                                   f"{H}x{W} synthetic sequence, memory grid {map_w}x{map_h} @ {args.cell} m, one scene per GPU "
+                                   f"(BASELINE.json configs[2]/[3]); proposal masks "
+                                   + ("computed only for the <=100 proposals the memory update reads (outputs bitwise identical to the "
+                                      "reference's 256-proposal pass, reported by --full as variants.all_256_proposal_masks)" if lazy else
+                                      "computed for all 256 proposals as the reference does")
+                                   + ("; detection masks computed once per distinct class-agnostic box (detections of one proposal share "
+                                      "it; bitwise identical to one ROI per detection, reported by --full as variants.one_mask_roi_per_detection)"
+                                      if dedup else "; one mask-head ROI per detection"),
+                       **mask_counts,
+                       "image": f"{H}x{W}", "memory_cells": map_w * map_h, "weights": "random-init (synthetic_state_dict seed 0)",
+                       "memory_cls_score_thresh": args.memory_thresh,
+                       "schedule": ("five HIP streams per scene inside model([episode]): main chain (memory read + fusion, tower, proposal "
+                                    "decoding, proposal masks), side (box cascade, detection and memory selection, memory write), "
+                                    "look-ahead (the next frame's memory-independent ResNet trunk), detection (detection mask pass + "
+                                    "post-process + paste, may trail under the next frame), caller; Instances are sliced out two frames "
+                                    "behind the enqueue; every step does one frame's full work, results bitwise equal to one stream"
+                                    if model.overlap_branches else "one HIP stream"),
+                       **frame_counts},
+            "boundary": "model([episode of <=20 frame dicts]) -> [{'instances': Instances(pred_boxes, scores, pred_classes i64, "
+                        "pred_masks bool [D,H,W])}] per frame (train_mp3d.py:186, custom_rcnn.py:537-546); inputs resident in HBM",
+            "full": args.full,
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line({}, {})), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below is beside the headline --------------------------------------------------------------------------
     # replay (untimed): the same frames from the same reset state give the same counters (every kernel is deterministic)
     run_boundary(frames, 0, args.warmup)
     model.stats_log = []
@@ -1013,38 +1069,12 @@ def main():
         mk = [int(c[2].item()) for c in counts]
         uq = [int(c[3].item()) for c in counts]
         dm = [int(c[4].item()) for c in counts]
-        lazy = bool(model.lazy_proposal_masks)
-        dedup = bool(model.dedup_detection_masks)
-        total_frames = args.steps * world
-        result = {
-            "metric": "frames/sec (640x640, implicit_memory); frames/sec/GPU = value / n_gpus",
-            "value": round(total_frames / elapsed, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32" if headline_math == "fp32" else "f32 emulated as 3 x bf16 on the bf16 MFMA pipe, fp32 accumulate", "data": "synthetic",
-            "config": {"workload": f"recurrent per-frame inference, MEMORY_TYPE implicit_memory, MAP_FEAT_FUSION sum, "
-                                   f"{H}x{W} synthetic sequence, memory grid {map_w}x{map_h} @ {args.cell} m, one scene per GPU "
-                                   f"(BASELINE.json configs[2]/[3]); proposal masks "
-                                   + ("computed only for the <=100 proposals the memory update reads (outputs bitwise identical to the "
-                                      "reference's 256-proposal pass, reported as variants.all_256_proposal_masks)" if lazy else
-                                      "computed for all 256 proposals as the reference does")
-                                   + ("; detection masks computed once per distinct class-agnostic box (detections of one proposal share "
-                                      "it; bitwise identical to one ROI per detection, reported as variants.one_mask_roi_per_detection)"
-                                      if dedup else "; one mask-head ROI per detection"),
-                       "detection_mask_rois_per_frame_mean": round(float(np.mean(dm)), 1),
-                       "proposal_masks_per_frame_mean": round(float(np.mean(uq)), 1) if lazy else round(float(np.mean(pc)), 1),
-                       "image": f"{H}x{W}", "memory_cells": map_w * map_h, "weights": "random-init (synthetic_state_dict seed 0)",
-                       "memory_cls_score_thresh": args.memory_thresh,
-                       "schedule": ("five HIP streams per scene inside model([episode]): main chain (memory read + fusion, tower, proposal "
-                                    "decoding, proposal masks), side (box cascade, detection and memory selection, memory write), "
-                                    "look-ahead (the next frame's memory-independent ResNet trunk), detection (detection mask pass + "
-                                    "post-process + paste, may trail under the next frame), caller; Instances are sliced out two frames "
-                                    "behind the enqueue; every step does one frame's full work, results bitwise equal to one stream"
-                                    if model.overlap_branches else "one HIP stream"),
-                       "proposals_per_frame_mean": round(float(np.mean(pc)), 1), "detections_per_frame_mean": round(float(np.mean(dc)), 1),
-                       "memory_instances_per_frame_mean": round(float(np.mean(mk)), 1)},
-            "boundary": "model([episode of <=20 frame dicts]) -> [{'instances': Instances(pred_boxes, scores, pred_classes i64, "
-                        "pred_masks bool [D,H,W])}] per frame (train_mp3d.py:186, custom_rcnn.py:537-546); inputs resident in HBM",
+        result = headline_line(
+            {"detection_mask_rois_per_frame_mean": round(float(np.mean(dm)), 1),
+             "proposal_masks_per_frame_mean": round(float(np.mean(uq)), 1) if lazy else round(float(np.mean(pc)), 1)},
+            {"proposals_per_frame_mean": round(float(np.mean(pc)), 1), "detections_per_frame_mean": round(float(np.mean(dc)), 1),
+             "memory_instances_per_frame_mean": round(float(np.mean(mk)), 1)})
+        result.update({
             "boundary_host_inputs": boundary_host,
             "roofline": roofline,
             "roofline_hbm": roofline_hbm,
@@ -1053,7 +1083,7 @@ def main():
             "variants": variants,
             "eval_allreduce_ms": round(t_ar * 1e3, 3),
             "ap50_synthetic": None if ap is None else round(ap["AP50"], 3),
-        }
+        })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:   # reported at N=1 only (bench contract)
         result["cpu_baseline"] = cpu_baseline(sd, host_frames[:args.cpu_warmup + args.cpu_frames], args, args.cpu_budget_s)
     if rank == 0:

@@ -450,6 +450,30 @@ def test_record_buffer_overflow_raises():
     assert rows_needed([6, 6, 6]) >= 6 * 256 > rows_needed(18) - 256 * 2
 
 
+def test_bench_full_is_an_option_and_off_by_default():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` is the headline only; `--full` switches everything else on, and the
+    `--no-*` switches that trim a `--full` run are still accepted beside it and without it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("eod_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    def parse(*argv):
+        keep, sys.argv = sys.argv, ["bench.py", *argv]
+        try:
+            return bench.parse()
+        finally:
+            sys.argv = keep
+
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and (a.gpus, a.steps, a.warmup, a.dump_outputs) == (1, 7, 2, None)
+    assert parse("--full").full is True
+    a = parse("--full", "--no-variants", "--no-cpu-baseline", "--no-config5", "--no-train-step", "--no-kernel-events")
+    assert a.full is True and a.variants is False and a.no_cpu_baseline and a.no_config5 and a.no_train_step and a.no_kernel_events
+    a = parse("--no-variants", "--no-cpu-baseline")
+    assert a.full is False and a.variants is False and a.no_cpu_baseline
+
+
 def test_bench_refuses_more_gpus_than_devices():
     """`python bench.py --gpus 8` without a launcher must start 8 workers or exit non-zero -- never run one rank and print n_gpus 1."""
     import subprocess

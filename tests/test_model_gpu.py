@@ -712,3 +712,44 @@ def test_bench_dump_outputs_is_the_last_timed_step_and_repeats(tmp_path):
     assert np.array_equal(a["pred_boxes"], inst.pred_boxes.tensor.cpu().numpy()) and np.array_equal(a["scores"], inst.scores.cpu().numpy())
     assert np.array_equal(a["pred_classes"], inst.pred_classes.cpu().numpy().astype(np.float32))
     assert np.array_equal(a["pred_masks_area"], inst.pred_masks.sum(dim=(1, 2)).cpu().numpy().astype(np.float64))
+
+
+def test_bench_plain_run_is_the_headline_and_full_adds_the_rest(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` prints the headline fields and none of the extra measurements; `--full` prints the
+    same fields with everything else beside them, and what the last timed step returns (`--dump-outputs`) is the same bits in both."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    extras = ("boundary_host_inputs", "roofline", "roofline_hbm", "frame_roofline", "variants", "eval_allreduce_ms", "ap50_synthetic",
+              "cpu_baseline")
+    counts = ("detection_mask_rois_per_frame_mean", "proposal_masks_per_frame_mean", "proposals_per_frame_mean",
+              "detections_per_frame_mean", "memory_instances_per_frame_mean")
+    lines, dumps = {}, {}
+    for name, more in (("plain", []), ("full", ["--full", "--cpu-frames", "1", "--cpu-warmup", "1"])):
+        d = os.path.join(str(tmp_path), name)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                            "--size", "128", "160", "--grid", "20", "20", "--cell", "0.5", "--dump-outputs", d] + more,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = r.stdout.strip().splitlines()
+        assert len(out) == 1, out                  # one JSON result line and nothing else on stdout
+        lines[name] = json.loads(out[0])
+        dumps[name] = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["n_gpus"] == 1
+        assert (line["steps"], line["warmup"]) == (4, 2) and line["metric"].startswith("frames/sec")
+        assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 1.0) < 5e-3    # value = frames / s of the timed steps
+        assert "workload" in line["config"] and "schedule" in line["config"]
+    assert all(plain[k] == full[k] for k in ("metric", "unit", "higher_is_better", "dtype", "scaling", "data", "boundary"))
+    assert plain["full"] is False and not any(k in plain for k in extras) and not any(k in plain["config"] for k in counts)
+    assert full["full"] is True and all(k in full for k in extras) and all(k in full["config"] for k in counts)
+    assert {k: v for k, v in full["config"].items() if k not in counts} == plain["config"]
+    v = full["variants"]
+    assert all(k in v and v[k]["value"] > 0 for k in ("enqueue_only", "all_256_proposal_masks", "one_mask_roi_per_detection",
+                                                      "reference_faithful_mask_work", "memory_cls_score_thresh_0", "bf16x3_split_mfma"))
+    assert full["boundary_host_inputs"]["value"] > 0 and full["roofline"]["bound"] == "mfma" and full["roofline"]["launches"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["timed_frames"] == 1 and full["frame_roofline"]["achieved_tflops"] > 0
+    assert sorted(dumps["plain"]) == sorted(dumps["full"]) and len(dumps["plain"]) == 5
+    assert all(np.array_equal(dumps["plain"][k], dumps["full"][k]) for k in dumps["plain"])

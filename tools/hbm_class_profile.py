@@ -34,7 +34,7 @@ def main():
                     "back_to_back_launches": len(b2b),
                     "back_to_back_median_us": round(float(np.median(b2b)), 2) if b2b else None,
                     "back_to_back_avg_us": round(float(np.mean(b2b)), 2) if b2b else None}
-    text = json.dumps({"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-variants",
+    text = json.dumps({"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-variants",
                        "note": "avg_us mixes the launches inside the frames (sharing the chip with the look-ahead trunk and the "
                                "previous frame's detection pass) with the probe's back-to-back launches; the probe figures are the "
                                "ones `roofline_hbm` is computed from",

@@ -42,7 +42,7 @@ def main():
     det = shapes.get(3676 * 256)
     prop = shapes.get(1568 * 256)
     out = {"kernel": "conv_igemm_kernel<64,64,32> mask_fcn 3x3 (M = rois * 196, N = 256, K = 2304)",
-           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes of `bench.py --steps 6 --warmup 3 --no-variants "
+           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes of `bench.py --steps 6 --warmup 3 --full --no-variants "
                      "--no-cpu-baseline --no-kernel-events`; counters are KB; FETCH_SIZE x2 = the gfx950 correction for wide (16 B per "
                      "lane) coalesced reads of MI355X_MICROARCH.md's HBM section; the launches run in the default multi-stream schedule",
            "detection_pass_launch": det, "proposal_pass_launch": prop,
