@@ -18,9 +18,12 @@ class Recorder:
     pointers were given); ROIAlign payloads collect the host copies of the first box lists they met (the cascade's three stages)."""
     KEEP_BOXES = 3
 
-    def __init__(self):
+    def __init__(self, inference: bool = False):
+        """`inference`: also wrap the entry points only the inference frame calls (tests/_inference_cases.py lists them); without it
+        the recorder is the training module's, call for call."""
         self.calls: Dict[str, Dict[tuple, dict]] = {}
         self._undo = []
+        self.inference = inference
 
     def note(self, family: str, key: tuple, **payload) -> dict:
         fam = self.calls.setdefault(family, {})
@@ -107,6 +110,8 @@ class Recorder:
             self._patch(ops, name, make)
         self._patch(ops.MemoryProjectorBackward, "__call__", projector_backward)
         self._patch(ops.AdamW, "nonfinite", nonfinite)
+        if self.inference:
+            self._enter_inference(ops)
 
         # ctypes level: an attribute on the loaded library object shadows the exported function for everybody who goes through it
         lib = _lib.load()
@@ -133,6 +138,162 @@ class Recorder:
                            ("eod_maxpool3x3s2_backward", maxpool_backward)):
             self._patch(lib, name, make)
         return self
+
+    def _enter_inference(self, ops):
+        """The entry points of the inference frame that the training step does not call (or calls with other arguments).  Every key
+        is (shapes, capacities, flags, which optional pointers were given, batch); the paste keeps host copies of the first few real
+        box / row lists it was given (they are replayed)."""
+        rec = self
+
+        def given(*ts):
+            return tuple(t is not None for t in ts)
+
+        def host(t, n=None):
+            return None if t is None else (t.detach().cpu().clone() if n is None else t.detach().cpu()[:n].clone())
+
+        def preprocess_image(orig):
+            def f(img, mean, std, div=32, out=None):
+                rec.note("preprocess_image", (int(img.shape[1]), int(img.shape[2]), int(div), out is not None),
+                         mean=tuple(float(v) for v in mean), std=tuple(float(v) for v in std))
+                return orig(img, mean, std, div=div, out=out)
+            return f
+
+        def maxpool3x3s2(orig):
+            def f(x, N, H, W, Cc):
+                rec.note("maxpool3x3s2", (int(N), int(H), int(W), int(Cc)))
+                return orig(x, N, H, W, Cc)
+            return f
+
+        def proposals(orig):
+            def f(self, head_out):
+                d = self.desc
+                sizes = tuple(self.level_off[l + 1] - self.level_off[l] for l in range(d.levels))
+                rec.note("proposals", (sizes, tuple(int(d.level_w[l]) for l in range(d.levels)), int(d.pre_nms_topk), int(d.post_nms_topk),
+                                           int(d.cap), int(d.batch), int(d.head_stride)),
+                             strides=tuple(int(d.level_stride[l]) for l in range(d.levels)), scales=tuple(float(d.level_scale[l]) for l in range(d.levels)),
+                             score_thresh=float(d.score_thresh), nms_thresh=float(d.nms_thresh))
+                return orig(self, head_out)
+            return f
+
+        def zs_classify(orig):
+            def f(feat, zs, prob_acc, accumulate, featn_out, count, R_cap, C1, temp=50.0, zs_mem=None, prop_scores=None, mem_scores_out=None,
+                  final_inv_stages=0.0, batch=1, wide=False):
+                rec.note("zs_classify", (int(R_cap), int(C1), bool(accumulate), float(temp), float(final_inv_stages), int(batch), bool(wide))
+                         + given(featn_out, count, zs_mem, prop_scores, mem_scores_out))
+                return orig(feat, zs, prob_acc, accumulate, featn_out, count, R_cap, C1, temp, zs_mem=zs_mem, prop_scores=prop_scores,
+                            mem_scores_out=mem_scores_out, final_inv_stages=final_inv_stages, batch=batch, wide=wide)
+            return f
+
+        def cascade_stage_tail(orig):
+            def f(feat, zs, prob_acc, accumulate, featn_out, count, R_cap, C1, temp, hb, bb2, boxes_in, boxes_out, weights, clip, img_w, img_h,
+                  zs_mem=None, prop_scores=None, mem_scores_out=None, final_inv_stages=0.0, deltas_out=None, batch=1, wide=False):
+                rec.note("cascade_stage_tail", (int(R_cap), int(C1), bool(accumulate), float(temp), float(final_inv_stages), int(batch), bool(wide),
+                                                tuple(float(w) for w in weights), bool(clip), float(img_w), float(img_h))
+                         + given(featn_out, count, zs_mem, prop_scores, mem_scores_out, deltas_out))
+                return orig(feat, zs, prob_acc, accumulate, featn_out, count, R_cap, C1, temp, hb, bb2, boxes_in, boxes_out, weights, clip,
+                            img_w, img_h, zs_mem=zs_mem, prop_scores=prop_scores, mem_scores_out=mem_scores_out,
+                            final_inv_stages=final_inv_stages, deltas_out=deltas_out, batch=batch, wide=wide)
+            return f
+
+        def apply_deltas(orig):
+            def f(deltas, ld, boxes, out, count, R_cap, weights, clip, img_w, img_h, batch=1):
+                rec.note("apply_deltas", (int(ld), int(R_cap), tuple(float(w) for w in weights), bool(clip), float(img_w), float(img_h), int(batch),
+                                          count is not None))
+                return orig(deltas, ld, boxes, out, count, R_cap, weights, clip, img_w, img_h, batch=batch)
+            return f
+
+        def memory_scores(orig):
+            def f(featn, zs, prop_scores, scores_out, count, R_cap, C1):
+                rec.note("memory_scores", (int(R_cap), int(C1), count is not None))
+                return orig(featn, zs, prop_scores, scores_out, count, R_cap, C1)
+            return f
+
+        def selector(orig):
+            def f(self, boxes, scores, count, img_w, img_h, score_thresh, nms_thresh):
+                rec.note("detection_selector", (int(self.R_cap), int(self.C1), int(self.topk), int(self.batch), self.uniq_rows is not None,
+                                                self.rep_of is not None, float(img_w), float(img_h), float(score_thresh), float(nms_thresh),
+                                                count is not None))
+                return orig(self, boxes, scores, count, img_w, img_h, score_thresh, nms_thresh)
+            return f
+
+        def mask_predictor_sigmoid(orig):
+            def f(x, w, bias, rows, Cc, count, unit_rows, out=None, out_units=None):
+                rec.note("mask_predictor_sigmoid", (int(rows), int(Cc), int(unit_rows)) + given(count, out, out_units))
+                return orig(x, w, bias, rows, Cc, count, unit_rows, out=out, out_units=out_units)
+            return f
+
+        def detector_postprocess(orig):
+            def f(boxes, scores, classes, count, cap, sx, sy, out_w, out_h, ob, os_, oc, osrc, ocount, remap=None, batch=1):
+                rec.note("detector_postprocess", (int(cap), float(sx), float(sy), float(out_w), float(out_h), remap is not None, int(batch),
+                                                  count is not None))
+                return orig(boxes, scores, classes, count, cap, sx, sy, out_w, out_h, ob, os_, oc, osrc, ocount, remap=remap, batch=batch)
+            return f
+
+        def paste_masks(orig):
+            def f(prob, boxes, rows, count, K_cap, H, W, thr, out, batch=1, prob_units=0):
+                e = rec.note("paste_masks", (int(K_cap), int(H), int(W), float(thr), int(batch), int(prob_units)) + given(rows, count), lists=[])
+                if len(e["lists"]) < rec.KEEP_BOXES:
+                    n = batch * K_cap
+                    e["lists"].append(dict(boxes=host(boxes.reshape(-1, 4), n), rows=host(rows, n), count=host(count)))
+                return orig(prob, boxes, rows, count, K_cap, H, W, thr, out, batch=batch, prob_units=prob_units)
+            return f
+
+        def unproject_grid_index(orig):
+            def f(depth, T, intr, proj_shift, map_shift, cell, map_w, map_h, order=0, want_xyz=False):
+                rec.note("unproject_grid_index", (int(depth.shape[0]), int(depth.shape[1]), int(map_w), int(map_h), int(order), bool(want_xyz)),
+                         cell=float(cell), intr=tuple(float(v) for v in intr))
+                return orig(depth, T, intr, proj_shift, map_shift, cell, map_w, map_h, order, want_xyz)
+            return f
+
+        def memory_normalize_f16(orig):
+            def f(mem, obs, out=None):
+                rec.note("memory_normalize_f16", (int(mem.shape[0]), int(mem.shape[1]), out is not None))
+                return orig(mem, obs, out=out)
+            return f
+
+        def memory_normalize_dirty_f16(orig):
+            def f(mem, obs, dirty, out):
+                rec.note("memory_normalize_dirty_f16", (int(mem.shape[0]), int(mem.shape[1])))
+                return orig(mem, obs, dirty, out)
+            return f
+
+        def projector(orig):
+            def f(self, pooled_f16, feats, H, W, weight, mode, batch=1):
+                rec.note("memory_projector", (int(H), int(W), float(weight), str(mode), int(batch)))
+                return orig(self, pooled_f16, feats, H, W, weight, mode, batch=batch)
+            return f
+
+        def writer(orig):
+            def f(self, featn, prop_boxes, prop_masks, det_rows, det_count, proj, mem, obs, dirty=None, err=None, snapshot=None):
+                d = self.desc
+                rec.note("memory_writer", (int(d.H), int(d.W), int(d.n_cells), int(d.K_cap), int(d.R_cap), int(d.batch), float(d.mask_thresh))
+                         + given(dirty, err, snapshot))
+                return orig(self, featn, prop_boxes, prop_masks, det_rows, det_count, proj, mem, obs, dirty=dirty, err=err, snapshot=snapshot)
+            return f
+
+        def concat_lists(orig):
+            def f(lists, counts, cap_in, id_stride, batch, out, out_count):
+                rec.note("concat_lists", (int(cap_in), int(id_stride), int(batch)))
+                return orig(lists, counts, cap_in, id_stride, batch, out, out_count)
+            return f
+
+        def semmap_labels(orig):
+            def f(mem, obs, zs, thresh):
+                rec.note("semmap_labels", (int(mem.shape[0]), int(mem.shape[1]), int(zs.shape[1]), float(thresh)))
+                return orig(mem, obs, zs, thresh)
+            return f
+
+        for name, make in (("preprocess_image", preprocess_image), ("maxpool3x3s2", maxpool3x3s2), ("zs_classify", zs_classify),
+                           ("cascade_stage_tail", cascade_stage_tail), ("apply_deltas", apply_deltas), ("memory_scores", memory_scores),
+                           ("mask_predictor_sigmoid", mask_predictor_sigmoid), ("detector_postprocess", detector_postprocess),
+                           ("paste_masks", paste_masks), ("unproject_grid_index", unproject_grid_index),
+                           ("memory_normalize_f16", memory_normalize_f16), ("memory_normalize_dirty_f16", memory_normalize_dirty_f16),
+                           ("concat_lists", concat_lists), ("semmap_labels", semmap_labels)):
+            self._patch(ops, name, make)
+        self._patch(ops.ProposalDecoder, "__call__", proposals)
+        self._patch(ops.DetectionSelector, "__call__", selector)
+        self._patch(ops.MemoryProjector, "__call__", projector)
+        self._patch(ops.MemoryWriter, "__call__", writer)
 
     def __exit__(self, *exc):
         for owner, name, orig in reversed(self._undo):
