@@ -1,5 +1,5 @@
 // fp32 convolution emulated on the bf16 matrix cores (three-way operand split): opt-in arithmetic mode, DESIGN.md §3.
-#include "conv_common.h"
+#include "conv_operands.h"
 
 namespace eodconv {
 namespace {
@@ -60,117 +60,44 @@ __global__ __launch_bounds__(256) void conv_bf16x3_kernel(ConvArgs p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  int M = p.M;
-  M = conv_row_limit(p, M);
-  const int ntiles = ((M + BM - 1) / BM) * p.tiles_n;
-  if ((int)blockIdx.x >= ntiles) return;
-  const int t = xcd_remap(blockIdx.x, ntiles);
+  int M;
+  const int t = conv_first_tile<BM>(p, M);
+  if (t < 0) return;
   const int tile_m = t / p.tiles_n;
   const int tile_n = t - tile_m * p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   if (!conv_tile_active(p, m0, BM)) return;
   const int z = blockIdx.y;
-  const int c_begin = z * p.cps;
-  int c_end = c_begin + p.cps;
-  if (c_end > p.nchunks) c_end = p.nchunks;
+  int c_end;
+  const int c_begin = conv_chunk_range(p, p.cps, z, c_end);
 
   const int lr = tid >> 3, lq = tid & 7;
   unsigned a_voff[AR];
   unsigned long long a_mask[AR];
   unsigned a_pitch[MULTI ? AR : 1];
 #pragma unroll
-  for (int i = 0; i < AR; ++i) {
-    const int m = m0 + lr + 32 * i;
-    int iy0 = 0, ix0 = 0, off = 0, hh = 1, ww = 1;
-    const bool rowok = m < M;
-    if (rowok) {
-      if (MULTI) {
-        int l = 0;
-        while (l + 1 < p.nlv && m >= p.lv_off[l + 1]) ++l;
-        const int local = m - p.lv_off[l];
-        ww = p.lv_w[l];
-        hh = p.lv_h[l];
-        const int oy = local / ww;
-        iy0 = oy - p.pad;
-        ix0 = (local - oy * ww) - p.pad;
-        off = p.lv_off[l];
-      } else {
-        const int tq = (int)fdiv((unsigned)m, p.div_ow);
-        const int ox = m - tq * p.OW;
-        const int img = (int)fdiv((unsigned)tq, p.div_oh);
-        const int oy = tq - img * p.OH;
-        iy0 = oy * p.stride - p.pad;
-        ix0 = ox * p.stride - p.pad;
-        off = img * p.H * p.W;
-        hh = p.H;
-        ww = p.W;
-      }
-    }
-    unsigned long long mask = 0;
-    if (rowok) {
-      mask = tap_mask(iy0, ix0, hh, ww, p.KH, p.KW);
-    }
-    a_mask[i] = mask;
-    a_voff[i] = (unsigned)(((off + iy0 * ww + ix0) * p.Cin + 4 * lq) * 4);
-    if (MULTI) a_pitch[i] = (unsigned)(ww * p.Cin * 4);
-  }
+  for (int i = 0; i < AR; ++i) conv_row_address<MULTI>(p, m0 + lr + 32 * i, M, lq, a_voff[i], a_mask[i], a_pitch[MULTI ? i : 0]);
   unsigned w_voff[BR];
 #pragma unroll
-  for (int j = 0; j < BR; ++j) {
-    const int n = n0 + lr + 32 * j;
-    w_voff[j] = n < p.Cout ? (unsigned)((n * p.Kpad + 4 * lq) * 4) : 0xFFFFFFFFu;
-  }
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
+  for (int j = 0; j < BR; ++j) w_voff[j] = conv_w_row_offset(p, n0 + lr + 32 * j, lq);
+  const __amdgpu_buffer_rsrc_t rsrc_x = conv_buffer(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_w = conv_buffer(p.w, p.w_bytes);
 
   // Software pipeline: while chunk c is multiplied, the raw fp32 registers of chunk c+1 (fetched one iteration earlier) are
   // split into bf16 pieces between the MFMAs and immediately refilled with the loads of chunk c+2; the pieces go to LDS at
   // the top of the next iteration.  One staging unit (= one float4 of this thread) is attached to every group of MFMAs.
   f32x4 raw[AR + BR];
   Split3 sp[AR + BR];
-  struct TapInfo { int tap, ky; unsigned tap_off, k0b; };
 #ifdef ABL_NOGLOBAL
   bool chunk_guard = false;
 #endif
-  // tap_info() is called for consecutive chunks (c_begin, c_begin + 1, ...): the (tap, channel) position is advanced instead of
-  // re-derived with two divisions per chunk.  The one or two calls past c_end describe chunks that are fetched (range-checked
-  // buffer loads) and never used.
-  int nx_tap, nx_c0, nx_ky, nx_kx, nx_k0 = c_begin * BK;
-  nx_tap = nx_k0 / p.Cin;
-  nx_c0 = nx_k0 - nx_tap * p.Cin;
-  nx_ky = nx_tap / p.KW;
-  nx_kx = nx_tap - nx_ky * p.KW;
-  auto tap_info = [&](int) {
-    TapInfo ti;
-    ti.tap = nx_tap < 63 ? nx_tap : 63;
-    ti.ky = nx_ky;
-    ti.tap_off = MULTI ? (unsigned)((nx_kx * p.Cin + nx_c0) * 4) : (unsigned)(((nx_ky * p.W + nx_kx) * p.Cin + nx_c0) * 4);
-    ti.k0b = (unsigned)(nx_k0 * 4);
-    nx_k0 += BK;
-    nx_c0 += BK;
-    if (nx_c0 >= p.Cin) {
-      nx_c0 = 0;
-      ++nx_tap;
-      if (++nx_kx == p.KW) {
-        nx_kx = 0;
-        ++nx_ky;
-      }
-    }
-    return ti;
-  };
+  ChunkWalker<BK, MULTI> walk(p, c_begin);
   auto load_unit = [&](const TapInfo& ti, int u) {
 #ifdef ABL_NOGLOBAL
     if (chunk_guard) return;
 #endif
-    if (u < AR) {
-      const bool ok = (a_mask[u] >> ti.tap) & 1ull;
-      unsigned vo = a_voff[u] + ti.tap_off;
-      if (MULTI) vo += (unsigned)ti.ky * a_pitch[u];
-      vo = ok ? vo : 0xFFFFFFFFu;
-      raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, 0, 0));
-    } else {
-      raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[u - AR], ti.k0b, 0));
-    }
+    if (u < AR) raw[u] = conv_load_a<MULTI>(rsrc_x, ti, a_voff[u], a_mask[u], a_pitch[MULTI ? u : 0]);
+    else raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[u - AR], ti.k0b, 0));
   };
 
   f32x16 acc[TM][TN];
@@ -191,12 +118,12 @@ __global__ __launch_bounds__(256) void conv_bf16x3_kernel(ConvArgs p) {
   constexpr int GROUPS = 2 * TM * TN;
   constexpr int UPG = (UNITS + GROUPS - 1) / GROUPS;
   {
-    const TapInfo t0 = tap_info(c_begin);
+    const TapInfo t0 = walk.next(p);
 #pragma unroll
     for (int u = 0; u < UNITS; ++u) load_unit(t0, u);
 #pragma unroll
     for (int u = 0; u < UNITS; ++u) sp[u] = split3(raw[u]);
-    const TapInfo t1 = tap_info(c_begin + 1);
+    const TapInfo t1 = walk.next(p);
 #pragma unroll
     for (int u = 0; u < UNITS; ++u) load_unit(t1, u);
   }
@@ -215,7 +142,7 @@ __global__ __launch_bounds__(256) void conv_bf16x3_kernel(ConvArgs p) {
       *reinterpret_cast<uint2*>(dst + 128) = sp[u].l;
     }
     __syncthreads();
-    const TapInfo tn = tap_info(chunk + 2);
+    const TapInfo tn = walk.next(p);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       bf16x8_t af[TM][3], bfr[TN][3];
@@ -293,66 +220,26 @@ __global__ __launch_bounds__(512) void conv_bf16x3_w8_kernel(ConvArgs p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  int M = p.M;
-  M = conv_row_limit(p, M);
-  const int ntiles = ((M + BM - 1) / BM) * p.tiles_n;
-  if ((int)blockIdx.x >= ntiles) return;
-  const int t = xcd_remap(blockIdx.x, ntiles);
+  int M;
+  const int t = conv_first_tile<BM>(p, M);
+  if (t < 0) return;
   const int tile_m = t / p.tiles_n;
   const int tile_n = t - tile_m * p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   if (!conv_tile_active(p, m0, BM)) return;
   const int z = blockIdx.y;
-  const int c_begin = z * p.cps;
-  int c_end = c_begin + p.cps;
-  if (c_end > p.nchunks) c_end = p.nchunks;
+  int c_end;
+  const int c_begin = conv_chunk_range(p, p.cps, z, c_end);
 
   const int lr = tid >> 3, lq = tid & 7;      // 64 rows per pass, 8 float4 per row
   unsigned a_voff[AR];
   unsigned long long a_mask[AR];
   unsigned a_pitch[MULTI ? AR : 1];
 #pragma unroll
-  for (int i = 0; i < AR; ++i) {
-    const int m = m0 + lr + 64 * i;
-    int iy0 = 0, ix0 = 0, off = 0, hh = 1, ww = 1;
-    const bool rowok = m < M;
-    if (rowok) {
-      if (MULTI) {
-        int l = 0;
-        while (l + 1 < p.nlv && m >= p.lv_off[l + 1]) ++l;
-        const int local = m - p.lv_off[l];
-        ww = p.lv_w[l];
-        hh = p.lv_h[l];
-        const int oy = local / ww;
-        iy0 = oy - p.pad;
-        ix0 = (local - oy * ww) - p.pad;
-        off = p.lv_off[l];
-      } else {
-        const int tq = (int)fdiv((unsigned)m, p.div_ow);
-        const int ox = m - tq * p.OW;
-        const int img = (int)fdiv((unsigned)tq, p.div_oh);
-        const int oy = tq - img * p.OH;
-        iy0 = oy * p.stride - p.pad;
-        ix0 = ox * p.stride - p.pad;
-        off = img * p.H * p.W;
-        hh = p.H;
-        ww = p.W;
-      }
-    }
-    unsigned long long mask = 0;
-    if (rowok) {
-      mask = tap_mask(iy0, ix0, hh, ww, p.KH, p.KW);
-    }
-    a_mask[i] = mask;
-    a_voff[i] = (unsigned)(((off + iy0 * ww + ix0) * p.Cin + 4 * lq) * 4);
-    if (MULTI) a_pitch[i] = (unsigned)(ww * p.Cin * 4);
-  }
+  for (int i = 0; i < AR; ++i) conv_row_address<MULTI>(p, m0 + lr + 64 * i, M, lq, a_voff[i], a_mask[i], a_pitch[MULTI ? i : 0]);
   unsigned w_voff[BR > 0 ? BR : 1];
 #pragma unroll
-  for (int j = 0; j < BR; ++j) {
-    const int n = n0 + lr + 64 * j;
-    w_voff[j] = n < p.Cout ? (unsigned)((n * p.Kpad + 4 * lq) * 4) : 0xFFFFFFFFu;
-  }
+  for (int j = 0; j < BR; ++j) w_voff[j] = conv_w_row_offset(p, n0 + lr + 64 * j, lq);
   // WS: piece q = tid + 512 u of the [128 rows][12 pieces] weight tile
   unsigned w3_voff[BP];
   int w3_lds[BP];
@@ -364,7 +251,7 @@ __global__ __launch_bounds__(512) void conv_bf16x3_w8_kernel(ConvArgs p) {
     w3_voff[u] = n < p.Cout ? (unsigned)(n * (p.Kpad / 32) * 192 + pc * 16) : 0xFFFFFFFFu;
     w3_lds[u] = (BM + row) * ROWB + pc * 16;
   }
-  const __amdgpu_buffer_rsrc_t rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w3), 0, WS ? p.w3_bytes : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w3 = conv_buffer(p.w3, WS ? p.w3_bytes : 0u);
   u32x4_t braw[BP];
   auto load_w3 = [&](int chunk) {
     if (chunk > c_end - 1) chunk = c_end - 1;
@@ -375,52 +262,19 @@ __global__ __launch_bounds__(512) void conv_bf16x3_w8_kernel(ConvArgs p) {
 #pragma unroll
     for (int u = 0; u < BP; ++u) *reinterpret_cast<u32x4_t*>(stage + w3_lds[u]) = braw[u];
   };
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = conv_buffer(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_w = conv_buffer(p.w, p.w_bytes);
 
   f32x4 raw[UNITS];
   bool in_loop = false;     // diagnostic builds (tools/ablate/run_bf16x3.py) drop parts of the loop body
   (void)in_loop;
-  struct TapInfo { int tap, ky; unsigned tap_off, k0b; };
-  // tap_info() is called for consecutive chunks (c_begin, c_begin + 1, ...): the (tap, channel) position is advanced instead of
-  // re-derived with two divisions per chunk.  The one or two calls past c_end describe chunks that are fetched (range-checked
-  // buffer loads) and never used.
-  int nx_tap, nx_c0, nx_ky, nx_kx, nx_k0 = c_begin * BK;
-  nx_tap = nx_k0 / p.Cin;
-  nx_c0 = nx_k0 - nx_tap * p.Cin;
-  nx_ky = nx_tap / p.KW;
-  nx_kx = nx_tap - nx_ky * p.KW;
-  auto tap_info = [&](int) {
-    TapInfo ti;
-    ti.tap = nx_tap < 63 ? nx_tap : 63;
-    ti.ky = nx_ky;
-    ti.tap_off = MULTI ? (unsigned)((nx_kx * p.Cin + nx_c0) * 4) : (unsigned)(((nx_ky * p.W + nx_kx) * p.Cin + nx_c0) * 4);
-    ti.k0b = (unsigned)(nx_k0 * 4);
-    nx_k0 += BK;
-    nx_c0 += BK;
-    if (nx_c0 >= p.Cin) {
-      nx_c0 = 0;
-      ++nx_tap;
-      if (++nx_kx == p.KW) {
-        nx_kx = 0;
-        ++nx_ky;
-      }
-    }
-    return ti;
-  };
+  ChunkWalker<BK, MULTI> walk(p, c_begin);
   auto load_unit = [&](const TapInfo& ti, int u) {
 #ifdef ABL_NOGLOBAL
     if (in_loop) return;
 #endif
-    if (u < AR) {
-      const bool ok = (a_mask[u] >> ti.tap) & 1ull;
-      unsigned vo = a_voff[u] + ti.tap_off;
-      if (MULTI) vo += (unsigned)ti.ky * a_pitch[u];
-      vo = ok ? vo : 0xFFFFFFFFu;
-      raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, 0, 0));
-    } else {
-      raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[u - AR], ti.k0b, 0));
-    }
+    if (u < AR) raw[u] = conv_load_a<MULTI>(rsrc_x, ti, a_voff[u], a_mask[u], a_pitch[MULTI ? u : 0]);
+    else raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[u - AR], ti.k0b, 0));
   };
   // staging unit u of this thread lands at st_off[u] inside a stage
   auto st_off = [&](int u) { return u < AR ? (lr + 64 * u) * ROWB + lq * 8 : (BM + lr + 64 * (u - AR)) * ROWB + lq * 8; };
@@ -459,12 +313,12 @@ __global__ __launch_bounds__(512) void conv_bf16x3_w8_kernel(ConvArgs p) {
   const int b_fo = (BM + wn * 64 + frow) * ROWB + fh * 16;
 
   {
-    const TapInfo t0 = tap_info(c_begin);
+    const TapInfo t0 = walk.next(p);
 #pragma unroll
     for (int u = 0; u < UNITS; ++u) load_unit(t0, u);
 #pragma unroll
     for (int u = 0; u < UNITS; ++u) stage_unit(lds, u);
-    const TapInfo t1 = tap_info(c_begin + 1);
+    const TapInfo t1 = walk.next(p);
 #pragma unroll
     for (int u = 0; u < UNITS; ++u) load_unit(t1, u);
     if (WS) {
@@ -479,7 +333,7 @@ __global__ __launch_bounds__(512) void conv_bf16x3_w8_kernel(ConvArgs p) {
     char* cur = lds + st * STAGE;
     char* nxt = lds + (st ^ 1) * STAGE;
     __syncthreads();      // stage `cur` fully written (previous iteration), stage `nxt` no longer read
-    const TapInfo tn = tap_info(chunk + 2);
+    const TapInfo tn = walk.next(p);
     bf16x8_t af[2][2][3], bfr[2][2][3];    // [K=16 step][tile][piece]
 #pragma unroll
     for (int i = 0; i < 2; ++i)

@@ -1,6 +1,7 @@
-// Shared by the convolution translation units: launch arguments, the fused epilogue and the launch entry points of the
-// kernel families (fp32 MFMA: conv_fp32.hip, bf16x3 split: conv_bf16x3.hip, f16 operands: conv_f16.hip).  Planning,
-// argument checks and the C ABI live in conv_igemm.hip.
+// Shared by the convolution translation units: launch arguments, the row-count rules, the fused epilogue and the launch entry
+// points of the kernel families (fp32 MFMA: conv_fp32.hip, bf16x3 split: conv_bf16x3.hip, f16 operands: conv_f16.hip).  What the
+// forward kernels do before their first MFMA -- tile claim, operand addressing, K-chunk walk, masked activation load -- is in
+// conv_operands.h, which includes this file.  Planning, argument checks and the C ABI live in conv_igemm.hip.
 #pragma once
 #include "eod_common.h"
 #include "../../include/eod_hip.h"

@@ -1,5 +1,5 @@
 // Convolution with operands rounded to binary16 on the f16 matrix cores, fp32 accumulate: opt-in arithmetic mode, DESIGN.md §3.
-#include "conv_common.h"
+#include "conv_operands.h"
 
 namespace eodconv {
 namespace {
@@ -55,66 +55,26 @@ __global__ __launch_bounds__(NT) void conv_f16_kernel(ConvArgs p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  int M = p.M;
-  M = conv_row_limit(p, M);
-  const int ntiles = ((M + BM - 1) / BM) * p.tiles_n;
-  if ((int)blockIdx.x >= ntiles) return;
-  const int t = xcd_remap(blockIdx.x, ntiles);
+  int M;
+  const int t = conv_first_tile<BM>(p, M);
+  if (t < 0) return;
   const int tile_m = t / p.tiles_n;
   const int tile_n = t - tile_m * p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   if (!conv_tile_active(p, m0, BM)) return;
   const int z = blockIdx.y;
-  const int c_begin = z * p.cps;
-  int c_end = c_begin + p.cps;
-  if (c_end > p.nchunks) c_end = p.nchunks;
+  int c_end;
+  const int c_begin = conv_chunk_range(p, p.cps, z, c_end);
 
   const int lr = tid / TPR, lq = tid % TPR;
   unsigned a_voff[AR];
   unsigned long long a_mask[AR];
   unsigned a_pitch[MULTI ? AR : 1];
 #pragma unroll
-  for (int i = 0; i < AR; ++i) {
-    const int m = m0 + lr + RPP * i;
-    int iy0 = 0, ix0 = 0, off = 0, hh = 1, ww = 1;
-    const bool rowok = m < M;
-    if (rowok) {
-      if (MULTI) {
-        int l = 0;
-        while (l + 1 < p.nlv && m >= p.lv_off[l + 1]) ++l;
-        const int local = m - p.lv_off[l];
-        ww = p.lv_w[l];
-        hh = p.lv_h[l];
-        const int oy = local / ww;
-        iy0 = oy - p.pad;
-        ix0 = (local - oy * ww) - p.pad;
-        off = p.lv_off[l];
-      } else {
-        const int tq = (int)fdiv((unsigned)m, p.div_ow);
-        const int ox = m - tq * p.OW;
-        const int img = (int)fdiv((unsigned)tq, p.div_oh);
-        const int oy = tq - img * p.OH;
-        iy0 = oy * p.stride - p.pad;
-        ix0 = ox * p.stride - p.pad;
-        off = img * p.H * p.W;
-        hh = p.H;
-        ww = p.W;
-      }
-    }
-    unsigned long long mask = 0;
-    if (rowok) {
-      mask = tap_mask(iy0, ix0, hh, ww, p.KH, p.KW);
-    }
-    a_mask[i] = mask;
-    a_voff[i] = (unsigned)(((off + iy0 * ww + ix0) * p.Cin + 4 * lq) * 4);
-    if (MULTI) a_pitch[i] = (unsigned)(ww * p.Cin * 4);
-  }
+  for (int i = 0; i < AR; ++i) conv_row_address<MULTI>(p, m0 + lr + RPP * i, M, lq, a_voff[i], a_mask[i], a_pitch[MULTI ? i : 0]);
   unsigned w_voff[BR > 0 ? BR : 1];
 #pragma unroll
-  for (int j = 0; j < BR; ++j) {
-    const int n = n0 + lr + RPP * j;
-    w_voff[j] = n < p.Cout ? (unsigned)((n * p.Kpad + 4 * lq) * 4) : 0xFFFFFFFFu;
-  }
+  for (int j = 0; j < BR; ++j) w_voff[j] = conv_w_row_offset(p, n0 + lr + RPP * j, lq);
   // WH: piece q = tid + NT u of the [BN rows][PPR pieces] weight tile
   unsigned wh_voff[BP > 0 ? BP : 1];
   int wh_lds[BP > 0 ? BP : 1];
@@ -126,51 +86,18 @@ __global__ __launch_bounds__(NT) void conv_f16_kernel(ConvArgs p) {
     wh_voff[u] = n < p.Cout ? (unsigned)(n * p.Kpad * 2 + pc * 16) : 0xFFFFFFFFu;
     wh_lds[u] = (BM + row) * ROWB + pc * 16;
   }
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_wh = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wh), 0, WH ? p.wh_bytes : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = conv_buffer(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_w = conv_buffer(p.w, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_wh = conv_buffer(p.wh, WH ? p.wh_bytes : 0u);
 
   f32x4 raw[UNITS];
   u32x4_t braw[BP > 0 ? BP : 1];
-  struct TapInfo { int tap, ky; unsigned tap_off, k0b; };
-  // tap_info() is called for consecutive chunks (c_begin, c_begin + 1, ...): the (tap, channel) position is advanced instead of
-  // re-derived with two divisions per chunk.  The one or two calls past c_end describe chunks that are fetched (range-checked
-  // buffer loads) and never used.
-  int nx_tap, nx_c0, nx_ky, nx_kx, nx_k0 = c_begin * BK;
-  nx_tap = nx_k0 / p.Cin;
-  nx_c0 = nx_k0 - nx_tap * p.Cin;
-  nx_ky = nx_tap / p.KW;
-  nx_kx = nx_tap - nx_ky * p.KW;
-  auto tap_info = [&]() {
-    TapInfo ti;
-    ti.tap = nx_tap < 63 ? nx_tap : 63;
-    ti.ky = nx_ky;
-    ti.tap_off = MULTI ? (unsigned)((nx_kx * p.Cin + nx_c0) * 4) : (unsigned)(((nx_ky * p.W + nx_kx) * p.Cin + nx_c0) * 4);
-    ti.k0b = (unsigned)(nx_k0 * 4);
-    nx_k0 += BK;
-    nx_c0 += BK;
-    if (nx_c0 >= p.Cin) {
-      nx_c0 = 0;
-      ++nx_tap;
-      if (++nx_kx == p.KW) {
-        nx_kx = 0;
-        ++nx_ky;
-      }
-    }
-    return ti;
-  };
+  ChunkWalker<BK, MULTI> walk(p, c_begin);
   auto load_chunk = [&](const TapInfo& ti) {
 #pragma unroll
     for (int u = 0; u < UNITS; ++u) {
-      if (u < AR) {
-        const bool ok = (a_mask[u] >> ti.tap) & 1ull;
-        unsigned vo = a_voff[u] + ti.tap_off;
-        if (MULTI) vo += (unsigned)ti.ky * a_pitch[u];
-        vo = ok ? vo : 0xFFFFFFFFu;
-        raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, 0, 0));
-      } else {
-        raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[u - AR], ti.k0b, 0));
-      }
+      if (u < AR) raw[u] = conv_load_a<MULTI>(rsrc_x, ti, a_voff[u], a_mask[u], a_pitch[MULTI ? u : 0]);
+      else raw[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[u - AR], ti.k0b, 0));
     }
 #pragma unroll
     for (int u = 0; u < BP; ++u) braw[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_wh, wh_voff[u], ti.k0b >> 1, 0);
@@ -198,16 +125,16 @@ __global__ __launch_bounds__(NT) void conv_f16_kernel(ConvArgs p) {
   const int a_fo = (wm * TM * 32 + frow) * ROWB + fh * 16;
   const int b_fo = (BM + wn * TN * 32 + frow) * ROWB + fh * 16;
 
-  load_chunk(tap_info());
+  load_chunk(walk.next(p));
   stage_chunk(lds);
-  load_chunk(tap_info());
+  load_chunk(walk.next(p));
   for (int chunk = c_begin; chunk < c_end; ++chunk) {
     const int st = (chunk - c_begin) & 1;
     const char* cur = lds + st * STAGE;
     char* nxt = lds + (st ^ 1) * STAGE;
     __syncthreads();      // stage `cur` fully written (previous iteration), stage `nxt` no longer read
     stage_chunk(nxt);     // chunk + 1, fetched one iteration ago
-    load_chunk(tap_info());   // chunk + 2
+    load_chunk(walk.next(p));   // chunk + 2
 #pragma unroll
     for (int s = 0; s < BK / 16; ++s) {
       f16x8_t af[TM], bfr[TN];

@@ -18,14 +18,7 @@
 // remap so that the workgroups sharing an L2 walk neighbouring tiles (same weight panel / same pixel rows).
 // Small problems are split along K (grid.y) into fp32 slabs reduced by a second kernel that also applies the
 // epilogue: deterministic, no atomics.
-#include "conv_common.h"
-
-#ifndef EOD_MFMA_PRIO
-#define EOD_MFMA_PRIO 1
-#endif
-#ifndef EOD_LDS_PIPE
-#define EOD_LDS_PIPE 1
-#endif
+#include "conv_operands.h"
 
 namespace eodconv {
 namespace {
@@ -55,118 +48,48 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  int M = p.M;
-  M = conv_row_limit(p, M);
-  // Only the tiles that hold valid rows do work; the XCD remap is taken over THAT count so that a short dynamic
-  // row count (e.g. 256 of 320 ROI slots) still spreads evenly over the 8 XCDs instead of idling the last ones.
-  const int ntiles = ((M + BM - 1) / BM) * p.tiles_n;
-  if ((int)blockIdx.x >= ntiles) return;
-  const int t = xcd_remap(blockIdx.x, ntiles);
+  int M;
+  const int t = conv_first_tile<BM>(p, M);
+  if (t < 0) return;
   const int tile_m = t / p.tiles_n;
   const int tile_n = t - tile_m * p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   if (!conv_tile_active(p, m0, BM)) return;
-
   const int z = blockIdx.y;
-  const int c_begin = z * p.cps;
-  int c_end = c_begin + p.cps;
-  if (c_end > p.nchunks) c_end = p.nchunks;
+  int c_end;
+  const int c_begin = conv_chunk_range(p, p.cps, z, c_end);
 
   const int lr = tid / QPR, lq = tid % QPR;
-  // Operand addressing.  Both tiles are fetched with SRSRC buffer loads (32-bit byte offsets + hardware range check):
-  //  * every tile row gets ONE byte offset (its (ky,kx)=(0,0) tap position) and a bit mask of the taps that fall inside
-  //    the image, both computed once per workgroup; per chunk a load costs an add, a bit test and a select -- no
-  //    64-bit address arithmetic, no exec-mask branches; a masked-off / out-of-tile lane gets offset 0xFFFFFFFF, which
-  //    the range check turns into zeros (the conv's zero padding);
-  //  * a weight row's offset never changes: the K position goes into the scalar offset of the instruction.
-  int a_off[AR], a_iy[AR], a_ix[AR];        // TAP4 (stem) path only
+  // operand addressing: conv_operands.h.  The stem (TAP4) keeps the row origins and tests its taps per load instead.
+  int a_off[AR], a_iy[AR], a_ix[AR];
   unsigned a_voff[AR];
   unsigned long long a_mask[AR];
   unsigned a_pitch[MULTI ? AR : 1];
 #pragma unroll
   for (int i = 0; i < AR; ++i) {
     const int m = m0 + lr + RPP * i;
-    int iy0 = 0, ix0 = 0, off = 0, hh = 1, ww = 1;
     const bool rowok = m < M;
-    if (rowok) {
-      if (MULTI) {
-        int l = 0;
-        while (l + 1 < p.nlv && m >= p.lv_off[l + 1]) ++l;
-        const int local = m - p.lv_off[l];
-        ww = p.lv_w[l];
-        hh = p.lv_h[l];
-        const int oy = local / ww;
-        iy0 = oy - p.pad;
-        ix0 = (local - oy * ww) - p.pad;
-        off = p.lv_off[l];
-      } else {
-        const int t2 = (int)fdiv((unsigned)m, p.div_ow);      // invariant divisors: one mul_hi instead of a division sequence
-        const int ox = m - t2 * p.OW;
-        const int img = (int)fdiv((unsigned)t2, p.div_oh);
-        const int oy = t2 - img * p.OH;
-        iy0 = oy * p.stride - p.pad;
-        ix0 = ox * p.stride - p.pad;
-        off = img * p.H * p.W;
-        hh = p.H;
-        ww = p.W;
-      }
-    }
-    a_iy[i] = rowok ? iy0 : -(1 << 28);
-    a_ix[i] = ix0;
-    a_off[i] = off;
-    if (!TAP4) {
-      unsigned long long mask = 0;
-      if (rowok) {
-        mask = tap_mask(iy0, ix0, hh, ww, p.KH, p.KW);
-      }
-      a_mask[i] = mask;
-      a_voff[i] = (unsigned)(((off + iy0 * ww + ix0) * p.Cin + 4 * lq) * 4);   // may wrap for padded taps: only used when the tap bit is set
-      if (MULTI) a_pitch[i] = (unsigned)(ww * p.Cin * 4);
-    }
+    const RowOrigin o = conv_row_origin<MULTI>(p, m, rowok);
+    a_iy[i] = rowok ? o.iy0 : -(1 << 28);
+    a_ix[i] = o.ix0;
+    a_off[i] = o.off;
+    if (!TAP4) conv_row_address<MULTI>(p, o, rowok, lq, a_voff[i], a_mask[i], a_pitch[MULTI ? i : 0]);
   }
   unsigned w_voff[BR];
 #pragma unroll
-  for (int j = 0; j < BR; ++j) {
-    const int n = n0 + lr + RPP * j;
-    w_voff[j] = n < p.Cout ? (unsigned)((n * p.Kpad + 4 * lq) * 4) : 0xFFFFFFFFu;
-  }
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
+  for (int j = 0; j < BR; ++j) w_voff[j] = conv_w_row_offset(p, n0 + lr + RPP * j, lq);
+  const __amdgpu_buffer_rsrc_t rsrc_x = conv_buffer(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_w = conv_buffer(p.w, p.w_bytes);
 
   f32x4 ar0[AR], br0[BR];
   f32x4 ar1[PF2 ? AR : 1], br1[PF2 ? BR : 1];
-  // (tap, channel offset) of the NEXT chunk to fetch: chunks are fetched in order, so the position is advanced instead of
-  // re-derived with two divisions per chunk (Cin is a multiple of BK on this path)
-  int nx_tap = 0, nx_c0 = 0, nx_ky = 0, nx_kx = 0;
-  if (!TAP4) {
-    const int k0 = c_begin * BK;
-    nx_tap = k0 / p.Cin;
-    nx_c0 = k0 - nx_tap * p.Cin;
-    nx_ky = nx_tap / p.KW;
-    nx_kx = nx_tap - nx_ky * p.KW;
-  }
+  ChunkWalker<BK, MULTI> walk(p, c_begin);      // unused by the stem
   auto load_chunk = [&](int chunk, auto& ar, auto& br) {
     const int k0 = chunk * BK;
     if (!TAP4) {
-      const int tap = nx_tap, c0 = nx_c0, ky = nx_ky, kx = nx_kx;
-      nx_c0 += BK;
-      if (nx_c0 >= p.Cin) {
-        nx_c0 = 0;
-        ++nx_tap;
-        if (++nx_kx == p.KW) {
-          nx_kx = 0;
-          ++nx_ky;
-        }
-      }
-      const unsigned tap_off = MULTI ? (unsigned)((kx * p.Cin + c0) * 4) : (unsigned)(((ky * p.W + kx) * p.Cin + c0) * 4);
+      const TapInfo ti = walk.next(p);
 #pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const bool ok = (a_mask[i] >> tap) & 1ull;
-        unsigned vo = a_voff[i] + tap_off;
-        if (MULTI) vo += (unsigned)ky * a_pitch[i];
-        vo = ok ? vo : 0xFFFFFFFFu;
-        ar[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, 0, 0));
-      }
+      for (int i = 0; i < AR; ++i) ar[i] = conv_load_a<MULTI>(rsrc_x, ti, a_voff[i], a_mask[i], a_pitch[MULTI ? i : 0]);
     } else {
       const int tap = chunk * 8 + lq;
       const int ky = tap / p.KW;
@@ -183,12 +106,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
     }
     if (p.in_relu) {
 #pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        ar[i].x = fmaxf(ar[i].x, 0.f);
-        ar[i].y = fmaxf(ar[i].y, 0.f);
-        ar[i].z = fmaxf(ar[i].z, 0.f);
-        ar[i].w = fmaxf(ar[i].w, 0.f);
-      }
+      for (int i = 0; i < AR; ++i) ar[i] = conv_relu4(ar[i]);
     }
 #pragma unroll
     for (int j = 0; j < BR; ++j)
@@ -213,6 +131,29 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
   const float* a_base = As + (wm * TM * 32 + frag_row) * LS + frag_k;
   const float* b_base = Bs + (wn * TN * 32 + frag_row) * LS + frag_k;
 
+  // one chunk of MFMAs from the operand tiles at ab / bb: per k-step one fragment read per 32-row tile, then the tt / i / j nest
+  auto multiply = [&](const float* ab, const float* bb) {
+#pragma unroll
+    for (int kk = 0; kk < BK / 8; ++kk) {
+      f32x4 af[TM], bf[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(ab + i * 32 * LS + kk * 8);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(bb + j * 32 * LS + kk * 8);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            if (TM * TN == 1 && (tt & 1))
+              acc_b = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][tt], bf[j][tt], acc_b, 0, 0, 0);
+            else
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][tt], bf[j][tt], acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
+  };
   auto stage_and_multiply = [&](auto& ar, auto& br, int next_chunk) {
 #pragma unroll
     for (int i = 0; i < AR; ++i) *reinterpret_cast<f32x4*>(As + (lr + RPP * i) * LS + 4 * lq) = ar[i];
@@ -220,7 +161,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
     for (int j = 0; j < BR; ++j) *reinterpret_cast<f32x4*>(Bs + (lr + RPP * j) * LS + 4 * lq) = br[j];
     __syncthreads();
     if (next_chunk < c_end) load_chunk(next_chunk, ar, br);
-    if constexpr (EOD_LDS_PIPE && TM * TN == 1) {
+    if constexpr (TM * TN == 1) {
       // 64x64 tile: the fragment reads of k-step kk + 1 are issued before the four MFMAs of k-step kk (two fragment sets in
       // registers), so that the LDS latency runs under the MFMAs of the same wave instead of after them
       f32x4 af[2], bf[2];
@@ -233,36 +174,17 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
           af[nxt] = *reinterpret_cast<const f32x4*>(a_base + (kk + 1) * 8);
           bf[nxt] = *reinterpret_cast<const f32x4*>(b_base + (kk + 1) * 8);
         }
-        if (EOD_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt)
           if (tt & 1)
             acc_b = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][tt], bf[cur][tt], acc_b, 0, 0, 0);
           else
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][tt], bf[cur][tt], acc[0][0], 0, 0, 0);
-        if (EOD_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
       }
     } else {
-#pragma unroll
-      for (int kk = 0; kk < BK / 8; ++kk) {
-        f32x4 af[TM], bf[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(a_base + i * 32 * LS + kk * 8);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(b_base + j * 32 * LS + kk * 8);
-        if (EOD_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              if (TM * TN == 1 && (tt & 1))
-                acc_b = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][tt], bf[j][tt], acc_b, 0, 0, 0);
-              else
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][tt], bf[j][tt], acc[i][j], 0, 0, 0);
-        if (EOD_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
-      }
+      multiply(a_base, b_base);
     }
     __syncthreads();
   };
@@ -280,28 +202,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
     for (int chunk = c_begin; chunk < c_end; ++chunk) {
       const bool more = chunk + 1 < c_end;
       if (more) load_chunk(chunk + 1, ar0, br0);
-      const float* ab = a_base + cur * BUF;
-      const float* bb = b_base + cur * BUF;
-#pragma unroll
-      for (int kk = 0; kk < BK / 8; ++kk) {
-        f32x4 af[TM], bf[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(ab + i * 32 * LS + kk * 8);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(bb + j * 32 * LS + kk * 8);
-        if (EOD_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              if (TM * TN == 1 && (tt & 1))
-                acc_b = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][tt], bf[j][tt], acc_b, 0, 0, 0);
-              else
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][tt], bf[j][tt], acc[i][j], 0, 0, 0);
-        if (EOD_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
-      }
+      multiply(a_base + cur * BUF, b_base + cur * BUF);
       if (more) store_tiles(cur ^ 1);
       __syncthreads();
       cur ^= 1;
@@ -394,107 +295,43 @@ __global__ __launch_bounds__(NW * 64) void conv_wavek_kernel(ConvArgs p) {
   float* As = lds + wave * (2 * 32 * LS);
   float* Bs = As + 32 * LS;
 
-  int M = p.M;
-  M = conv_row_limit(p, M);
-  const int ntiles = ((M + 31) / 32) * p.tiles_n;
-  if ((int)blockIdx.x >= ntiles) return;
-  const int t = xcd_remap(blockIdx.x, ntiles);
+  int M;
+  const int t = conv_first_tile<32>(p, M);
+  if (t < 0) return;
   const int tile_m = t / p.tiles_n;
   const int tile_n = t - tile_m * p.tiles_n;
   const int m0 = tile_m * 32, n0 = tile_n * 32;
   if (!conv_tile_active(p, m0, 32)) return;
 
   // this wave's chunks
-  const int cpw = (p.nchunks + NW - 1) / NW;
-  const int c_begin = wave * cpw;
-  int c_end = c_begin + cpw;
-  if (c_end > p.nchunks) c_end = p.nchunks;
+  int c_end;
+  const int c_begin = conv_chunk_range(p, (p.nchunks + NW - 1) / NW, wave, c_end);
 
   const int lr = lane >> 3, lq = lane & 7;
   unsigned a_voff[AR];
   unsigned long long a_mask[AR];
   unsigned a_pitch[MULTI ? AR : 1];
-#pragma unroll
-  for (int i = 0; i < AR; ++i) {
-    const int m = m0 + lr + 8 * i;
-    int iy0 = 0, ix0 = 0, off = 0, hh = 1, ww = 1;
-    const bool rowok = m < M;
-    if (rowok) {
-      if (MULTI) {
-        int l = 0;
-        while (l + 1 < p.nlv && m >= p.lv_off[l + 1]) ++l;
-        const int local = m - p.lv_off[l];
-        ww = p.lv_w[l];
-        hh = p.lv_h[l];
-        const int oy = local / ww;
-        iy0 = oy - p.pad;
-        ix0 = (local - oy * ww) - p.pad;
-        off = p.lv_off[l];
-      } else {
-        const int t2 = (int)fdiv((unsigned)m, p.div_ow);
-        const int ox = m - t2 * p.OW;
-        const int img = (int)fdiv((unsigned)t2, p.div_oh);
-        const int oy = t2 - img * p.OH;
-        iy0 = oy * p.stride - p.pad;
-        ix0 = ox * p.stride - p.pad;
-        off = img * p.H * p.W;
-        hh = p.H;
-        ww = p.W;
-      }
-    }
-    a_mask[i] = rowok ? tap_mask(iy0, ix0, hh, ww, p.KH, p.KW) : 0ull;
-    a_voff[i] = (unsigned)(((off + iy0 * ww + ix0) * p.Cin + 4 * lq) * 4);
-    if (MULTI) a_pitch[i] = (unsigned)(ww * p.Cin * 4);
-  }
   unsigned w_voff[AR];
 #pragma unroll
-  for (int j = 0; j < AR; ++j) {
-    const int n = n0 + lr + 8 * j;
-    w_voff[j] = n < p.Cout ? (unsigned)((n * p.Kpad + 4 * lq) * 4) : 0xFFFFFFFFu;
+  for (int i = 0; i < AR; ++i) {
+    conv_row_address<MULTI>(p, m0 + lr + 8 * i, M, lq, a_voff[i], a_mask[i], a_pitch[MULTI ? i : 0]);
+    w_voff[i] = conv_w_row_offset(p, n0 + lr + 8 * i, lq);
   }
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = conv_buffer(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_w = conv_buffer(p.w, p.w_bytes);
 
   // two operand sets in registers: while chunk c is multiplied, chunks c+1 and c+2 are in flight (a wave walks its K share alone:
   // with 1-2 waves per SIMD the global-load latency is hidden by prefetch depth, not by occupancy)
   f32x4 ar0[AR], br0[AR], ar1[AR], br1[AR];
-  int nx_tap, nx_c0, nx_ky, nx_kx;
-  {
-    const int k0 = c_begin * BK;
-    nx_tap = k0 / p.Cin;
-    nx_c0 = k0 - nx_tap * p.Cin;
-    nx_ky = nx_tap / p.KW;
-    nx_kx = nx_tap - nx_ky * p.KW;
-  }
+  ChunkWalker<BK, MULTI> walk(p, c_begin);
   auto load_chunk = [&](int chunk, f32x4 (&ar)[AR], f32x4 (&br)[AR]) {
     const int k0 = chunk * BK;
-    const int tap = nx_tap, c0 = nx_c0, ky = nx_ky, kx = nx_kx;
-    nx_c0 += BK;
-    if (nx_c0 >= p.Cin) {
-      nx_c0 = 0;
-      ++nx_tap;
-      if (++nx_kx == p.KW) {
-        nx_kx = 0;
-        ++nx_ky;
-      }
-    }
-    const unsigned tap_off = MULTI ? (unsigned)((kx * p.Cin + c0) * 4) : (unsigned)(((ky * p.W + kx) * p.Cin + c0) * 4);
+    const TapInfo ti = walk.next(p);
 #pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      const bool ok = (a_mask[i] >> tap) & 1ull;
-      unsigned vo = a_voff[i] + tap_off;
-      if (MULTI) vo += (unsigned)ky * a_pitch[i];
-      vo = ok ? vo : 0xFFFFFFFFu;
-      ar[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, 0, 0));
-    }
+    for (int i = 0; i < AR; ++i) ar[i] = conv_load_a<MULTI>(rsrc_x, ti, a_voff[i], a_mask[i], a_pitch[MULTI ? i : 0]);
     if (p.in_relu) {
 #pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        ar[i].x = fmaxf(ar[i].x, 0.f);
-        ar[i].y = fmaxf(ar[i].y, 0.f);
-        ar[i].z = fmaxf(ar[i].z, 0.f);
-        ar[i].w = fmaxf(ar[i].w, 0.f);
-      }
+      for (int i = 0; i < AR; ++i) ar[i] = conv_relu4(ar[i]);
     }
 #pragma unroll
     for (int j = 0; j < AR; ++j)

@@ -123,25 +123,6 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_gn_kernel(ConvArgs p) 
   }
 }
 
-inline int big_tile_env() {
-  static const int v = [] {
-    const char* e = getenv("EOD_CONV_BIG_TILE");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-
-inline int default_bk() {
-  static const int v = [] {
-    const char* e = getenv("EOD_CONV_BK");
-    // measured end to end on the final schedule (profiles/r01_bench_640_default.log era): BK=32 140.8 frames/s / 119.6 TFLOP/s on the
-    // mask GEMM vs BK=64 139.4 / 117.4 (smaller LDS tile -> one more workgroup per CU; the halved barrier count of BK=64 stopped
-    // paying once the K-loop bookkeeping became incremental)
-    return (e && atoi(e) == 64) ? 64 : 32;
-  }();
-  return v;
-}
-
 // Process-wide arithmetic mode of eod_conv2d (eod_set_conv_math / EOD_CONV_MATH): 0 fp32 MFMA, 1 bf16x3 split, 2 f16 operands.
 // The environment value is matched exactly; anything else (unset, empty, a misspelling) is the fp32 default.
 std::atomic<int>& math_mode() {
@@ -162,23 +143,7 @@ struct Plan {
   int wavek;  // 0, or the number of waves (4 / 8) of the 32x32-tile kernel that splits K over the waves of a workgroup
 };
 
-inline int midsplit_env() {          // experiment knob: EOD_CONV_MIDSPLIT=0 turns the 256..1024-tile split-K rule off
-  static const int v = [] {
-    const char* e = getenv("EOD_CONV_MIDSPLIT");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-inline int wavek_env() {
-  static const int v = [] {
-    const char* e = getenv("EOD_CONV_WAVEK");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
+Plan make_plan(const EodConvDesc* d, int M) {
   // 256x128: bf16x3 / f16 8-wave kernels only; 64x256: fused mask-head tail (out_mode 2) only
   static const int cfg[5][2] = {{128, 128}, {128, 64}, {64, 64}, {256, 128}, {64, 256}};
   Plan pl{};
@@ -193,7 +158,6 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
   if (f16_forced) pick = ft == 4 ? 3 : 2;
   else if (ft >= 1 && ft <= 3) pick = ft - 1;
   else if (ft == 4 && fbk == 5 && half_ok) pick = 3;
-  else if (M >= 32768 && big_tile_env() >= 1 && big_tile_env() <= 3) pick = big_tile_env() - 1;   // experiment knob
   const bool bk64_ok = !d->tap4 && d->Cin % 64 == 0 && d->Kpad % 64 == 0;
   pl.glds = f16_forced ? 3 : ((fbk == 5 && half_ok) ? 2 : 0);
   // tile and split-K are decided on `plan_rows` when given (a batch planned like one image: identical K walk, bitwise equal results)
@@ -227,9 +191,11 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
   // f16: BK = 32 measured faster or equal on the frame's layers (two 256x128 workgroups per CU instead of one; tools/f16_check.py);
   // BK = 64 stays selectable (force_tile 8x) where Cin % 64 == 0, so that a chunk never straddles two filter taps
   if (pl.glds == 3) pl.bk = (fbk == 8 && d->Cin % 64 == 0) ? 64 : 32;
-  else pl.bk = (pl.glds || d->out_mode == 2) ? 32 : ((fbk == 2 && bk64_ok) ? 64 : (fbk == 1 ? 32 : (bk64_ok && default_bk() == 64 ? 64 : 32)));
+  // fp32: BK = 32 unless force_tile 2x asks for 64.  Measured end to end on the final schedule (profiles/r01_bench_640_default.log
+  // era): BK=32 140.8 frames/s / 119.6 TFLOP/s on the mask GEMM vs BK=64 139.4 / 117.4 (smaller LDS tile -> one more workgroup per
+  // CU; the halved barrier count of BK=64 stopped paying once the K-loop bookkeeping became incremental)
+  else pl.bk = (pl.glds == 0 && d->out_mode != 2 && fbk == 2 && bk64_ok) ? 64 : 32;
   const int nchunks = d->Kpad / pl.bk;
-  (void)nchunks32;
   pl.nchunks = nchunks;
   pl.tile = pick + 1;
   pl.bm = cfg[pick][0];
@@ -244,7 +210,7 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
     splitk = d->force_splitk;
   } else if (pl.glds == 0 && !d->tap4 && nchunks >= 8 &&
              ((d->force_tile == 6 || d->force_tile == 7) ||
-              (tiles < 256 && nchunks <= 192 && pl.bk == 32 && d->force_tile == 0 && wavek_env() &&
+              (tiles < 256 && nchunks <= 192 && pl.bk == 32 && d->force_tile == 0 &&
                ((Mp <= 512 && nchunks / (nchunks >= 64 ? 8 : 4) >= 8) || nchunks >= 128)))) {
     // Few rows and a deep K (ResNet layer4 at batch 1, FPN lateral / output 5, P6/P7, the box heads' 1024-wide FC layers): K is
     // split over the waves of a workgroup that owns a 32x32 tile (conv_wavek_kernel) -- no slabs, no reduce launch.  Eight waves
@@ -267,7 +233,7 @@ Plan make_plan(const EodConvDesc* d, int M, int nchunks32) {
     int maxs = nchunks / 4;
     splitk = want < maxs ? want : maxs;
     if (splitk < 1) splitk = 1;
-  } else if (tiles >= 256 && tiles <= 1024 && d->m_count == nullptr && nchunks >= 18 && midsplit_env()) {
+  } else if (tiles >= 256 && tiles <= 1024 && d->m_count == nullptr && nchunks >= 18) {
     // A few hundred tiles on 256 CUs: every workgroup is resident at once and a CU works through its workgroups' MFMAs one
     // after the other, so the launch takes ceil(tiles / 256) tile times -- the CenterNet tower's 536 tiles take 3 where 2.09
     // would do.  Split-K makes the units finer: time ~ ceil(tiles * s / 256) / s (+ ~0.12 of a tile for the slab reduce).
@@ -401,14 +367,14 @@ extern "C" int eod_conv2d_gn_fused(const EodConvDesc* d) {
   EodConvDesc t = *d;
   t.gn_partial = nullptr;
   if (check_desc(&t) != EOD_OK) return 0;
-  return make_plan(&t, total_rows(&t), t.Kpad / 32).splitk > 1 ? 1 : 0;
+  return make_plan(&t, total_rows(&t)).splitk > 1 ? 1 : 0;
 }
 
 extern "C" int eod_conv2d_plan(const EodConvDesc* d, EodConvPlan* out) {
   if (!out) return EOD_ERR_NULL;
   const int st = check_desc(d);
   if (st != EOD_OK) return st;
-  const Plan pl = make_plan(d, total_rows(d), d->Kpad / 32);
+  const Plan pl = make_plan(d, total_rows(d));
   out->tile = pl.tile; out->bm = pl.bm; out->bn = pl.bn; out->bk = pl.bk;
   out->splitk = pl.splitk; out->cps = pl.cps; out->nchunks = pl.nchunks;
   out->wavek = pl.wavek; out->glds = pl.glds;
@@ -420,8 +386,7 @@ extern "C" int eod_conv2d_plan(const EodConvDesc* d, EodConvPlan* out) {
 extern "C" size_t eod_conv2d_workspace_bytes(const EodConvDesc* d) {
   if (check_desc(d) != EOD_OK) return 0;
   const int M = total_rows(d);
-  const int nchunks = d->Kpad / 32;
-  const Plan pl = make_plan(d, M, nchunks);
+  const Plan pl = make_plan(d, M);
   if (pl.splitk <= 1) return 0;
   return (size_t)pl.splitk * M * d->Cout * sizeof(float);
 }
@@ -467,7 +432,7 @@ extern "C" int eod_conv2d(const EodConvDesc* d, eod_stream_t stream) {
   a.gn_groups = d->gn_groups;
   a.y2 = d->y2;
   a.split_n = d->split_n;
-  const Plan pl = make_plan(d, a.M, d->Kpad / 32);
+  const Plan pl = make_plan(d, a.M);
   if (d->gn_partial && pl.splitk <= 1) return EOD_ERR_BAD_DIMS;      // the statistics ride on the slab reduce (see eod_conv2d_gn_fused)
   a.nchunks = pl.nchunks;
   a.splitk = pl.splitk; a.cps = pl.cps; a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n;

@@ -454,8 +454,8 @@ def test_production_calls_match_fp64_in_both_modes(dev, recorded, size):
 # Families `make_plan` has code for that no force_tile = 0 call can get, whatever its shape: listed with the reason, asserted absent
 # (a planner change that makes one reachable has to move it to the required set), and run through force_tile in the supplement.
 UNREACHABLE = {
-    # default_bk() is 32 unless EOD_CONV_BK=64 is set in the environment (an experiment knob)
-    "fp32 64x64 BK64": "BK = 64 is chosen by the EOD_CONV_BK environment knob or force_tile 2x only",
+    # make_plan gives the fp32 kernel BK = 32 (measured) unless the call forces 64
+    "fp32 64x64 BK64": "BK = 64 is chosen by force_tile 2x only",
     # t128 >= 512 implies t256 >= 256 (ceil(M / 256) >= ceil(M / 128) / 2): the 256x128 kernel always wins the comparison
     "bf16x3 128x128 BK32": "the planner's t128 >= 512 branch is shadowed by t256 >= 256",
 }
