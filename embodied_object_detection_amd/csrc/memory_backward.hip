@@ -1,6 +1,12 @@
-// Backward of the memory READ (first slice): gradients of the three `map_merge_projection` 1x1 convolutions and of
-// the cascaded average pools of `CustomRecurrentFPN.forward` (Detic/detic/modeling/backbone/timm.py:142-192), the part of
-// `forward_model` (custom_rcnn.py:584-679) that is specific to the spatial memory.  Forward, per level l = 3, 4, 5:
+// The training step's backward kernels that are not a convolution's weight gradient (those: conv_wgrad.hip):
+//   * backward of the memory READ: gradients of the three `map_merge_projection` 1x1 convolutions and of the cascaded average pools
+//     of `CustomRecurrentFPN.forward` (Detic/detic/modeling/backbone/timm.py:142-192), below;
+//   * AdamW with detectron2's clip by value, for one tensor and for many in one launch, and the loss scaler's non-finite pass;
+//   * backward of the FPN top-down add (upsample), of the trunk's 3x3 s2 max pool and of ReLU;
+//   * the rotation of a layer's weights for its input-gradient convolution.
+//
+// The memory read (the part of `forward_model`, custom_rcnn.py:584-679, that is specific to the spatial memory).  Forward, per level
+// l = 3, 4, 5:
 //
 //   E_l = half(avg_pool2(float(E_{l-1})))          E_2 := avg_pool4(float(memory[proj]))  (fp32)
 //   out_l = (conv1x1(float(E_l); W_l, b_l) * weight) + P_l
@@ -17,10 +23,9 @@
 // The memory table itself is an input of the reference's training step (loaded from disk, loader.py:199-223), not a parameter: no
 // gradient flows below E_2.
 //
-// Kernel 1 needs no LDS staging: the MFMA operand layout of v_mfma_f32_32x32x2_f32 (lane l supplies row l % 32, k = l / 32) reads
-// 32 consecutive channels of one position per half wave -- coalesced as the rows lie in memory.  A workgroup owns one 32x32 tile
-// of dW_l; its four waves take a quarter of the positions each and are added in wave order (deterministic).
-#include "eod_common.h"
+// Kernel 1 is the direct scheme of wgrad_common.h: a workgroup owns one 32x32 tile of dW_l, its four waves take a quarter of the
+// positions each and are added in wave order (deterministic).
+#include "wgrad_common.h"
 #include <algorithm>
 #include "../../include/eod_hip.h"
 #include <hip/hip_fp16.h>
@@ -55,66 +60,22 @@ __global__ __launch_bounds__(256) void proj_backward_weights_kernel(BwdArgs a) {
   const int level = blockIdx.y;
   const int tile = blockIdx.x;              // 8 (co) x 16 (ci) tiles of 32x32
   const int co0 = (tile >> 4) * 32, ci0 = (tile & 15) * 32;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int P = a.rows[level];
   const float* __restrict__ G = a.g[level];
-  const int col = lane & 31, kh = lane >> 5;
-  // positions of this workgroup's range, then of this wave: a contiguous quarter, rounded to whole k-steps of 8 positions
-  const int steps = (P + 7) / 8;
-  const int sps = (steps + a.splits - 1) / a.splits;
-  const int z_begin = (int)blockIdx.z * sps;
-  const int z_end = min(z_begin + sps, steps);
-  const int spw = (sps + 3) / 4;
-  const int s_begin = z_begin + wave * spw;
-  int s_end = s_begin + spw;
-  if (s_end > z_end) s_end = z_end;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float bsum = 0.f;
+  const int col = threadIdx.x & 31;
   const int ci = ci0 + col;
-  for (int s = s_begin; s < s_end; ++s) {
-    float av[4], bv[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int pos = s * 8 + 2 * t + kh;       // instruction t contracts positions 8 s + 2 t and 8 s + 2 t + 1
-      const bool ok = pos < P;
-      av[t] = ok ? G[(size_t)pos * 256 + co0 + col] : 0.f;
-      bv[t] = ok ? __half2float(a.pooled[frag_half_offset(a.tile_base[level] + (pos >> 5), pos & 31, ci >> 3) + (ci & 7)]) : 0.f;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t], acc, 0, 0, 0);
-      bsum += av[t];
-    }
-  }
-  __shared__ float red[3 * 16 * 64];
-  __shared__ float bred[4 * 64];
-  bred[wave * 64 + lane] = bsum;
-  if (wave > 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[((wave - 1) * 16 + r) * 64 + lane] = acc[r];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 1; w < 4; ++w)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] += red[((w - 1) * 16 + r) * 64 + lane];
-  // C/D layout: column (ci) = lane & 31, row (co) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-  float* dw = a.splits > 1 ? a.part + ((size_t)level * a.splits + blockIdx.z) * (256 * 512) : a.dw[level];
-  float* db = a.splits > 1 ? a.bpart + ((size_t)level * a.splits + blockIdx.z) * 256 : a.db[level];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = co0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-    dw[(size_t)co * 512 + ci] = acc[r] * a.weight;
-  }
-  if ((tile & 15) == 0 && lane < 32) {
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v += bred[w * 64 + lane] + bred[w * 64 + 32 + lane];    // even + odd positions, wave order
-    db[co0 + lane] = v * a.weight;
-  }
+  wgrad_direct_tile(
+      a, a.rows[level],
+      [&](int pos, float& gv, float& xv) {
+        gv = G[(size_t)pos * 256 + co0 + col];
+        xv = __half2float(a.pooled[frag_half_offset(a.tile_base[level] + (pos >> 5), pos & 31, ci >> 3) + (ci & 7)]);
+      },
+      [&](float*& dst, float*& db_tile) {
+        float *dw, *db;
+        wgrad_outputs(a, (size_t)level * a.splits + blockIdx.z, 256 * 512, 256, a.dw[level], a.db[level], dw, db);
+        dst = dw + (size_t)co0 * 512 + ci;
+        db_tile = (tile & 15) == 0 ? db + co0 : nullptr;
+      },
+      512, a.weight);
 }
 
 struct PoolBwdArgs {
@@ -257,599 +218,6 @@ __global__ __launch_bounds__(256) void grads_nonfinite_kernel(FiniteMulti a) {
   if (bad) *a.flag = 1;
 }
 
-// Third slice: backward of a stride-1 'same' convolution layer (FPN output convs timm.py:118-136, CenterNet tower
-// centernet_head.py:141-161, mask head convs: KH x KW taps, NHWC).  Weight gradient in the layout of the packed forward weights:
-//   dW[co][(ky, kx, ci)] = sum over positions (n, oy, ox) of G[pos][co] * X[n][oy + ky - pad][ox + kx - pad][ci]      (0 outside the image)
-//   db[co] = sum over positions of G[pos][co]
-// Same scheme as proj_backward_weights_kernel: no LDS staging, the MFMA operand layout of v_mfma_f32_32x32x2_f32 reads 32 consecutive
-// channels of one position per half wave (coalesced as the NHWC rows lie in memory); a workgroup owns one 32 (co) x 32 (ci) tile of
-// one tap, its four waves take a quarter of the positions each and are added in wave order (deterministic).  The gradient with
-// respect to the input is a convolution of G with the 180-degree rotated, in/out-transposed weights: eod_conv2d (ops.ConvBackward).
-#define WGRAD_MAX_LEVELS 8
-struct ConvBwdArgs {
-  const float* x;   // [N,H,W,Cin]
-  const float* g;   // [N,H,W,Cout]
-  float* dw;        // [Cout][KH*KW*Cin]
-  float* db;        // [Cout] or null
-  int N, H, W, Cin, Cout, KH, KW, pad, stride, OH, OW;
-  FastDiv div_w, div_h;     // by OW, OH
-  // splits > 1 (blockIdx.z): the positions are cut into `splits` contiguous ranges, each writing its own partial dW / db into
-  // part [splits][Cout * Ktot] / bpart [splits][Cout]; wgrad_reduce_kernel adds them in range order.  Layers with few channel tiles
-  // and many positions (the trunk's first stages: 4 .. 64 workgroups otherwise) fill the chip this way.
-  int splits;
-  float* part;
-  float* bpart;
-  // pyramid mode of the LDS-tiled kernel (nlv > 0; stride 1, 'same' padding): x / g are row lists, rows [lv_off[l], lv_off[l+1])
-  // are an lv_h[l] x lv_w[l] image, the weights are shared by the levels and dW / db are summed over all of them
-  int nlv;
-  int lv_off[WGRAD_MAX_LEVELS + 1], lv_h[WGRAD_MAX_LEVELS], lv_w[WGRAD_MAX_LEVELS];
-};
-
-__global__ __launch_bounds__(256) void conv_backward_weights_kernel(ConvBwdArgs a) {
-  const int ci_tiles = a.Cin >> 5;
-  const int tile = blockIdx.x;                       // (co tile, ci tile)
-  const int co0 = (tile / ci_tiles) * 32, ci0 = (tile % ci_tiles) * 32;
-  const int tap = blockIdx.y;
-  const int ky = tap / a.KW, kx = tap - ky * a.KW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 31, kh = lane >> 5;
-  const int P = a.N * a.OH * a.OW;            // positions of the OUTPUT grid
-  const int steps = (P + 7) / 8;
-  const int sps = (steps + a.splits - 1) / a.splits;           // steps of this split
-  const int z_begin = blockIdx.z * sps;
-  const int z_end = min(z_begin + sps, steps);
-  const int spw = (sps + 3) / 4;
-  const int s_begin = z_begin + wave * spw;
-  int s_end = s_begin + spw;
-  if (s_end > z_end) s_end = z_end;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float bsum = 0.f;
-  for (int s = s_begin; s < s_end; ++s) {
-    float av[4], bv[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int pos = s * 8 + 2 * t + kh;            // instruction t contracts positions 8 s + 2 t and 8 s + 2 t + 1
-      float gv = 0.f, xv = 0.f;
-      if (pos < P) {
-        gv = a.g[(size_t)pos * a.Cout + co0 + col];
-        const int row = (int)fdiv((unsigned)pos, a.div_w);           // n * OH + oy
-        const int ox = pos - row * a.OW;
-        const int n = (int)fdiv((unsigned)row, a.div_h);
-        const int oy = row - n * a.OH;
-        const int iy = oy * a.stride + ky - a.pad, ix = ox * a.stride + kx - a.pad;
-        if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-          xv = a.x[((size_t)(n * a.H + iy) * a.W + ix) * a.Cin + ci0 + col];
-      }
-      av[t] = gv;
-      bv[t] = xv;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t], acc, 0, 0, 0);
-      bsum += av[t];
-    }
-  }
-  __shared__ float red[3 * 16 * 64];
-  __shared__ float bred[4 * 64];
-  bred[wave * 64 + lane] = bsum;
-  if (wave > 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[((wave - 1) * 16 + r) * 64 + lane] = acc[r];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 1; w < 4; ++w)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] += red[((w - 1) * 16 + r) * 64 + lane];
-  // C/D layout: column (ci) = lane & 31, row (co) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-  const int Ktot = a.KH * a.KW * a.Cin;
-  float* dw = a.splits > 1 ? a.part + (size_t)blockIdx.z * a.Cout * Ktot : a.dw;
-  float* db = a.splits > 1 ? a.bpart + (size_t)blockIdx.z * a.Cout : a.db;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = co0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-    dw[(size_t)co * Ktot + (size_t)tap * a.Cin + ci0 + col] = acc[r];
-  }
-  if (a.db && tap == 0 && (tile % ci_tiles) == 0 && lane < 32) {
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v += bred[w * 64 + lane] + bred[w * 64 + 32 + lane];    // even + odd positions, wave order
-    db[co0 + lane] = v;
-  }
-}
-
-// The same contraction with a 64 (co) x 64 (ci) register block per wave (round 4).  The 32 x 32 form above issues one MFMA per pair
-// of operand loads and redoes the position arithmetic (two divisions, the tap's bounds test) for every load: 35 TFLOP/s, bound by
-// instruction issue and by the L1 operand path, not by the matrix cores.  Here a k-step loads G for two 32-channel blocks and X for
-// two, with ONE position computation, and feeds four MFMAs: half the loads and a quarter of the address arithmetic per FLOP.  The
-// four waves of a workgroup still split the range's positions and are added in wave order through LDS; a layer with 32 channels on
-// one side (the 5-channel head padded to 32, bbox_pred.2) runs with the second block switched off.
-__global__ __launch_bounds__(256) void conv_backward_weights_rb_kernel(ConvBwdArgs a) {
-  const int ci_tiles = (a.Cin + 63) >> 6;
-  const int tile = blockIdx.x;                       // (co tile, ci tile) of 64 x 64
-  const int co0 = (tile / ci_tiles) * 64, ci0 = (tile % ci_tiles) * 64;
-  const bool co2 = co0 + 32 < a.Cout, ci2 = ci0 + 32 < a.Cin;     // workgroup-uniform
-  const int tap = blockIdx.y;
-  const int ky = tap / a.KW, kx = tap - ky * a.KW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 31, kh = lane >> 5;
-  const int P = a.N * a.OH * a.OW;
-  const int steps = (P + 7) / 8;
-  const int sps = (steps + a.splits - 1) / a.splits;
-  const int z_begin = blockIdx.z * sps;
-  const int z_end = min(z_begin + sps, steps);
-  const int spw = (sps + 3) / 4;
-  const int s_begin = z_begin + wave * spw;
-  int s_end = s_begin + spw;
-  if (s_end > z_end) s_end = z_end;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  float bsum0 = 0.f, bsum1 = 0.f;
-  for (int s = s_begin; s < s_end; ++s) {
-    float g0[4], g1[4], x0[4], x1[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int pos = s * 8 + 2 * t + kh;            // instruction t contracts positions 8 s + 2 t and 8 s + 2 t + 1
-      float ga = 0.f, gb = 0.f, xa = 0.f, xb = 0.f;
-      if (pos < P) {
-        const float* gp = a.g + (size_t)pos * a.Cout + co0 + col;
-        ga = gp[0];
-        if (co2) gb = gp[32];
-        const int row = (int)fdiv((unsigned)pos, a.div_w);           // n * OH + oy
-        const int ox = pos - row * a.OW;
-        const int n = (int)fdiv((unsigned)row, a.div_h);
-        const int oy = row - n * a.OH;
-        const int iy = oy * a.stride + ky - a.pad, ix = ox * a.stride + kx - a.pad;
-        if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W) {
-          const float* xp = a.x + ((size_t)(n * a.H + iy) * a.W + ix) * a.Cin + ci0 + col;
-          xa = xp[0];
-          if (ci2) xb = xp[32];
-        }
-      }
-      g0[t] = ga; g1[t] = gb; x0[t] = xa; x1[t] = xb;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(g0[t], x0[t], acc[0][0], 0, 0, 0);
-      if (ci2) acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(g0[t], x1[t], acc[0][1], 0, 0, 0);
-      if (co2) acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(g1[t], x0[t], acc[1][0], 0, 0, 0);
-      if (co2 && ci2) acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(g1[t], x1[t], acc[1][1], 0, 0, 0);
-      bsum0 += g0[t];
-      bsum1 += g1[t];
-    }
-  }
-  // waves 1..3 hand their 64 x 64 block to wave 0 through LDS, one 32 x 32 quarter at a time (12 KB), added in wave order
-  __shared__ float red[3 * 16 * 64];
-  __shared__ float bred[2][4 * 64];
-  bred[0][wave * 64 + lane] = bsum0;
-  bred[1][wave * 64 + lane] = bsum1;
-  const int Ktot = a.KH * a.KW * a.Cin;
-  float* dw = a.splits > 1 ? a.part + (size_t)blockIdx.z * a.Cout * Ktot : a.dw;
-  float* db = a.splits > 1 ? a.bpart + (size_t)blockIdx.z * a.Cout : a.db;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if ((i && !co2) || (j && !ci2)) continue;      // workgroup-uniform
-      __syncthreads();                               // the previous quarter has been consumed
-      if (wave > 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[((wave - 1) * 16 + r) * 64 + lane] = acc[i][j][r];
-      }
-      __syncthreads();
-      if (wave == 0) {
-        f32x16 v = acc[i][j];
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] += red[((w - 1) * 16 + r) * 64 + lane];
-        // C/D layout: column (ci) = lane & 31, row (co) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int co = co0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh;
-          dw[(size_t)co * Ktot + (size_t)tap * a.Cin + ci0 + 32 * j + col] = v[r];
-        }
-      }
-    }
-  }
-  if (a.db && tap == 0 && (tile % ci_tiles) == 0 && wave == 0 && lane < 32) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (i && !co2) continue;
-      float v = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) v += bred[i][w * 64 + lane] + bred[i][w * 64 + 32 + lane];    // even + odd positions, wave order
-      db[co0 + 32 * i + lane] = v;
-    }
-  }
-}
-
-// LDS-tiled form (round 4, second step): the contraction index of dW = G^T . X is the POSITION, the slow index of both operands, so
-// the register-blocked kernel above still fetches one dword per lane and MFMA and computes an address per operand pair.  Here a
-// workgroup (2 x 2 waves, 64 co x 64 ci of one tap) walks its position range in chunks of 32: the chunk's G rows [32][64] and the
-// tap-shifted, border-masked X rows [32][64] are fetched with two 16-byte loads per thread each (ONE position computation per load)
-// into registers, staged in LDS as they lie ([position][channel]: conflict-free stores), and every MFMA operand is one ds_read_b32
-// (lane = channel, half wave = position parity).  The next chunk's global loads are in flight under the 16 MFMAs of the current one.
-template <bool LEVELS>
-__global__ __launch_bounds__(256) void conv_backward_weights_lds_kernel(ConvBwdArgs a) {
-  constexpr int PK = 32, TC = 64;
-  __shared__ __attribute__((aligned(16))) float As[PK][TC];
-  __shared__ __attribute__((aligned(16))) float Bs[PK][TC];
-  __shared__ float bred[16][TC];
-  const int ci_tiles = (a.Cin + 63) >> 6;
-  const int tile = blockIdx.x;
-  const int co0 = (tile / ci_tiles) * 64, ci0 = (tile % ci_tiles) * 64;
-  const int tap = blockIdx.y;
-  const int ky = tap / a.KW, kx = tap - ky * a.KW;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r = lane & 31, kh = lane >> 5;
-  const int P = LEVELS ? a.lv_off[a.nlv] : a.N * a.OH * a.OW;
-  const int chunks = (P + PK - 1) / PK;
-  const int cps = (chunks + a.splits - 1) / a.splits;
-  const int c_begin = blockIdx.z * cps;
-  const int c_end = min(c_begin + cps, chunks);
-  // loader role: thread -> (position row lp + 16 i, four channels c4 .. c4 + 3)
-  const int lp = tid >> 4, c4 = (tid & 15) * 4;
-  const bool g_ok = co0 + c4 < a.Cout, x_ok = ci0 + c4 < a.Cin;          // Cout, Cin are multiples of 32 (and of 4)
-  f32x4 gr[2], xr[2];
-  auto load_chunk = [&](int c) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int pos = c * PK + lp + 16 * i;
-      f32x4 gv = {0.f, 0.f, 0.f, 0.f}, xv = {0.f, 0.f, 0.f, 0.f};
-      if (pos < P) {
-        if (g_ok) gv = *reinterpret_cast<const f32x4*>(a.g + (size_t)pos * a.Cout + co0 + c4);
-        if (LEVELS) {
-          int l = 0;
-#pragma unroll
-          for (int q = 1; q < WGRAD_MAX_LEVELS; ++q) l += (q < a.nlv && pos >= a.lv_off[q]) ? 1 : 0;
-          const int base = a.lv_off[l], lw = a.lv_w[l], lh = a.lv_h[l];
-          const int local = pos - base;
-          const int oy = local / lw, ox = local - oy * lw;
-          const int iy = oy + ky - a.pad, ix = ox + kx - a.pad;
-          if (x_ok && (unsigned)iy < (unsigned)lh && (unsigned)ix < (unsigned)lw)
-            xv = *reinterpret_cast<const f32x4*>(a.x + ((size_t)base + (size_t)iy * lw + ix) * a.Cin + ci0 + c4);
-        } else {
-          const int row = (int)fdiv((unsigned)pos, a.div_w);           // n * OH + oy
-          const int ox = pos - row * a.OW;
-          const int n = (int)fdiv((unsigned)row, a.div_h);
-          const int oy = row - n * a.OH;
-          const int iy = oy * a.stride + ky - a.pad, ix = ox * a.stride + kx - a.pad;
-          if (x_ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-            xv = *reinterpret_cast<const f32x4*>(a.x + ((size_t)(n * a.H + iy) * a.W + ix) * a.Cin + ci0 + c4);
-        }
-      }
-      gr[i] = gv;
-      xr[i] = xv;
-    }
-  };
-  f32x16 acc;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-  f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-  if (c_begin < c_end) load_chunk(c_begin);
-  for (int c = c_begin; c < c_end; ++c) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      *reinterpret_cast<f32x4*>(&As[lp + 16 * i][c4]) = gr[i];
-      *reinterpret_cast<f32x4*>(&Bs[lp + 16 * i][c4]) = xr[i];
-      bsum += gr[i];
-    }
-    __syncthreads();
-    if (c + 1 < c_end) load_chunk(c + 1);
-    const float* ap = &As[kh][wm * 32 + r];
-    const float* bp = &Bs[kh][wn * 32 + r];
-#pragma unroll
-    for (int kk = 0; kk < PK / 2; ++kk)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[kk * 2 * TC], bp[kk * 2 * TC], acc, 0, 0, 0);
-    __syncthreads();
-  }
-  // C/D layout: column (ci) = lane & 31, row (co) = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
-  const int Ktot = a.KH * a.KW * a.Cin;
-  float* dw = a.splits > 1 ? a.part + (size_t)blockIdx.z * a.Cout * Ktot : a.dw;
-  float* db = a.splits > 1 ? a.bpart + (size_t)blockIdx.z * a.Cout : a.db;
-  const int ci = ci0 + wn * 32 + r;
-  if (ci < a.Cin) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int co = co0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * kh;
-      if (co < a.Cout) dw[(size_t)co * Ktot + (size_t)tap * a.Cin + ci] = acc[q];
-    }
-  }
-  if (a.db && tap == 0 && (tile % ci_tiles) == 0) {
-    // db[co] = sum over the positions: the 16 loader rows' sums, added in row order
-    bred[lp][c4 + 0] = bsum.x; bred[lp][c4 + 1] = bsum.y; bred[lp][c4 + 2] = bsum.z; bred[lp][c4 + 3] = bsum.w;
-    __syncthreads();
-    if (tid < TC && co0 + tid < a.Cout) {
-      float v = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v += bred[q][tid];
-      db[co0 + tid] = v;
-    }
-  }
-}
-
-// The LDS-tiled weight gradient in f16 arithmetic (the AMP training step): dW = half(G)^T . half(X) on
-// v_mfma_f32_32x32x16_f16, fp32 accumulate; db = the fp32 sum of the unrounded G.  Same workgroup shape (2 x 2 waves, 64 co x 64 ci of
-// one tap), position ranges and partial-result layout as the fp32 kernel above.  The contraction index is the position, and the f16
-// MFMA wants 8 consecutive k per lane, so the operands are transposed on their way into LDS: a loader thread fetches four channels
-// of FOUR consecutive positions (four 16-byte loads per operand and chunk of 64 positions), rounds them (v_cvt_pk_f16_f32: RNE,
-// overflow to inf, nothing clamped) and writes, per channel, its four positions as one 8-byte store into the [channel][position]
-// image.  Rows are 64 halves + 16 bytes (144: an odd number of 16-byte slots, as in conv_f16.hip), so that the one ds_read_b128
-// per operand and MFMA (lane = channel, half wave = positions 8h .. 8h + 7 of the K = 16 step) is conflict free.
-typedef _Float16 wg_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
-typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned wg_pk_f16(float a, float b) {
-  wg_f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wg_f16x2));   // v_cvt_pk_f16_f32 (RNE)
-}
-
-__global__ __launch_bounds__(256) void conv_backward_weights_f16_kernel(ConvBwdArgs a) {
-  constexpr int PK = 64, TC = 64, ROWB = 2 * PK + 16;
-  __shared__ __attribute__((aligned(16))) char As[TC * ROWB];     // half(G)^T: [co][position]
-  __shared__ __attribute__((aligned(16))) char Bs[TC * ROWB];     // half(X)^T: [ci][position]
-  __shared__ float bred[16][TC];
-  const int ci_tiles = (a.Cin + 63) >> 6;
-  const int tile = blockIdx.x;
-  const int co0 = (tile / ci_tiles) * 64, ci0 = (tile % ci_tiles) * 64;
-  const int tap = blockIdx.y;
-  const int ky = tap / a.KW, kx = tap - ky * a.KW;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r = lane & 31, kh = lane >> 5;
-  const int P = a.N * a.OH * a.OW;
-  const int chunks = (P + PK - 1) / PK;
-  const int cps = (chunks + a.splits - 1) / a.splits;
-  const int c_begin = blockIdx.z * cps;
-  const int c_end = min(c_begin + cps, chunks);
-  // loader role: thread -> (positions 4 lp .. 4 lp + 3 of the chunk, channels c4 .. c4 + 3)
-  const int lp = tid >> 4, c4 = (tid & 15) * 4;
-  const bool g_ok = co0 + c4 < a.Cout, x_ok = ci0 + c4 < a.Cin;          // Cout, Cin are multiples of 32 (and of 4)
-  f32x4 gr[4], xr[4];
-  auto load_chunk = [&](int c) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int pos = c * PK + 4 * lp + i;
-      f32x4 gv = {0.f, 0.f, 0.f, 0.f}, xv = {0.f, 0.f, 0.f, 0.f};
-      if (pos < P) {
-        if (g_ok) gv = *reinterpret_cast<const f32x4*>(a.g + (size_t)pos * a.Cout + co0 + c4);
-        const int row = (int)fdiv((unsigned)pos, a.div_w);           // n * OH + oy
-        const int ox = pos - row * a.OW;
-        const int n = (int)fdiv((unsigned)row, a.div_h);
-        const int oy = row - n * a.OH;
-        const int iy = oy * a.stride + ky - a.pad, ix = ox * a.stride + kx - a.pad;
-        if (x_ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-          xv = *reinterpret_cast<const f32x4*>(a.x + ((size_t)(n * a.H + iy) * a.W + ix) * a.Cin + ci0 + c4);
-      }
-      gr[i] = gv;
-      xr[i] = xv;
-    }
-  };
-  f32x16 acc;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-  f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-  if (c_begin < c_end) load_chunk(c_begin);
-  for (int c = c_begin; c < c_end; ++c) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {                                      // channel c4 + j: its four positions, rounded, 8 bytes
-      *reinterpret_cast<uint2*>(As + (c4 + j) * ROWB + lp * 8) = make_uint2(wg_pk_f16(gr[0][j], gr[1][j]), wg_pk_f16(gr[2][j], gr[3][j]));
-      *reinterpret_cast<uint2*>(Bs + (c4 + j) * ROWB + lp * 8) = make_uint2(wg_pk_f16(xr[0][j], xr[1][j]), wg_pk_f16(xr[2][j], xr[3][j]));
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bsum += gr[i];                         // positions in ascending order, unrounded
-    __syncthreads();
-    if (c + 1 < c_end) load_chunk(c + 1);
-    const char* ap = As + (wm * 32 + r) * ROWB + kh * 16;
-    const char* bp = Bs + (wn * 32 + r) * ROWB + kh * 16;
-#pragma unroll
-    for (int s = 0; s < PK / 16; ++s) {
-      const wg_f16x8 af = __builtin_bit_cast(wg_f16x8, *reinterpret_cast<const uint4*>(ap + s * 32));
-      const wg_f16x8 bf = __builtin_bit_cast(wg_f16x8, *reinterpret_cast<const uint4*>(bp + s * 32));
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  // C/D layout: column (ci) = lane & 31, row (co) = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
-  const int Ktot = a.KH * a.KW * a.Cin;
-  float* dw = a.splits > 1 ? a.part + (size_t)blockIdx.z * a.Cout * Ktot : a.dw;
-  float* db = a.splits > 1 ? a.bpart + (size_t)blockIdx.z * a.Cout : a.db;
-  const int ci = ci0 + wn * 32 + r;
-  if (ci < a.Cin) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int co = co0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * kh;
-      if (co < a.Cout) dw[(size_t)co * Ktot + (size_t)tap * a.Cin + ci] = acc[q];
-    }
-  }
-  if (a.db && tap == 0 && (tile % ci_tiles) == 0) {
-    // db[co] = sum over the positions: the 16 loader rows' sums, added in row order
-    bred[lp][c4 + 0] = bsum.x; bred[lp][c4 + 1] = bsum.y; bred[lp][c4 + 2] = bsum.z; bred[lp][c4 + 3] = bsum.w;
-    __syncthreads();
-    if (tid < TC && co0 + tid < a.Cout) {
-      float v = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v += bred[q][tid];
-      db[co0 + tid] = v;
-    }
-  }
-}
-
-// dW / db = the partial results of the position ranges added in range order (deterministic)
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bpart, float* __restrict__ dw,
-                                                           float* __restrict__ db, size_t n, int Cout, int splits) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n + (db ? Cout : 0); i += (size_t)gridDim.x * blockDim.x) {
-    float v = 0.f;
-    if (i < n) {
-      for (int z = 0; z < splits; ++z) v += part[(size_t)z * n + i];
-      dw[i] = v;
-    } else {
-      const size_t c = i - n;
-      for (int z = 0; z < splits; ++z) v += bpart[(size_t)z * Cout + c];
-      db[c] = v;
-    }
-  }
-}
-
-// Weight gradient of a 4-channel layer whose kernel rows are wider than 8 taps (fallback; the stem, timm.py:279, takes the MFMA
-// kernel below): tap layout, packed k = (ky, kx, ci), ci < 4.  Workgroup = one tap x 16 output channels; its 16 waves take every 16th output position, lane =
-// (co, ci); the 16 partial sums are added in wave order through LDS (deterministic).  Tap 0's workgroups also write db.
-__global__ __launch_bounds__(1024) void conv_backward_weights_tap4_kernel(ConvBwdArgs a) {
-  __shared__ float part[16][64];
-  __shared__ float partb[16][16];
-  const int tap = blockIdx.x, co0 = blockIdx.y * 16;
-  const int ky = tap / a.KW, kx = tap - ky * a.KW;
-  const int t = threadIdx.x, ci = t & 3, col = (t >> 2) & 15, lane_p = t >> 6;
-  const int P = a.N * a.OH * a.OW;
-  const int pps = (P + a.splits - 1) / a.splits;
-  const int p_begin = blockIdx.z * pps, p_end = min(p_begin + pps, P);
-  float acc = 0.f, accb = 0.f;
-#pragma unroll 4
-  for (int p = p_begin + lane_p; p < p_end; p += 16) {
-    const int ox = p % a.OW, r = p / a.OW;
-    const int oy = r % a.OH, n = r / a.OH;
-    const float gv = a.g[(size_t)p * a.Cout + co0 + col];
-    accb += gv;
-    const int iy = oy * a.stride - a.pad + ky, ix = ox * a.stride - a.pad + kx;
-    if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) acc += gv * a.x[((size_t)(n * a.H + iy) * a.W + ix) * 4 + ci];
-  }
-  part[lane_p][t & 63] = acc;
-  if (ci == 0) partb[lane_p][col] = accb;
-  __syncthreads();
-  if (t < 64) {
-    float s = 0.f;
-    for (int i = 0; i < 16; ++i) s += part[i][t];
-    const int Ktot = a.KH * a.KW * 4;
-    float* dw = a.splits > 1 ? a.part + (size_t)blockIdx.z * a.Cout * Ktot : a.dw;
-    float* db = a.splits > 1 ? a.bpart + (size_t)blockIdx.z * a.Cout : a.db;
-    dw[(size_t)(co0 + col) * Ktot + tap * 4 + ci] = s;
-    if (tap == 0 && ci == 0 && a.db) {
-      float sb = 0.f;
-      for (int i = 0; i < 16; ++i) sb += partb[i][col];
-      db[co0 + col] = sb;
-    }
-  }
-}
-
-// The stem's weight gradient on the matrix cores (KW * 4 <= 32): for one kernel row ky the packed columns (kx, ci) of an output
-// position are KW * 4 CONSECUTIVE floats of the 4-channel image row, so a workgroup owns a 32 (co) x 32 (kx, ci) tile of one ky and
-// contracts over the positions exactly like conv_backward_weights_kernel (columns >= KW * 4 are computed and dropped).
-__global__ __launch_bounds__(256) void conv_backward_weights_tap4_mfma_kernel(ConvBwdArgs a) {
-  const int tile = blockIdx.x;                       // (co tile, ky)
-  const int co0 = (tile / a.KH) * 32, ky = tile % a.KH;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 31, kh = lane >> 5;
-  const int kx = col >> 2;
-  const bool col_live = kx < a.KW;
-  const int P = a.N * a.OH * a.OW;
-  const int steps = (P + 7) / 8;
-  const int sps = (steps + a.splits - 1) / a.splits;
-  const int z_begin = blockIdx.z * sps;
-  const int z_end = min(z_begin + sps, steps);
-  const int spw = (sps + 3) / 4;
-  const int s_begin = z_begin + wave * spw;
-  int s_end = s_begin + spw;
-  if (s_end > z_end) s_end = z_end;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float bsum = 0.f;
-  for (int s = s_begin; s < s_end; ++s) {
-    float av[4], bv[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int pos = s * 8 + 2 * t + kh;
-      float gv = 0.f, xv = 0.f;
-      if (pos < P) {
-        gv = a.g[(size_t)pos * a.Cout + co0 + col];
-        const int row = (int)fdiv((unsigned)pos, a.div_w);
-        const int ox = pos - row * a.OW;
-        const int n = (int)fdiv((unsigned)row, a.div_h);
-        const int oy = row - n * a.OH;
-        const int iy = oy * a.stride + ky - a.pad, ix = ox * a.stride + kx - a.pad;
-        if (col_live && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-          xv = a.x[((size_t)(n * a.H + iy) * a.W + ix) * 4 + (col & 3)];
-      }
-      av[t] = gv;
-      bv[t] = xv;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t], acc, 0, 0, 0);
-      bsum += av[t];
-    }
-  }
-  __shared__ float red[3 * 16 * 64];
-  __shared__ float bred[4 * 64];
-  bred[wave * 64 + lane] = bsum;
-  if (wave > 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[((wave - 1) * 16 + r) * 64 + lane] = acc[r];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 1; w < 4; ++w)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] += red[((w - 1) * 16 + r) * 64 + lane];
-  const int Ktot = a.KH * a.KW * 4;
-  float* dw = a.splits > 1 ? a.part + (size_t)blockIdx.z * a.Cout * Ktot : a.dw;
-  float* db = a.splits > 1 ? a.bpart + (size_t)blockIdx.z * a.Cout : a.db;
-  if (col_live) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-      dw[(size_t)co * Ktot + ky * a.KW * 4 + col] = acc[r];
-    }
-  }
-  if (a.db && ky == 0 && lane < 32) {
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v += bred[w * 64 + lane] + bred[w * 64 + 32 + lane];
-    db[co0 + lane] = v;
-  }
-}
-
-// Input gradient of a STRIDED convolution (P6 / P7, timm.py:359-364; the trunk's stride-2 layers), gather form: one workgroup per
-// input position, thread = input channel; dX[n][iy][ix][ci] = sum over the taps (ky, kx) with (iy + pad - ky) and (ix + pad - kx)
-// multiples of the stride of sum_co G[n][(iy + pad - ky) / s][(ix + pad - kx) / s][co] * W[co][(ky, kx, ci)].  Weight reads are
-// coalesced over ci, G values are broadcasts.  (Stride-1 layers use eod_conv2d with the rotated weights: matrix cores.)
-__global__ __launch_bounds__(256) void conv_backward_input_kernel(ConvBwdArgs a, const float* __restrict__ w, int Kpad, float* __restrict__ dx) {
-  const int pos = blockIdx.x;                         // (n, iy, ix)
-  const int ix = pos % a.W, t = pos / a.W;
-  const int iy = t % a.H, n = t / a.H;
-  for (int ci = threadIdx.x; ci < a.Cin; ci += blockDim.x) {
-    float acc = 0.f;
-    for (int ky = 0; ky < a.KH; ++ky) {
-      const int ny = iy + a.pad - ky;
-      if (ny < 0 || ny % a.stride != 0) continue;
-      const int oy = ny / a.stride;
-      if (oy >= a.OH) continue;
-      for (int kx = 0; kx < a.KW; ++kx) {
-        const int nx = ix + a.pad - kx;
-        if (nx < 0 || nx % a.stride != 0) continue;
-        const int ox = nx / a.stride;
-        if (ox >= a.OW) continue;
-        const float* gp = a.g + ((size_t)(n * a.OH + oy) * a.OW + ox) * a.Cout;
-        const float* wp = w + (size_t)(ky * a.KW + kx) * a.Cin + ci;
-        for (int co = 0; co < a.Cout; ++co) acc += gp[co] * wp[(size_t)co * Kpad];
-      }
-    }
-    dx[(size_t)pos * a.Cin + ci] = acc;
-  }
-}
-
 // FPN top-down add (timm.py:128-133: lateral + nearest x2 of the coarser level): the coarser level's gradient is the sum over each
 // 2x2 block of the finer level's gradient (the lateral branch gets the gradient itself).  g [N,2h,2w,C] -> out [N,h,w,C] (+= when
 // accumulate: the coarser level also has its own output-conv branch).
@@ -937,186 +305,6 @@ __global__ __launch_bounds__(256) void relu_backward_kernel(const float* __restr
 }
 
 }  // namespace
-
-static int conv_bwd_args(ConvBwdArgs& a, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride) {
-  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 31) || (Cout & 31) || KH <= 0 || KW <= 0 || KH * KW > 64 ||
-      pad < 0 || stride < 1 || H + 2 * pad < KH || W + 2 * pad < KW)
-    return EOD_ERR_BAD_DIMS;
-  if ((long)N * H * W >= (1L << 28)) return EOD_ERR_BAD_DIMS;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.pad = pad; a.stride = stride;
-  a.OH = (H + 2 * pad - KH) / stride + 1;
-  a.OW = (W + 2 * pad - KW) / stride + 1;
-  a.div_w = eod_make_fastdiv((unsigned)a.OW);
-  a.div_h = eod_make_fastdiv((unsigned)a.OH);
-  return EOD_OK;
-}
-
-// position ranges of a weight-gradient launch: enough workgroups for the chip, ranges of at least 16 steps (128 positions)
-// EOD_WGRAD_RB=0 selects the 32 x 32 kernel of round 3 (same-box A/B of the two; read once)
-static bool wgrad_register_blocked() {
-  static const bool on = [] {
-    const char* e = getenv("EOD_WGRAD_RB");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// EOD_WGRAD_LDS=0 falls back to the register-blocked kernel (same-box A/B; read once)
-static bool wgrad_lds() {
-  static const bool on = [] {
-    const char* e = getenv("EOD_WGRAD_LDS");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-static int wgrad_splits(int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride) {
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  const long P = (long)N * OH * OW;
-  const bool tap4_scalar = Cin == 4 && KW > 8;                    // wider kernel rows than a 32-column tile: the scalar kernel
-  const long wgs = Cin == 4 ? (tap4_scalar ? (long)KH * KW * (Cout >> 4) : (long)(Cout >> 5) * KH)
-                   : wgrad_register_blocked() ? (long)((Cout + 63) >> 6) * ((Cin + 63) >> 6) * KH * KW        // 64 x 64 register blocks
-                                              : (long)(Cout >> 5) * (Cin >> 5) * KH * KW;
-  long s = tap4_scalar ? 16 : (768 + wgs - 1) / wgs;
-  const long cap = tap4_scalar ? P / 2048 : (Cin != 4 && wgrad_lds() ? (P + 31) / 32 / 4 : (P + 7) / 8 / 16);
-  if (s > cap) s = cap;
-  if (s > 64) s = 64;
-  return s < 1 ? 1 : (int)s;
-}
-
-extern "C" size_t eod_conv2d_backward_weights_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride) {
-  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || pad < 0 || stride < 1) return 0;
-  stride &= ~EOD_WGRAD_F16;                    // the f16 kernel cuts the positions like the fp32 one
-  if (stride < 1) return 0;
-  const int s = wgrad_splits(N, H, W, Cin, Cout, KH, KW, pad, stride);
-  return s > 1 ? (size_t)s * ((size_t)Cout * KH * KW * Cin + Cout) * sizeof(float) : 0;
-}
-
-static int conv2d_backward_weights_impl(const float* x, const float* g, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad,
-                                        int stride, float* dw, float* db, void* workspace, size_t workspace_bytes, eod_stream_t stream) {
-  if (!x || !g || !dw) return EOD_ERR_NULL;
-  // EOD_WGRAD_F16 on the stride argument: the f16 kernel (32-multiple channel counts; the 4-channel stem has no f16 form)
-  const bool f16 = stride > 0 && (stride & EOD_WGRAD_F16) != 0;
-  if (stride > 0) stride &= ~EOD_WGRAD_F16;
-  if (f16 && Cin == 4) return EOD_ERR_BAD_DIMS;
-  if (f16 && (!eod_aligned16(x) || !eod_aligned16(g))) return EOD_ERR_ALIGN;
-  ConvBwdArgs a{};
-  const int st = conv_bwd_args(a, N, H, W, Cin == 4 ? 32 : Cin, Cout, KH, KW, pad, stride);     // Cin == 4: the stem's tap layout
-  if (st != EOD_OK) return st;
-  a.Cin = Cin;
-  a.x = x; a.g = g; a.dw = dw; a.db = db;
-  a.splits = 1;
-  const size_t n = (size_t)Cout * KH * KW * Cin;
-  if (workspace) {
-    const size_t need = eod_conv2d_backward_weights_workspace_bytes(N, H, W, Cin, Cout, KH, KW, pad, stride);
-    if (need > workspace_bytes) return EOD_ERR_CAPACITY;
-    if (need) {
-      a.splits = wgrad_splits(N, H, W, Cin, Cout, KH, KW, pad, stride);
-      a.part = static_cast<float*>(workspace);
-      a.bpart = a.part + (size_t)a.splits * n;
-    }
-  }
-  if (f16)
-    hipLaunchKernelGGL(conv_backward_weights_f16_kernel, dim3(((Cout + 63) >> 6) * ((Cin + 63) >> 6), KH * KW, a.splits), dim3(256), 0,
-                       (hipStream_t)stream, a);
-  else if (Cin == 4 && KW <= 8)
-    hipLaunchKernelGGL(conv_backward_weights_tap4_mfma_kernel, dim3((Cout >> 5) * KH, 1, a.splits), dim3(256), 0, (hipStream_t)stream, a);
-  else if (Cin == 4)
-    hipLaunchKernelGGL(conv_backward_weights_tap4_kernel, dim3(KH * KW, Cout >> 4, a.splits), dim3(1024), 0, (hipStream_t)stream, a);
-  else if (wgrad_lds())
-    hipLaunchKernelGGL(conv_backward_weights_lds_kernel<false>, dim3(((Cout + 63) >> 6) * ((Cin + 63) >> 6), KH * KW, a.splits), dim3(256), 0,
-                       (hipStream_t)stream, a);
-  else if (wgrad_register_blocked())
-    hipLaunchKernelGGL(conv_backward_weights_rb_kernel, dim3(((Cout + 63) >> 6) * ((Cin + 63) >> 6), KH * KW, a.splits), dim3(256), 0,
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(conv_backward_weights_kernel, dim3((Cout >> 5) * (Cin >> 5), KH * KW, a.splits), dim3(256), 0, (hipStream_t)stream, a);
-  if (a.splits > 1) {
-    size_t blocks = (n + Cout + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a.part, a.bpart, dw, db, n, Cout, a.splits);
-  }
-  return eod_launch_status();
-}
-
-extern "C" int eod_conv2d_backward_weights(const float* x, const float* g, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad,
-                                           int stride, float* dw, float* db, eod_stream_t stream) {
-  return conv2d_backward_weights_impl(x, g, N, H, W, Cin, Cout, KH, KW, pad, stride, dw, db, nullptr, 0, stream);
-}
-
-extern "C" int eod_conv2d_backward_weights_ws(const float* x, const float* g, int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                                              int pad, int stride, float* dw, float* db, void* workspace, size_t workspace_bytes,
-                                              eod_stream_t stream) {
-  if (workspace_bytes && !workspace) return EOD_ERR_NULL;
-  return conv2d_backward_weights_impl(x, g, N, H, W, Cin, Cout, KH, KW, pad, stride, dw, db, workspace, workspace_bytes, stream);
-}
-
-// Pyramid mode: one launch for a level-shared layer (CenterNet tower / head, centernet_head.py:141-161) over all levels' rows.
-static int wgrad_levels_splits(long rows, int Cin, int Cout, int KH, int KW) {
-  const long wgs = (long)((Cout + 63) >> 6) * ((Cin + 63) >> 6) * KH * KW;
-  long s = (768 + wgs - 1) / wgs;
-  const long cap = (rows + 31) / 32 / 4;
-  if (s > cap) s = cap;
-  if (s > 64) s = 64;
-  return s < 1 ? 1 : (int)s;
-}
-
-extern "C" size_t eod_conv2d_backward_weights_levels_workspace_bytes(int rows, int Cin, int Cout, int KH, int KW) {
-  if (rows <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return 0;
-  const int s = wgrad_levels_splits(rows, Cin, Cout, KH, KW);
-  return s > 1 ? (size_t)s * ((size_t)Cout * KH * KW * Cin + Cout) * sizeof(float) : 0;
-}
-
-extern "C" int eod_conv2d_backward_weights_levels(const float* x, const float* g, int levels, const int32_t* level_off,
-                                                  const int32_t* level_h, const int32_t* level_w, int Cin, int Cout, int KH, int KW, int pad,
-                                                  float* dw, float* db, void* workspace, size_t workspace_bytes, eod_stream_t stream) {
-  if (!x || !g || !dw || !level_off || !level_h || !level_w) return EOD_ERR_NULL;
-  if (levels < 1 || levels > WGRAD_MAX_LEVELS || Cin <= 0 || Cout <= 0 || (Cin & 31) || (Cout & 31) || KH <= 0 || KW <= 0 || KH != KW ||
-      pad * 2 != KH - 1 || level_off[0] != 0)
-    return EOD_ERR_BAD_DIMS;
-  for (int l = 0; l < levels; ++l)
-    if (level_h[l] <= 0 || level_w[l] <= 0 || level_off[l + 1] - level_off[l] != level_h[l] * level_w[l]) return EOD_ERR_BAD_DIMS;
-  if (workspace_bytes && !workspace) return EOD_ERR_NULL;
-  if (!eod_aligned16(x) || !eod_aligned16(g) || !eod_aligned16(dw)) return EOD_ERR_ALIGN;
-  ConvBwdArgs a{};
-  a.x = x; a.g = g; a.dw = dw; a.db = db;
-  a.N = 1; a.H = a.OH = level_h[0]; a.W = a.OW = level_w[0];
-  a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.pad = pad; a.stride = 1;
-  a.nlv = levels;
-  for (int l = 0; l < levels; ++l) {
-    a.lv_off[l] = level_off[l]; a.lv_h[l] = level_h[l]; a.lv_w[l] = level_w[l];
-  }
-  a.lv_off[levels] = level_off[levels];
-  a.splits = 1;
-  const size_t n = (size_t)Cout * KH * KW * Cin;
-  const size_t need = eod_conv2d_backward_weights_levels_workspace_bytes(level_off[levels], Cin, Cout, KH, KW);
-  if (workspace && need) {
-    if (need > workspace_bytes) return EOD_ERR_CAPACITY;
-    a.splits = wgrad_levels_splits(level_off[levels], Cin, Cout, KH, KW);
-    a.part = static_cast<float*>(workspace);
-    a.bpart = a.part + (size_t)a.splits * n;
-  }
-  hipLaunchKernelGGL(conv_backward_weights_lds_kernel<true>, dim3(((Cout + 63) >> 6) * ((Cin + 63) >> 6), KH * KW, a.splits), dim3(256), 0,
-                     (hipStream_t)stream, a);
-  if (a.splits > 1) {
-    size_t blocks = (n + Cout + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a.part, a.bpart, dw, db, n, Cout, a.splits);
-  }
-  return eod_launch_status();
-}
-
-extern "C" int eod_conv2d_backward_input(const float* g, const float* w, int Kpad, int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                                         int pad, int stride, float* dx, eod_stream_t stream) {
-  if (!g || !w || !dx) return EOD_ERR_NULL;
-  ConvBwdArgs a{};
-  const int st = conv_bwd_args(a, N, H, W, Cin, Cout, KH, KW, pad, stride);
-  if (st != EOD_OK) return st;
-  if (Kpad < KH * KW * Cin) return EOD_ERR_BAD_DIMS;
-  a.g = g;
-  hipLaunchKernelGGL(conv_backward_input_kernel, dim3(N * H * W), dim3(256), 0, (hipStream_t)stream, a, w, Kpad, dx);
-  return eod_launch_status();
-}
 
 extern "C" int eod_upsample2_sum_backward(const float* g, float* out, int N, int h, int w, int C, int accumulate, eod_stream_t stream) {
   if (!g || !out) return EOD_ERR_NULL;
@@ -1325,7 +513,7 @@ extern "C" int eod_adamw_step_multi(const EodAdamWTensor* tensors, int count, do
 
 #define PROJ_WGRAD_SPLITS 8
 extern "C" size_t eod_memory_project_backward_weights_workspace_bytes(void) {
-  return (size_t)3 * PROJ_WGRAD_SPLITS * (256 * 512 + 256) * sizeof(float);
+  return wgrad_workspace_bytes(PROJ_WGRAD_SPLITS, 3, 256 * 512, 256);
 }
 
 static int memory_project_backward_weights_impl(const float* g3, const float* g4, const float* g5, const uint16_t* pooled_f16, int H,
@@ -1363,19 +551,9 @@ static int memory_project_backward_weights_impl(const float* g3, const float* g4
     base += (a.rows[l] + 31) / 32;
   }
   a.weight = weight;
-  a.splits = 1;
-  if (workspace) {
-    a.splits = PROJ_WGRAD_SPLITS;
-    a.part = static_cast<float*>(workspace);
-    a.bpart = a.part + (size_t)3 * PROJ_WGRAD_SPLITS * 256 * 512;
-  }
-  hipLaunchKernelGGL(proj_backward_weights_kernel, dim3(128, 3, a.splits), dim3(256), 0, (hipStream_t)stream, a);
-  if (a.splits > 1) {
-    for (int l = 0; l < 3; ++l)
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(513), dim3(256), 0, (hipStream_t)stream, a.part + (size_t)l * a.splits * 256 * 512,
-                         a.bpart + (size_t)l * a.splits * 256, a.dw[l], a.db[l], (size_t)256 * 512, 256, a.splits);
-  }
-  return eod_launch_status();
+  return wgrad_launch_ranges(a, PROJ_WGRAD_SPLITS, workspace, workspace_bytes, 3, 256 * 512, 256, a.dw, a.db, (hipStream_t)stream, [&] {
+    hipLaunchKernelGGL(proj_backward_weights_kernel, dim3(128, 3, a.splits), dim3(256), 0, (hipStream_t)stream, a);
+  });
 }
 
 extern "C" int eod_memory_pool_backward(const float* dec3, const float* dec4, const float* dec5, int H, int W, uint16_t* ge3_f16,

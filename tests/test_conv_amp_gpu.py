@@ -1,11 +1,14 @@
 """The f16 arithmetic of the AMP training step, launch by launch (-m gpu): every input-gradient and weight-gradient launch the
 backbone's backward really makes (recorded from one `AmpTrainer` step at 640x640 and from a two-frame trunk batch) against fp64 on
 the half-rounded operands and on the unrounded ones, the planner's choice per layer, run-to-run bitwise weight gradients over the
-position splits, and IEEE behaviour beyond half's range together with the found-inf pass."""
+position splits, the edges of the f16 weight-gradient kernel's index arithmetic (chunks of 64 positions, empty ranges, half-filled
+channel tiles, image boundaries inside a chunk), and IEEE behaviour beyond half's range together with the found-inf pass."""
 import math
 
 import pytest
 import torch
+
+from _conv_cases import exact_hw
 
 pytestmark = pytest.mark.gpu
 
@@ -203,3 +206,119 @@ def test_overflow_is_not_clamped_and_the_found_inf_pass_sees_it():
     many[67][32] = float("nan")
     opt.nonfinite(many, flag)
     assert int(flag.cpu()[0]) == 1
+
+
+# ------------------------------------------------------------------------------------------------
+# edges of the f16 weight-gradient kernel: the fp32 LDS-tiled kernel's frame with chunks of 64 positions
+# (tests/test_conv_backward_plans_gpu.py holds the fp32 twins)
+# ------------------------------------------------------------------------------------------------
+def _f16_split(shape):
+    """(chunks of 64 positions, ranges, chunks per range) of an f16 weight-gradient launch; the ranges from the workspace size the
+    library asks for."""
+    from embodied_object_detection_amd import _lib, ops
+    N, H, W, Cin, Cout, K, stride, pad = shape
+    need = _lib.load().eod_conv2d_backward_weights_workspace_bytes(N, H, W, Cin, Cout, K, K, pad, stride | ops.WGRAD_F16)
+    assert need % ((Cout * K * K * Cin + Cout) * 4) == 0
+    ranges = need // ((Cout * K * K * Cin + Cout) * 4) if need else 1
+    P = N * ((H + 2 * pad - K) // stride + 1) * ((W + 2 * pad - K) // stride + 1)
+    chunks = -(-P // 64)
+    return chunks, ranges, -(-chunks // ranges)
+
+
+def _poison(shape, dev):
+    """NaN in the workspace and in the blocks the caching allocator hands out next for dW / db: a range or an element that is not
+    written shows as NaN in the result (a stale value of the previous, identical run would not show)."""
+    from embodied_object_detection_amd import ops
+    _N, _H, _W, Cin, Cout, K, _s, _p = shape
+    ws = ops.ConvBackward._workspace.get(dev)
+    if ws is not None:
+        ws.fill_(float("nan"))
+    junk = [torch.full((Cout, K * K * Cin), float("nan"), device=dev), torch.full((Cout,), float("nan"), device=dev)]
+    del junk
+
+
+def _f16_edges(tag, shapes, seed0):
+    """Every shape twice with another layer's call in between (the shared workspace): bitwise equal, fully written, dW within
+    n_w * 2^-24 * conv(|a|, |b|) of fp64 on the half-rounded operands and within (2^-10 + 2^-22 + n_w * 2^-24) * conv(|a|, |b|) of
+    fp64 on the unrounded ones, db = the fp64 sum of the unrounded gradient."""
+    from embodied_object_detection_amd import ops
+    dev = torch.device("cuda:0")
+    half = lambda t: t.half().double()
+    other = ops.ConvBackward(ops.Conv(torch.randn((64, 64, 1, 1)), None, device=dev, name="o"), math="f16")
+    ox, og = torch.randn((1, 17, 19, 64), device=dev), torch.randn((1, 17, 19, 64), device=dev)
+    bad = []
+    for i, shape in enumerate(shapes):
+        N, H, W, Cin, Cout, K, stride, pad = shape
+        gen = torch.Generator().manual_seed(seed0 + i)
+        w = torch.randn((Cout, Cin, K, K), generator=gen) / math.sqrt(Cin * K * K)
+        conv = ops.Conv(w, torch.zeros(Cout), stride=stride, pad=pad, device=dev, name=f"{tag} {shape}")
+        OH, OW = conv.out_hw(H, W)
+        x = torch.relu(torch.randn((N, H, W, Cin), generator=gen))
+        g = torch.randn((N, OH, OW, Cout), generator=gen)
+        xd, gd = x.to(dev), g.to(dev)
+        bw = ops.ConvBackward(conv, math="f16")
+        bw(xd, None, gd, need_dx=False)                             # sizes the shared workspace for this layer
+        _poison(shape, dev)
+        a = bw(xd, None, gd, need_dx=False)
+        a = {k: a[k].clone() for k in ("dw", "db")}
+        other(ox, None, og, need_dx=False)
+        _poison(shape, dev)
+        b = bw(xd, None, gd, need_dx=False)
+        _, dwr, _ = _reference(half(x), half(g), half(w), stride, pad, False)
+        _, dwu, db64 = _reference(x, g, w, stride, pad, False)
+        _, dwa, _ = _reference(half(x).abs(), half(g).abs(), half(w).abs(), stride, pad, False)
+        n_w = N * OH * OW
+        dw, db = b["dw"].cpu().double(), b["db"].cpu().double()
+        e_r = float(((dw - dwr).abs() / (n_w * U32 * dwa + 1e-30)).max())
+        e_u = float(((dw - dwu).abs() / ((2.0 ** -10 + 2.0 ** -22 + n_w * U32) * dwa * 1.001 + 1e-30)).max())
+        print(f"{tag} {shape}: split {_f16_split(shape)}, fractions of the bounds: rounded {e_r:.4f}, unrounded {e_u:.4f}")
+        if not (torch.equal(a["dw"], b["dw"]) and torch.equal(a["db"], b["db"])):
+            bad.append(f"{shape}: two runs differ")
+        if not (bool(torch.isfinite(dw).all()) and bool(torch.isfinite(db).all())):
+            bad.append(f"{shape}: dW / db not fully written")
+        if not bool(((dw - dwr).abs() <= n_w * U32 * dwa + 1e-30).all()):
+            bad.append(f"{shape}: dW vs rounded operands, {e_r:.3f} of the bound")
+        if not bool(((dw - dwu).abs() <= (2.0 ** -10 + 2.0 ** -22 + n_w * U32) * dwa * 1.001 + 1e-30).all()):
+            bad.append(f"{shape}: dW vs unrounded operands, {e_u:.3f} of the bound")
+        if not torch.allclose(db, db64, rtol=1e-4, atol=1e-4 * float(db64.abs().max())):
+            bad.append(f"{shape}: db")
+    assert not bad, "\n".join(bad)
+
+
+def test_f16_position_counts_around_a_chunk_multiple():
+    """P = 64 k - 1, 64 k, 64 k + 1 (the last chunk holds 63, 64, 1 positions), one range and several."""
+    shapes = []
+    for P in (63, 64, 65, 64 * 20 - 1, 64 * 20, 64 * 20 + 1):
+        h, w = exact_hw(P)
+        shapes.append((1, h, w, 64, 64, 3, 1, 1) if h > 1 else (1, h, w, 64, 64, 1, 1, 0))
+    assert [_f16_split(s)[1] for s in shapes[:3]] == [1, 1, 1]
+    # 64 x 64 channels are one tile per tap: 768 workgroups want 86 ranges (3 x 3) or 64 (1 x 1); a quarter of the 40 / 41 chunks of 32
+    # positions caps them at 10
+    assert [_f16_split(s)[1] for s in shapes[3:]] == [10, 10, 10]
+    _f16_edges("P around 64 k", shapes, 7000)
+
+
+def test_f16_empty_last_ranges_add_zeros():
+    """64 ranges over 130 chunks of 64 positions are 3 chunks per range: ranges 44 .. 63 are EMPTY and must contribute exact zeros to
+    the reduce (the workspace holds NaN before each run)."""
+    shapes = [(1, 65, 128, 64, 64, 1, 1, 0), (1, 52, 160, 32, 32, 3, 1, 1)]
+    for s in shapes:
+        chunks, ranges, cps = _f16_split(s)
+        assert (chunks, ranges, cps) == (130, 64, 3) and -(-chunks // cps) == 44, (s, chunks, ranges, cps)
+    _f16_edges("empty ranges", shapes, 7100)
+
+
+def test_f16_half_filled_channel_tiles():
+    """Cin / Cout of 32, 96 and 160: the 64 x 64 tile's second half is switched off on one or both sides (`g_ok` / `x_ok`, the
+    guarded stores), db written by one tile column only."""
+    shapes = [(1, 21, 27, ci, co, k, 1, k // 2) for ci, co, k in ((32, 32, 3), (96, 96, 1), (160, 160, 3), (64, 32, 3), (32, 96, 3), (160, 32, 1))]
+    _f16_edges("half tiles", shapes, 7200)
+
+
+def test_f16_image_boundaries_inside_a_chunk():
+    """N = 2 and 3 with OH * OW not a multiple of 64: a chunk of 64 positions -- and a loader thread's four consecutive ones -- holds
+    the end of one image and the start of the next, whose border taps must not read across."""
+    shapes = [(2, 13, 9, 64, 64, 3, 1, 1), (3, 7, 11, 96, 64, 3, 1, 1), (3, 13, 15, 64, 128, 3, 2, 1), (2, 9, 7, 32, 64, 5, 1, 2)]
+    for N, H, W, _ci, _co, K, stride, pad in shapes:
+        assert (((H + 2 * pad - K) // stride + 1) * ((W + 2 * pad - K) // stride + 1)) % 64
+    _f16_edges("image boundaries", shapes, 7300)
