@@ -98,10 +98,113 @@ __device__ void block_sort_desc_reg(u64 (&v)[E], u64* xch) {
   }
 }
 
-__device__ __forceinline__ int next_pow2(int n) {
-  int p = 64;
-  while (p < n) p <<= 1;
-  return p;
+// sort the n keys of `buf` (n <= 1024 E) descending and leave them there in sorted order
+template <int E>
+__device__ __forceinline__ void sort_in_place(u64* buf, int n) {
+  u64 v[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int i = threadIdx.x * E + e;
+    v[e] = i < n ? buf[i] : 0ull;
+  }
+  __syncthreads();                     // every thread holds its keys: the buffer becomes the sort's exchange buffer
+  block_sort_desc_reg<E>(v, buf);
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int q = threadIdx.x * E + e;
+    if (q < n) buf[q] = v[e];
+  }
+  __syncthreads();
+}
+
+// ... with the smallest network that holds them (n <= 1024 EMAX, EMAX = 4 or 8)
+template <int EMAX>
+__device__ __forceinline__ void block_sort_keys(u64* buf, int n) {
+  static_assert(EMAX == 4 || EMAX == 8, "the callers' buffers hold 4096 or 8192 keys");
+  if (n <= 1024) sort_in_place<1>(buf, n);
+  else if (n <= 2048) sort_in_place<2>(buf, n);
+  else if (EMAX == 4 || n <= 4096) sort_in_place<4>(buf, n);
+  else sort_in_place<EMAX>(buf, n);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Steps the selection kernels share.  None of them declares LDS: the kernel owns every array and passes pointers.  The ones that
+// contain a barrier (block_*, and det_write_outputs further down) are called by ALL threads of the workgroup, from workgroup-uniform
+// control flow only; a wave_* step by all lanes of a wave.
+// ------------------------------------------------------------------------------------------------------
+// The 4096 bins of the score histograms are 2^14-wide ranges of the float bit pattern from 2^-7 up: a monotone function of the score.
+__device__ __forceinline__ int score_bin(unsigned bits) {
+  int bin = (int)(bits >> 14) - (int)(0x3C000000u >> 14);
+  return bin < 0 ? 0 : (bin > 4095 ? 4095 : bin);
+}
+
+// Workgroup suffix sum over 4096 bins, BPT consecutive bins per thread: h[] are the counts of bins BPT t .. BPT t + BPT - 1 in the
+// first 4096 / BPT threads and zero in the others.  Returns the number of candidates in the bins ABOVE this thread's; wsum[w]
+// (4096 / BPT / 64 entries) is left holding the total of wave w's bins.
+template <int BPT>
+__device__ __forceinline__ int block_bins_above(const int (&h)[BPT], int* wsum) {
+  constexpr int WAVES = 4096 / BPT / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int mine = 0;
+#pragma unroll
+  for (int j = 0; j < BPT; ++j) mine += h[j];
+  int inc = mine;                                    // inclusive suffix inside the wave (towards higher lanes)
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_down(inc, off, 64);
+    if (lane + off < 64) inc += t;
+  }
+  if (lane == 0 && wave < WAVES) wsum[wave] = inc;
+  __syncthreads();
+  int after = 0;                                     // candidates in the bins of higher threads' waves
+  for (int w = wave + 1; w < WAVES; ++w) after += wsum[w];
+  return after + inc - mine;
+}
+
+// The lowest bin of hist[4096] whose suffix reaches `want` (0 when want is 0), through *sh_cut, which the kernel has zeroed before
+// its last barrier.  1024 threads, thread t owns bins 4 t .. 4 t + 3.
+__device__ __forceinline__ int block_hist_cut(const int* hist, int want, int* wsum, int* sh_cut) {
+  const int tid = threadIdx.x;
+  const int h[4] = {hist[4 * tid], hist[4 * tid + 1], hist[4 * tid + 2], hist[4 * tid + 3]};
+  const int above = block_bins_above<4>(h, wsum);
+  // exactly one thread finds it
+  const int s3 = above + h[3], s2 = s3 + h[2], s1 = s2 + h[1], s0 = s1 + h[0];
+  if (want > 0) {
+    if (above < want && s3 >= want) *sh_cut = 4 * tid + 3;
+    else if (s3 < want && s2 >= want) *sh_cut = 4 * tid + 2;
+    else if (s2 < want && s1 >= want) *sh_cut = 4 * tid + 1;
+    else if (s1 < want && s0 >= want) *sh_cut = 4 * tid;
+  }
+  __syncthreads();
+  return *sh_cut;
+}
+
+// Greedy NMS inside a chunk of 64 boxes, by one wave: lane i holds word i of the chunk's diagonal block (bit c: box c > i is suppressed
+// by box i), `removed` the boxes earlier chunks suppressed.  Returns the kept boxes of the first `lim`.
+__device__ __forceinline__ u64 wave_resolve_diag(u64 diag, u64 removed, int lim) {
+  u64 kept = 0;
+  for (int i = 0; i < lim; ++i) {
+    // i is wave-uniform: v_readlane into scalar registers instead of an LDS-crossbar shuffle per step
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(diag & 0xFFFFFFFFull), i);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(diag >> 32), i);
+    if (!((removed >> i) & 1ull)) {
+      kept |= 1ull << i;
+      removed |= ((u64)hi << 32) | lo;
+    }
+  }
+  return kept;
+}
+
+// Ballot compaction, one key per thread and call: the keys with `in` are appended to the LDS list `buf` through its counter *sh_n
+// (one atomic per wave; the order of the list is not defined, it is sorted next).  Every lane of the wave calls it; no barrier inside.
+__device__ __forceinline__ void wave_compact_key(bool in, u64 key, int* sh_n, u64* buf) {
+  const int lane = threadIdx.x & 63;
+  const u64 bal = __ballot(in);
+  int base = 0;
+  if (lane == 0 && bal) base = atomicAdd(sh_n, __popcll(bal));
+  base = __shfl(base, 0, 64);
+  if (in) buf[base + __popcll(bal & ((1ull << lane) - 1ull))] = key;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -145,17 +248,13 @@ __device__ __forceinline__ ScanOut scene_outputs(ScanOut o, int b) {
 
 struct NmsSmem {
   float kb[NMS_KEPT_MAX * 4];   // kept boxes, in keep order
-  int kl[NMS_KEPT_MAX];         // their labels
   int kidx[NMS_KEPT_MAX];       // their position in the sorted list
   float cb[64 * 4];             // the chunk's boxes
   float cs[64];                 // the chunk's scores (the tie rule of the last chunks reads them one by one)
-  int cl[64];
   u64 diag[64];                 // bit c of word i: chunk box c (c > i) is suppressed by chunk box i
   u64 supp;                     // bit i: chunk box i is suppressed by a box kept in an earlier chunk
   int total, stop;
   float kth;
-  int flag[NMS_KEPT_MAX];       // unique rows
-  int wcnt[8];
 };
 
 __device__ __forceinline__ bool iou_over(float x1, float y1, float x2, float y2, float area_i, float a1, float b1, float a2, float b2,
@@ -168,12 +267,12 @@ __device__ __forceinline__ bool iou_over(float x1, float y1, float x2, float y2,
   return iou > thr;
 }
 
-// Greedy NMS over the first n entries of a score-sorted list (boxes / scores / labels / rows in global memory, written by this
-// workgroup before the call) + gather of the kept entries.  keep_ties: keep every kept box whose score equals the score of kept
-// box #max_keep (centernet.py:733-741, ">= kth"), else truncate at max_keep.  Block = 1024 threads.
-__device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* __restrict__ scores, const int* __restrict__ labels,
-                                 const int* __restrict__ rows, int n, float thr, int max_keep, int keep_ties, const ScanOut& o,
-                                 NmsSmem* S) {
+// Class-agnostic greedy NMS over the first n entries of a score-sorted list (boxes / scores in global memory, written by this
+// workgroup before the call) + gather of the kept entries (boxes, scores, count).  Every kept box whose score equals the score of
+// kept box #max_keep is kept too (centernet.py:733-741, ">= kth").  Returns whether the walk ended by that rule (and not because the
+// list ran out).  Block = 1024 threads.
+__device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* __restrict__ scores, int n, float thr, int max_keep,
+                                 const ScanOut& o, NmsSmem* S) {
   const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6;
   if (tid == 0) {
     S->total = 0;
@@ -182,16 +281,14 @@ __device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* _
   }
   __syncthreads();
   const int nchunk = (n + 63) >> 6;
-  // wave 0 holds the NEXT chunk's boxes / scores / labels in registers: its global loads are issued a whole chunk ahead instead of
+  // wave 0 holds the NEXT chunk's boxes / scores in registers: its global loads are issued a whole chunk ahead instead of
   // at the top of the chunk that needs them (one L2 round trip per chunk off the serial path)
   float nb0 = 0.f, nb1 = 0.f, nb2 = 0.f, nb3 = 0.f, nsc = 0.f;
-  int nlb = 0;
   auto fetch = [&](int c) {
     const int j = c * 64 + tid;
     if (tid < 64 && j < n) {
       nb0 = boxes[j * 4 + 0]; nb1 = boxes[j * 4 + 1]; nb2 = boxes[j * 4 + 2]; nb3 = boxes[j * 4 + 3];
       nsc = scores[j];
-      nlb = labels ? labels[j] : 0;
     }
   };
   fetch(0);
@@ -203,7 +300,6 @@ __device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* _
         S->cb[tid * 4 + 1] = nb1;
         S->cb[tid * 4 + 2] = nb2;
         S->cb[tid * 4 + 3] = nb3;
-        S->cl[tid] = nlb;
         S->cs[tid] = nsc;
       }
       S->diag[tid] = 0;
@@ -215,16 +311,13 @@ __device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* _
     const int nk = total0 < NMS_KEPT_MAX ? total0 : NMS_KEPT_MAX;
     const bool valid = lane < lim;
     float a1 = 0.f, b1 = 0.f, a2 = 0.f, b2 = 0.f;
-    int lj = 0;
     if (valid) {
       a1 = S->cb[lane * 4 + 0]; b1 = S->cb[lane * 4 + 1]; a2 = S->cb[lane * 4 + 2]; b2 = S->cb[lane * 4 + 3];
-      lj = S->cl[lane];
     }
     // (A) against the boxes kept in earlier chunks: wave `grp` takes kept boxes grp, grp + 16, ...
     bool sup = false;
     if (valid) {
       for (int j = grp; j < nk; j += 16) {
-        if (S->kl[j] != lj) continue;
         const float x1 = S->kb[j * 4 + 0], y1 = S->kb[j * 4 + 1], x2 = S->kb[j * 4 + 2], y2 = S->kb[j * 4 + 3];
         const float area_i = (x2 - x1) * (y2 - y1);
         if (iou_over(x1, y1, x2, y2, area_i, a1, b1, a2, b2, thr)) {
@@ -242,7 +335,7 @@ __device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* _
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c2 = grp * 4 + q;
-        if (c2 > lane && c2 < lim && S->cl[c2] == lj) {
+        if (c2 > lane && c2 < lim) {
           if (iou_over(a1, b1, a2, b2, area_i, S->cb[c2 * 4 + 0], S->cb[c2 * 4 + 1], S->cb[c2 * 4 + 2], S->cb[c2 * 4 + 3], thr))
             bits |= 1ull << c2;
         }
@@ -251,18 +344,7 @@ __device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* _
     }
     __syncthreads();
     if (tid < 64) {
-      const u64 diag = S->diag[tid];
-      u64 cur = S->supp;
-      u64 kept = 0;
-      for (int i = 0; i < lim; ++i) {
-        // i is wave-uniform: v_readlane into scalar registers instead of an LDS-crossbar shuffle per step
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(diag & 0xFFFFFFFFull), i);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(diag >> 32), i);
-        if (!((cur >> i) & 1ull)) {
-          kept |= (1ull << i);
-          cur |= ((u64)hi << 32) | lo;
-        }
-      }
+      const u64 kept = wave_resolve_diag(S->diag[tid], S->supp, lim);
       const int nkept = __popcll(kept);
       if (total0 + nkept < max_keep) {
         // fast path (every chunk but the last one): all lanes append their kept box in parallel
@@ -270,47 +352,38 @@ __device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* _
           const int pos = total0 + __popcll(kept & ((1ull << tid) - 1ull));
           if (pos < NMS_KEPT_MAX) {
             S->kb[pos * 4 + 0] = a1; S->kb[pos * 4 + 1] = b1; S->kb[pos * 4 + 2] = a2; S->kb[pos * 4 + 3] = b2;
-            S->kl[pos] = lj;
             S->kidx[pos] = c * 64 + tid;
           }
         }
         if (tid == 0) S->total = total0 + nkept;
       } else if (tid == 0) {
-        // append kept boxes one by one, honouring max_keep / ties
+        // append kept boxes one by one, honouring max_keep and the ties
         int total = total0;
         int stop = 0;
         float kth = S->kth;
         for (int i = 0; i < lim; ++i) {
           if (!((kept >> i) & 1ull)) continue;
           const int idx = c * 64 + i;
-          bool take = false;
-          if (total < max_keep) {
-            take = true;
-          } else if (keep_ties && S->cs[i] >= kth) {
-            take = true;
-          } else {
-            // boxes after this one have lower-or-equal score; with ties they may still be equal only if scores[idx] >= kth,
-            // which failed -> everything later is strictly lower: stop
+          if (total >= max_keep && !(S->cs[i] >= kth)) {
+            // boxes after this one have lower-or-equal score; they may still be equal only if scores[idx] >= kth, which failed ->
+            // everything later is strictly lower: stop
             stop = 1;
             break;
           }
-          if (take) {
-            if (total < NMS_KEPT_MAX) {
-              S->kb[total * 4 + 0] = S->cb[i * 4 + 0]; S->kb[total * 4 + 1] = S->cb[i * 4 + 1];
-              S->kb[total * 4 + 2] = S->cb[i * 4 + 2]; S->kb[total * 4 + 3] = S->cb[i * 4 + 3];
-              S->kl[total] = S->cl[i];
-              S->kidx[total] = idx;
-            }
-            ++total;
-            if (total == max_keep) kth = S->cs[i];
+          if (total < NMS_KEPT_MAX) {
+            S->kb[total * 4 + 0] = S->cb[i * 4 + 0]; S->kb[total * 4 + 1] = S->cb[i * 4 + 1];
+            S->kb[total * 4 + 2] = S->cb[i * 4 + 2]; S->kb[total * 4 + 3] = S->cb[i * 4 + 3];
+            S->kidx[total] = idx;
           }
+          ++total;
+          if (total == max_keep) kth = S->cs[i];
         }
         S->total = total;
         S->kth = kth;
         // if the list is full and the next chunk starts below kth, stop
         if (!stop && total >= max_keep) {
           const int nxt = (c + 1) * 64;
-          if (!keep_ties || nxt >= n || scores[nxt] < kth) stop = 1;
+          if (nxt >= n || scores[nxt] < kth) stop = 1;
         }
         S->stop = stop;
       }
@@ -337,99 +410,9 @@ __device__ bool block_greedy_nms(const float* __restrict__ boxes, const float* _
       o.out_boxes[r * 4 + 3] = S->kb[r * 4 + 3];
     }
     if (o.out_scores) o.out_scores[r] = scores[idx];
-    if (o.out_labels) o.out_labels[r] = S->kl[r];
-    if (o.out_rows) o.out_rows[r] = rows ? rows[idx] : idx;
-  }
-  if (o.rep_of && rows) {
-    // entries of one source row carry the same box: the first of them represents the group (the mask head is class agnostic)
-    if (tid < NMS_KEPT_MAX) S->flag[tid] = 0x7FFFFFFF;
-    __syncthreads();
-    int my_row = -1;
-    if (tid < total) {
-      my_row = rows[S->kidx[tid]];
-      if (my_row >= 0 && my_row < NMS_KEPT_MAX) atomicMin(&S->flag[my_row], tid);
-    }
-    __syncthreads();
-    int is_rep = 0;
-    if (tid < total) {
-      const int rep = (my_row >= 0 && my_row < NMS_KEPT_MAX) ? S->flag[my_row] : tid;
-      o.rep_of[tid] = rep;
-      is_rep = rep == tid;
-    }
-    u64 rb = 0;
-    if (tid < NMS_KEPT_MAX) {
-      rb = __ballot(is_rep != 0);
-      if (lane == 0) S->wcnt[grp] = __popcll(rb);
-    }
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
-      const int cw = S->wcnt[w];
-      if (w < grp) before += cw;
-      all += cw;
-    }
-    if (tid < NMS_KEPT_MAX && is_rep) o.rep_list[before + __popcll(rb & ((1ull << lane) - 1ull))] = tid;
-    if (tid == 0) *o.rep_count = all;
-    __syncthreads();
-  }
-  if (o.uniq_rows) {
-    // torch.unique of the kept rows: flags over the row ids (< NMS_KEPT_MAX), ballot compaction, ascending
-    if (tid < NMS_KEPT_MAX) S->flag[tid] = 0;
-    __syncthreads();
-    for (int r = tid; r < total; r += blockDim.x) {
-      const int row = rows ? rows[S->kidx[r]] : S->kidx[r];
-      if (row >= 0 && row < NMS_KEPT_MAX) S->flag[row] = 1;
-    }
-    __syncthreads();
-    int f = 0;
-    u64 fb = 0;
-    if (tid < NMS_KEPT_MAX) {
-      f = S->flag[tid];
-      fb = __ballot(f != 0);
-      if (lane == 0) S->wcnt[grp] = __popcll(fb);
-    }
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
-      const int cw = S->wcnt[w];
-      if (w < grp) before += cw;
-      all += cw;
-    }
-    if (tid < NMS_KEPT_MAX && f) {
-      const int pos = before + __popcll(fb & ((1ull << lane) - 1ull));
-      if (pos < o.uniq_cap) o.uniq_rows[pos] = tid;
-    }
-    if (tid == 0 && o.uniq_count) *o.uniq_count = all < o.uniq_cap ? all : o.uniq_cap;
   }
   __syncthreads();
   return stopped;
-}
-
-__device__ __forceinline__ int score_bin(unsigned bits) {
-  int bin = (int)(bits >> 14) - (int)(0x3C000000u >> 14);
-  return bin < 0 ? 0 : (bin > 4095 ? 4095 : bin);
-}
-
-// sort the n keys of `buf` (n <= 1024 E) descending and leave them there in sorted order
-template <int E>
-__device__ __forceinline__ void sort_in_place(u64* buf, int n) {
-  u64 v[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int i = threadIdx.x * E + e;
-    v[e] = i < n ? buf[i] : 0ull;
-  }
-  __syncthreads();                     // every thread holds its keys: the buffer becomes the sort's exchange buffer
-  block_sort_desc_reg<E>(v, buf);
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int q = threadIdx.x * E + e;
-    if (q < n) buf[q] = v[e];
-  }
-  __syncthreads();
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -456,6 +439,29 @@ struct CnArgs {
 __device__ __forceinline__ size_t cn_head_row(const CnArgs& p, int scene, int level, int i) {
   const int n = p.level_off[level + 1] - p.level_off[level];
   return (size_t)p.batch * p.level_off[level] + (size_t)scene * n + i;
+}
+
+// The box of position g (scene-local, on `level`) from the head's four regression outputs (centernet.py:321-339, 660-672).  `p` is the
+// kernel's own argument struct and `scene` the workgroup's scene: the head is the one operand no kernel offsets by its scene.
+__device__ __forceinline__ float4 cn_decode_box(const CnArgs& p, int scene, int level, int g) {
+  const int i = g - p.level_off[level];
+  const int w = p.level_w[level];
+  const int stride = p.level_stride[level];
+  const int gy_i = i / w, gx_i = i - gy_i * w;
+  const float gx = (float)(gx_i * stride + stride / 2);
+  const float gy = (float)(gy_i * stride + stride / 2);
+  const float* h = p.head + cn_head_row(p, scene, level, i) * p.head_stride;
+  const float sc = p.level_scale[level];
+  const float st = (float)stride;
+  const float r0 = fmaxf(h[1] * sc, 0.f) * st;
+  const float r1 = fmaxf(h[2] * sc, 0.f) * st;
+  const float r2 = fmaxf(h[3] * sc, 0.f) * st;
+  const float r3 = fmaxf(h[4] * sc, 0.f) * st;
+  const float x1 = gx - r0, y1 = gy - r1;
+  float x2 = gx + r2, y2 = gy + r3;
+  x2 = fmaxf(x2, x1 + 0.01f);
+  y2 = fmaxf(y2, y1 + 0.01f);
+  return make_float4(x1, y1, x2, y2);
 }
 
 #define EOD_SORT_MAX 16384
@@ -504,7 +510,7 @@ __global__ __launch_bounds__(1024) void cn_level_topk_kernel(CnArgs p) {
   // read of the level tables goes through it)
   u64* const cand_keys = p.cand_keys + (size_t)scene * p.pk_off[p.levels];
   int* const cand_cnt = p.cand_cnt + scene * 8;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   for (int i = tid; i < 4096; i += 1024) hist[i] = 0;
   if (tid == 0) {
     sh_cnt = 0;
@@ -522,9 +528,7 @@ __global__ __launch_bounds__(1024) void cn_level_topk_kernel(CnArgs p) {
       const float heat = eod_sigmoid_precise(p.head[(head0 + i) * p.head_stride]);
       if (heat > p.score_thresh) {
         k = make_key(heat, (unsigned)i);
-        int bin = (int)(__float_as_uint(heat) >> 14) - (int)(0x3C000000u >> 14);
-        bin = bin < 0 ? 0 : (bin > 4095 ? 4095 : bin);
-        atomicAdd(&hist[bin], 1);
+        atomicAdd(&hist[score_bin(__float_as_uint(heat))], 1);
         ++local;
       }
     }
@@ -534,46 +538,9 @@ __global__ __launch_bounds__(1024) void cn_level_topk_kernel(CnArgs p) {
   __syncthreads();
   const int cnt = sh_cnt;
   const int take = cnt < p.topk ? cnt : p.topk;
-  // suffix sums over the bins: thread t owns bins 4 t .. 4 t + 3
-  {
-    const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-    const int mine = h0 + h1 + h2 + h3;
-    int inc = mine;                                  // inclusive suffix inside the wave (towards higher lanes)
+  const int cut = block_hist_cut(hist, take, wsum, &sh_cut);
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int t = __shfl_down(inc, off, 64);
-      if (lane + off < 64) inc += t;
-    }
-    if (lane == 0) wsum[wave] = inc;
-    __syncthreads();
-    int after = 0;                                   // candidates in the bins of higher threads' waves
-    for (int w = wave + 1; w < 16; ++w) after += wsum[w];
-    const int above = after + inc - mine;            // candidates in bins > 4 t + 3
-    // the lowest bin whose suffix reaches `take`: exactly one thread finds it
-    const int s3 = above + h3, s2 = s3 + h2, s1 = s2 + h1, s0 = s1 + h0;
-    if (take > 0) {
-      if (above < take && s3 >= take) sh_cut = 4 * tid + 3;
-      else if (s3 < take && s2 >= take) sh_cut = 4 * tid + 2;
-      else if (s2 < take && s1 >= take) sh_cut = 4 * tid + 1;
-      else if (s1 < take && s0 >= take) sh_cut = 4 * tid;
-    }
-  }
-  __syncthreads();
-  const int cut = sh_cut;
-#pragma unroll
-  for (int e = 0; e < EMAX; ++e) {
-    bool in = false;
-    if (v[e]) {
-      int bin = (int)((unsigned)(v[e] >> 32) >> 14) - (int)(0x3C000000u >> 14);
-      bin = bin < 0 ? 0 : (bin > 4095 ? 4095 : bin);
-      in = bin >= cut;
-    }
-    const u64 bal = __ballot(in);
-    int base = 0;
-    if (lane == 0 && bal) base = atomicAdd(&sh_n2, __popcll(bal));
-    base = __shfl(base, 0, 64);
-    if (in) xch[base + __popcll(bal & ((1ull << lane) - 1ull))] = v[e];
-  }
+  for (int e = 0; e < EMAX; ++e) wave_compact_key(v[e] != 0 && score_bin((unsigned)(v[e] >> 32)) >= cut, v[e], &sh_n2, xch);
   __syncthreads();
   const int n2 = sh_n2;                              // take <= n2 <= cnt
   const int slots = p.pk_off[level + 1] - p.pk_off[level];
@@ -617,27 +584,11 @@ __global__ __launch_bounds__(1024) void cn_merge_nms_kernel(CnArgs p, float* sor
     const int g = (int)key_index(k);
     int level = 0;
     while (level + 1 < p.levels && g >= p.level_off[level + 1]) ++level;
-    const int i = g - p.level_off[level];
-    const int w = p.level_w[level];
-    const int stride = p.level_stride[level];
-    const int gy_i = i / w, gx_i = i - gy_i * w;
-    const float gx = (float)(gx_i * stride + stride / 2);
-    const float gy = (float)(gy_i * stride + stride / 2);
-    const float* h = p.head + cn_head_row(p, scene, level, i) * p.head_stride;
-    const float sc = p.level_scale[level];
-    const float st = (float)stride;
-    const float r0 = fmaxf(h[1] * sc, 0.f) * st;
-    const float r1 = fmaxf(h[2] * sc, 0.f) * st;
-    const float r2 = fmaxf(h[3] * sc, 0.f) * st;
-    const float r3 = fmaxf(h[4] * sc, 0.f) * st;
-    const float x1 = gx - r0, y1 = gy - r1;
-    float x2 = gx + r2, y2 = gy + r3;
-    x2 = fmaxf(x2, x1 + 0.01f);
-    y2 = fmaxf(y2, y1 + 0.01f);
-    sorted_boxes[r * 4 + 0] = x1;
-    sorted_boxes[r * 4 + 1] = y1;
-    sorted_boxes[r * 4 + 2] = x2;
-    sorted_boxes[r * 4 + 3] = y2;
+    const float4 bx = cn_decode_box(p, scene, level, g);
+    sorted_boxes[r * 4 + 0] = bx.x;
+    sorted_boxes[r * 4 + 1] = bx.y;
+    sorted_boxes[r * 4 + 2] = bx.z;
+    sorted_boxes[r * 4 + 3] = bx.w;
     sorted_scores[r] = key_score(k);
   };
   // Fast path: NMS 0.9 keeps nearly every candidate, so the post-NMS cut (256 + ties) is reached inside the best few hundred of
@@ -648,7 +599,7 @@ __global__ __launch_bounds__(1024) void cn_merge_nms_kernel(CnArgs p, float* sor
   __shared__ int wsum[16];
   __shared__ int sh_cut, sh_n2;
   if (n > 1024) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     for (int i = tid; i < 4096; i += 1024) hist[i] = 0;
     if (tid == 0) {
       sh_cut = 0;
@@ -659,50 +610,18 @@ __global__ __launch_bounds__(1024) void cn_merge_nms_kernel(CnArgs p, float* sor
     for (int e = 0; e < E; ++e)
       if (v[e]) atomicAdd(&hist[score_bin((unsigned)(v[e] >> 32))], 1);
     __syncthreads();
-    {
-      const int want = 1024;
-      const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-      const int mine = h0 + h1 + h2 + h3;
-      int inc = mine;
+    const int cut = block_hist_cut(hist, 1024, wsum, &sh_cut);
 #pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_down(inc, off, 64);
-        if (lane + off < 64) inc += t;
-      }
-      if (lane == 0) wsum[wave] = inc;
-      __syncthreads();
-      int after = 0;
-      for (int w = wave + 1; w < 16; ++w) after += wsum[w];
-      const int above = after + inc - mine;
-      const int s3 = above + h3, s2 = s3 + h2, s1 = s2 + h1, s0 = s1 + h0;
-      if (above < want && s3 >= want) sh_cut = 4 * tid + 3;
-      else if (s3 < want && s2 >= want) sh_cut = 4 * tid + 2;
-      else if (s2 < want && s1 >= want) sh_cut = 4 * tid + 1;
-      else if (s1 < want && s0 >= want) sh_cut = 4 * tid;
-    }
-    __syncthreads();
-    const int cut = sh_cut;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const bool in = v[e] != 0 && score_bin((unsigned)(v[e] >> 32)) >= cut;
-      const u64 bal = __ballot(in);
-      int base = 0;
-      if (lane == 0 && bal) base = atomicAdd(&sh_n2, __popcll(bal));
-      base = __shfl(base, 0, 64);
-      if (in) xch[base + __popcll(bal & ((1ull << lane) - 1ull))] = v[e];
-    }
+    for (int e = 0; e < E; ++e) wave_compact_key(v[e] != 0 && score_bin((unsigned)(v[e] >> 32)) >= cut, v[e], &sh_n2, xch);
     __syncthreads();
     const int n2 = sh_n2;                            // 1024 <= n2 <= n
     if (n2 < n && n2 <= 4096) {
-      if (n2 <= 1024) sort_in_place<1>(xch, n2);
-      else if (n2 <= 2048) sort_in_place<2>(xch, n2);
-      else sort_in_place<(E >= 4 ? 4 : E)>(xch, n2);
+      block_sort_keys<4>(xch, n2);
       EOD_STAMP(2);
       for (int r = tid; r < n2; r += 1024) decode(r, xch[r]);
       __syncthreads();
       EOD_STAMP(3);
-      const bool stopped = block_greedy_nms(sorted_boxes, sorted_scores, nullptr, nullptr, n2, nms_thresh, post_topk, 1, o,
-                                            reinterpret_cast<NmsSmem*>(xch));
+      const bool stopped = block_greedy_nms(sorted_boxes, sorted_scores, n2, nms_thresh, post_topk, o, reinterpret_cast<NmsSmem*>(xch));
       EOD_STAMP(4);
       if (stopped) return;                           // workgroup-uniform
     }
@@ -716,7 +635,7 @@ __global__ __launch_bounds__(1024) void cn_merge_nms_kernel(CnArgs p, float* sor
   }
   __syncthreads();          // the sorted list (global) and the end of the sort's use of xch
   EOD_STAMP(3);
-  block_greedy_nms(sorted_boxes, sorted_scores, nullptr, nullptr, n, nms_thresh, post_topk, 1, o, reinterpret_cast<NmsSmem*>(xch));
+  block_greedy_nms(sorted_boxes, sorted_scores, n, nms_thresh, post_topk, o, reinterpret_cast<NmsSmem*>(xch));
   EOD_STAMP(4);
 }
 
@@ -779,24 +698,7 @@ __global__ __launch_bounds__(256) void cn_rank_decode_kernel(CnArgs p, float* so
     rank += a;
     for (int q = a; q < b; ++q) rank += key_index(lk[q]) < g ? 1 : 0;
   }
-  const int i = (int)g - p.level_off[level];
-  const int w = p.level_w[level];
-  const int stride = p.level_stride[level];
-  const int gy_i = i / w, gx_i = i - gy_i * w;
-  const float gx = (float)(gx_i * stride + stride / 2);
-  const float gy = (float)(gy_i * stride + stride / 2);
-  const float* h = p.head + cn_head_row(p, scene, level, i) * p.head_stride;
-  const float scl = p.level_scale[level];
-  const float st = (float)stride;
-  const float r0 = fmaxf(h[1] * scl, 0.f) * st;
-  const float r1 = fmaxf(h[2] * scl, 0.f) * st;
-  const float r2 = fmaxf(h[3] * scl, 0.f) * st;
-  const float r3 = fmaxf(h[4] * scl, 0.f) * st;
-  const float x1 = gx - r0, y1 = gy - r1;
-  float x2 = gx + r2, y2 = gy + r3;
-  x2 = fmaxf(x2, x1 + 0.01f);
-  y2 = fmaxf(y2, y1 + 0.01f);
-  reinterpret_cast<float4*>(sorted_boxes)[rank] = make_float4(x1, y1, x2, y2);
+  reinterpret_cast<float4*>(sorted_boxes)[rank] = cn_decode_box(p, scene, level, (int)g);
   sorted_scores[rank] = sc;
 }
 
@@ -880,15 +782,7 @@ __global__ __launch_bounds__(1024) void nms_scan_kernel(const float* __restrict_
     if (grp == 0) {
       u64 rem = removed[c];
       if (lim < 64) rem |= ~0ull << lim;
-      u64 kept = 0;
-      for (int i = 0; i < lim; ++i) {
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(diag & 0xFFFFFFFFull), i);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(diag >> 32), i);
-        if (!((rem >> i) & 1ull)) {
-          kept |= 1ull << i;
-          rem |= ((u64)hi << 32) | lo;
-        }
-      }
+      const u64 kept = wave_resolve_diag(diag, rem, lim);
       // the cut: the first max_keep kept boxes, then every kept box whose score equals the max_keep-th's (centernet.py:733-741)
       const int total0 = sh_total;
       const bool mine = (kept >> lane) & 1ull;
@@ -949,6 +843,156 @@ __global__ __launch_bounds__(1024) void nms_scan_kernel(const float* __restrict_
 #define DET_WORDS (DET_MAX_R / 64)
 #define DET_MAX_C 24
 
+// ------------------------------------------------------------------------------------------------------
+// Steps of the two fast_rcnn_inference tails (det_select_kernel, detw_tail_kernel), 1024 threads
+// ------------------------------------------------------------------------------------------------------
+// Row r's box clipped to the image into cbx (the zero box for the rows beyond the count, `in` false); returns whether the row is in
+// use and its box finite.
+__device__ __forceinline__ bool det_clip_row(const float* boxes, int r, bool in, float img_w, float img_h, float* cbx) {
+  float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+  if (in) {
+    b0 = boxes[r * 4 + 0]; b1 = boxes[r * 4 + 1]; b2 = boxes[r * 4 + 2]; b3 = boxes[r * 4 + 3];
+  }
+  cbx[r * 4 + 0] = fminf(fmaxf(b0, 0.f), img_w);
+  cbx[r * 4 + 1] = fminf(fmaxf(b1, 0.f), img_h);
+  cbx[r * 4 + 2] = fminf(fmaxf(b2, 0.f), img_w);
+  cbx[r * 4 + 3] = fminf(fmaxf(b3, 0.f), img_h);
+  return in && isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3);
+}
+
+// IoU bit matrix of the R rows in use: bit b of Mx[r][w]: IoU(box r, box 64 w + b) > thr.  One word (64 partner rows) per thread
+// and step; the first `words` words of a row are written (>= ceil(R / 64): zero beyond the rows in use), no other is ever read.
+__device__ __forceinline__ void det_row_iou_matrix(const float* cbx, int R, int words, float nms_thresh, u64* Mx) {
+  const int W = (R + 63) >> 6;
+  for (int idx = threadIdx.x; idx < R * words; idx += 1024) {
+    const int r = idx / words, w = idx - r * words;
+    u64 bits = 0;
+    if (w < W) {
+      const float x1 = cbx[r * 4 + 0], y1 = cbx[r * 4 + 1], x2 = cbx[r * 4 + 2], y2 = cbx[r * 4 + 3];
+      const float area = (x2 - x1) * (y2 - y1);
+      for (int b = 0; b < 64; ++b) {
+        const int r2 = w * 64 + b;
+        if (r2 < R && r2 != r &&
+            iou_over(x1, y1, x2, y2, area, cbx[r2 * 4 + 0], cbx[r2 * 4 + 1], cbx[r2 * 4 + 2], cbx[r2 * 4 + 3], nms_thresh))
+          bits |= 1ull << b;
+      }
+    }
+    Mx[r * DET_WORDS + w] = bits;
+  }
+}
+
+// Rank of every kept entry of the sorted batch buf[0, n2) in list order (keptbits: bit q = entry q survives its class's NMS; n2 <=
+// 64 MAX_WORDS, MAX_WORDS = 64 or 128): popcounts of the words before it + of the bits below it.  The entries of rank < topk - total0
+// go to kept_key[total0 + rank].  Returns the number of kept entries of the batch.  wordpre[MAX_WORDS] and wsum are scratch.
+template <int MAX_WORDS>
+__device__ __forceinline__ int block_rank_and_take(const u64* keptbits, int n2, int total0, int topk, const u64* buf, u64* kept_key,
+                                                   int* wordpre, int* wsum) {
+  static_assert(MAX_WORDS == 64 || MAX_WORDS == 128, "one or two waves scan the words");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nwords = (n2 + 63) >> 6;
+  if (tid < MAX_WORDS) {
+    const int pc = tid < nwords ? __popcll(keptbits[tid]) : 0;
+    int inc = pc;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int t = __shfl_up(inc, off, 64);
+      if (lane >= off) inc += t;
+    }
+    wordpre[tid] = inc - pc;                               // exclusive inside the wave
+    if (lane == 63) wsum[wave] = inc;
+  }
+  __syncthreads();
+  for (int q = tid; q < n2; q += 1024) {
+    const u64 wbits = keptbits[q >> 6];
+    if ((wbits >> (q & 63)) & 1ull) {
+      const int rank = wordpre[q >> 6] + ((q >> 6) >= 64 ? wsum[0] : 0) + __popcll(wbits & ((1ull << (q & 63)) - 1ull));
+      const int pos = total0 + rank;
+      if (pos < topk && pos < NMS_KEPT_MAX) kept_key[pos] = buf[q];
+    }
+  }
+  return wsum[0] + (nwords > 64 ? wsum[1] : 0);
+}
+
+// Ballot compaction over one flag per thread of the first NMS_KEPT_MAX threads (false in the others): returns the number of set flags
+// below this thread's -- its slot in the compacted list -- and the number of all of them through *all.
+__device__ __forceinline__ int block_compact_flags(bool pred, int* wsum, int* all) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  u64 bal = 0;
+  if (tid < NMS_KEPT_MAX) {
+    bal = __ballot(pred);
+    if (lane == 0) wsum[wave] = __popcll(bal);
+  }
+  __syncthreads();
+  int before = 0;
+  *all = 0;
+#pragma unroll
+  for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
+    const int cw = wsum[w];
+    if (w < wave) before += cw;
+    *all += cw;
+  }
+  return before + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// The outputs of a selection from its kept keys (kept_key[0, total), key index = row * C + class): count, box / score / class / row
+// per detection, and the optional lists.  flag[NMS_KEPT_MAX] and wsum are scratch.
+__device__ __forceinline__ void det_write_outputs(const u64* kept_key, int total, int C, const float* cbx, const ScanOut& o, int* flag,
+                                                  int* wsum) {
+  const int tid = threadIdx.x;
+  if (total > o.cap) total = o.cap;
+  if (total > NMS_KEPT_MAX) total = NMS_KEPT_MAX;
+  if (tid == 0 && o.out_count) *o.out_count = total;
+  int my_row = -1;
+  if (tid < total) {
+    const u64 k = kept_key[tid];
+    const int slot = (int)key_index(k);
+    int r = slot / C;
+    const int cl = slot - r * C;
+    r = r < 0 ? 0 : (r >= DET_MAX_R ? DET_MAX_R - 1 : r);
+    my_row = r;
+    if (o.out_boxes) {
+      o.out_boxes[tid * 4 + 0] = cbx[r * 4 + 0];
+      o.out_boxes[tid * 4 + 1] = cbx[r * 4 + 1];
+      o.out_boxes[tid * 4 + 2] = cbx[r * 4 + 2];
+      o.out_boxes[tid * 4 + 3] = cbx[r * 4 + 3];
+    }
+    if (o.out_scores) o.out_scores[tid] = key_score(k);
+    if (o.out_labels) o.out_labels[tid] = cl;
+    if (o.out_rows) o.out_rows[tid] = r;
+  }
+  const bool row_flagged = tid < total && my_row >= 0 && my_row < NMS_KEPT_MAX;
+  if (o.rep_of) {
+    // entries of one source row carry the same box: the first of them represents the group (the mask head is class agnostic)
+    if (tid < NMS_KEPT_MAX) flag[tid] = 0x7FFFFFFF;
+    __syncthreads();
+    if (row_flagged) atomicMin(&flag[my_row], tid);
+    __syncthreads();
+    bool is_rep = false;
+    if (tid < total) {
+      const int rep = row_flagged ? flag[my_row] : tid;
+      o.rep_of[tid] = rep;
+      is_rep = rep == tid;
+    }
+    int all;
+    const int pos = block_compact_flags(is_rep, wsum, &all);
+    if (tid < NMS_KEPT_MAX && is_rep) o.rep_list[pos] = tid;
+    if (tid == 0) *o.rep_count = all;
+    __syncthreads();
+  }
+  if (o.uniq_rows) {
+    // torch.unique of the kept rows: flags over the row ids (< NMS_KEPT_MAX), ballot compaction, ascending
+    if (tid < NMS_KEPT_MAX) flag[tid] = 0;
+    __syncthreads();
+    if (row_flagged) flag[my_row] = 1;
+    __syncthreads();
+    const bool f = tid < NMS_KEPT_MAX && flag[tid] != 0;
+    int all;
+    const int pos = block_compact_flags(f, wsum, &all);
+    if (f && pos < o.uniq_cap) o.uniq_rows[pos] = tid;
+    if (tid == 0 && o.uniq_count) *o.uniq_count = all < o.uniq_cap ? all : o.uniq_cap;
+  }
+}
+
 __global__ __launch_bounds__(1024) void det_select_kernel(const float* boxes, const float* scores, const int* count, int R_cap, int C1,
                                                            float img_w, float img_h, float thr, float nms_thresh, int topk, ScanOut o) {
   EOD_CHAIN_PRIO();
@@ -996,18 +1040,10 @@ __global__ __launch_bounds__(1024) void det_select_kernel(const float* boxes, co
   }
   // a row takes part only if its box and ALL its scores are finite (d2 fast_rcnn_inference drops the others)
   for (int r = tid; r < R_cap; r += 1024) {
-    bool fin = r < R;
-    float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-    if (fin) {
-      b0 = boxes[r * 4 + 0]; b1 = boxes[r * 4 + 1]; b2 = boxes[r * 4 + 2]; b3 = boxes[r * 4 + 3];
-      fin = isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3);
+    bool fin = det_clip_row(boxes, r, r < R, img_w, img_h, cbx);
+    if (r < R)
       for (int q = 0; q < C1; ++q) fin = fin & (bool)isfinite(scores[r * C1 + q]);
-    }
     row_ok[r] = fin ? 1 : 0;
-    cbx[r * 4 + 0] = fminf(fmaxf(b0, 0.f), img_w);
-    cbx[r * 4 + 1] = fminf(fmaxf(b1, 0.f), img_h);
-    cbx[r * 4 + 2] = fminf(fmaxf(b2, 0.f), img_w);
-    cbx[r * 4 + 3] = fminf(fmaxf(b3, 0.f), img_h);
   }
   // the thread's scores: eight independent loads, one latency (slot i = e * 1024 + tid = (row, class))
   float sc[EMAX];
@@ -1019,20 +1055,7 @@ __global__ __launch_bounds__(1024) void det_select_kernel(const float* boxes, co
   }
   __syncthreads();
   EOD_STAMP(sb + 1);
-  // IoU bit matrix: one word (64 partner rows) per thread and step
-  for (int idx = tid; idx < R * W; idx += 1024) {
-    const int r = idx / W, w = idx - r * W;
-    const float x1 = cbx[r * 4 + 0], y1 = cbx[r * 4 + 1], x2 = cbx[r * 4 + 2], y2 = cbx[r * 4 + 3];
-    const float area = (x2 - x1) * (y2 - y1);
-    u64 bits = 0;
-    for (int b = 0; b < 64; ++b) {
-      const int r2 = w * 64 + b;
-      if (r2 < R && r2 != r &&
-          iou_over(x1, y1, x2, y2, area, cbx[r2 * 4 + 0], cbx[r2 * 4 + 1], cbx[r2 * 4 + 2], cbx[r2 * 4 + 3], nms_thresh))
-        bits |= 1ull << b;
-    }
-    Mx[r * DET_WORDS + w] = bits;
-  }
+  det_row_iou_matrix(cbx, R, W, nms_thresh, Mx);
   EOD_STAMP(sb + 2);
   // candidates: score > thr on a finite row; histogram of their score bits
   u64 key[EMAX];
@@ -1052,53 +1075,18 @@ __global__ __launch_bounds__(1024) void det_select_kernel(const float* boxes, co
   __syncthreads();
   const int n = sh_cnt;
   // the lowest bin whose suffix holds min(n, 1024) candidates
-  {
-    const int want = n < 1024 ? n : 1024;
-    const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-    const int mine = h0 + h1 + h2 + h3;
-    int inc = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int t = __shfl_down(inc, off, 64);
-      if (lane + off < 64) inc += t;
-    }
-    if (lane == 0) wsum[wave] = inc;
-    __syncthreads();
-    int after = 0;
-    for (int w = wave + 1; w < 16; ++w) after += wsum[w];
-    const int above = after + inc - mine;
-    const int s3 = above + h3, s2 = s3 + h2, s1 = s2 + h1, s0 = s1 + h0;
-    if (want > 0) {
-      if (above < want && s3 >= want) sh_cut = 4 * tid + 3;
-      else if (s3 < want && s2 >= want) sh_cut = 4 * tid + 2;
-      else if (s2 < want && s1 >= want) sh_cut = 4 * tid + 1;
-      else if (s1 < want && s0 >= want) sh_cut = 4 * tid;
-    }
-  }
-  __syncthreads();
-  const int cut = sh_cut;
+  const int cut = block_hist_cut(hist, n < 1024 ? n : 1024, wsum, &sh_cut);
   EOD_STAMP(sb + 3);
   for (int batch = 0; batch < 2; ++batch) {
     // batch 0: the candidates of the bins >= cut; batch 1 (only if batch 0 did not fill the list): all the others
 #pragma unroll
     for (int e = 0; e < EMAX; ++e) {
-      bool in = false;
-      if (key[e]) {
-        const bool hi = score_bin((unsigned)(key[e] >> 32)) >= cut;
-        in = batch == 0 ? hi : !hi;
-      }
-      const u64 bal = __ballot(in);
-      int base = 0;
-      if (lane == 0 && bal) base = atomicAdd(&sh_n2, __popcll(bal));
-      base = __shfl(base, 0, 64);
-      if (in) buf[base + __popcll(bal & ((1ull << lane) - 1ull))] = key[e];
+      const bool hi = score_bin((unsigned)(key[e] >> 32)) >= cut;
+      wave_compact_key(key[e] != 0 && (batch == 0 ? hi : !hi), key[e], &sh_n2, buf);
     }
     __syncthreads();
     const int n2 = sh_n2;
-    if (n2 <= 1024) sort_in_place<1>(buf, n2);
-    else if (n2 <= 2048) sort_in_place<2>(buf, n2);
-    else if (n2 <= 4096) sort_in_place<4>(buf, n2);
-    else sort_in_place<8>(buf, n2);
+    block_sort_keys<EMAX>(buf, n2);
     EOD_STAMP(sb + 4 + 2 * batch);
     // Greedy NMS over the sorted batch, per class and in parallel: suppression only acts inside a class, so the greedy walk over
     // the whole list is the same as C independent walks over each class's entries in list order.  Wave w takes classes w, w + 16:
@@ -1139,127 +1127,25 @@ __global__ __launch_bounds__(1024) void det_select_kernel(const float* boxes, co
       if (lane < DET_WORDS) supp[cls * DET_WORDS + lane] = myw;
     }
     __syncthreads();
-    // rank of every kept entry in list order: popcounts of the words before it + of the bits below it
-    {
-      const int nwords = (n2 + 63) >> 6;                   // <= 128
-      if (tid < 128) {
-        const int pc = tid < nwords ? __popcll(keptbits[tid]) : 0;
-        int inc = pc;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int t = __shfl_up(inc, off, 64);
-          if (lane >= off) inc += t;
-        }
-        wordpre[tid] = inc - pc;                             // exclusive inside the wave
-        if (lane == 63) wsum[wave] = inc;                    // waves 0 and 1
-      }
-      __syncthreads();
-      const int total0 = sh_total;
-      const int kept_all = wsum[0] + (nwords > 64 ? wsum[1] : 0);
-#pragma unroll
-      for (int e = 0; e < EMAX; ++e) {
-        const int q = e * 1024 + tid;
-        if (q < n2) {
-          const u64 wbits = keptbits[q >> 6];
-          if ((wbits >> (q & 63)) & 1ull) {
-            const int rank = wordpre[q >> 6] + ((q >> 6) >= 64 ? wsum[0] : 0) + __popcll(wbits & ((1ull << (q & 63)) - 1ull));
-            const int pos = total0 + rank;
-            if (pos < topk && pos < NMS_KEPT_MAX) kept_key[pos] = buf[q];
-          }
-        }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int total = total0 + kept_all;
-        const bool full = total >= topk;
-        if (full) total = topk;
-        sh_total = total;
-        // done when the list is full or no candidate is left for a second batch
-        sh_done = (full || batch == 1 || n2 >= n) ? 1 : 0;
-        sh_n2 = 0;
-      }
+    // the kept entries are ranked in list order and the first (topk - total) of them taken
+    const int total0 = sh_total;
+    const int kept_all = block_rank_and_take<1024 * EMAX / 64>(keptbits, n2, total0, topk, buf, kept_key, wordpre, wsum);
+    __syncthreads();
+    if (tid == 0) {
+      int total = total0 + kept_all;
+      const bool full = total >= topk;
+      if (full) total = topk;
+      sh_total = total;
+      // done when the list is full or no candidate is left for a second batch
+      sh_done = (full || batch == 1 || n2 >= n) ? 1 : 0;
+      sh_n2 = 0;
     }
     __syncthreads();
     EOD_STAMP(sb + 5 + 2 * batch);
     if (sh_done) break;
   }
   __syncthreads();
-  int total = sh_total;
-  if (total > o.cap) total = o.cap;
-  if (total > NMS_KEPT_MAX) total = NMS_KEPT_MAX;
-  if (tid == 0 && o.out_count) *o.out_count = total;
-  int my_row = -1;
-  if (tid < total) {
-    const u64 k = kept_key[tid];
-    const int slot = (int)key_index(k);
-    const int r = slot / C, cl = slot - r * C;
-    my_row = r;
-    if (o.out_boxes) {
-      o.out_boxes[tid * 4 + 0] = cbx[r * 4 + 0];
-      o.out_boxes[tid * 4 + 1] = cbx[r * 4 + 1];
-      o.out_boxes[tid * 4 + 2] = cbx[r * 4 + 2];
-      o.out_boxes[tid * 4 + 3] = cbx[r * 4 + 3];
-    }
-    if (o.out_scores) o.out_scores[tid] = key_score(k);
-    if (o.out_labels) o.out_labels[tid] = cl;
-    if (o.out_rows) o.out_rows[tid] = r;
-  }
-  if (o.rep_of) {
-    // entries of one source row carry the same box: the first of them represents the group (the mask head is class agnostic)
-    if (tid < NMS_KEPT_MAX) flag[tid] = 0x7FFFFFFF;
-    __syncthreads();
-    if (tid < total && my_row >= 0 && my_row < NMS_KEPT_MAX) atomicMin(&flag[my_row], tid);
-    __syncthreads();
-    int is_rep = 0;
-    if (tid < total) {
-      const int rep = (my_row >= 0 && my_row < NMS_KEPT_MAX) ? flag[my_row] : tid;
-      o.rep_of[tid] = rep;
-      is_rep = rep == tid;
-    }
-    u64 rb = 0;
-    if (tid < NMS_KEPT_MAX) {
-      rb = __ballot(is_rep != 0);
-      if (lane == 0) wsum[wave] = __popcll(rb);
-    }
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
-      const int cw = wsum[w];
-      if (w < wave) before += cw;
-      all += cw;
-    }
-    if (tid < NMS_KEPT_MAX && is_rep) o.rep_list[before + __popcll(rb & ((1ull << lane) - 1ull))] = tid;
-    if (tid == 0) *o.rep_count = all;
-    __syncthreads();
-  }
-  if (o.uniq_rows) {
-    // torch.unique of the kept rows: flags over the row ids (< NMS_KEPT_MAX), ballot compaction, ascending
-    if (tid < NMS_KEPT_MAX) flag[tid] = 0;
-    __syncthreads();
-    if (tid < total && my_row >= 0 && my_row < NMS_KEPT_MAX) flag[my_row] = 1;
-    __syncthreads();
-    int f = 0;
-    u64 fb = 0;
-    if (tid < NMS_KEPT_MAX) {
-      f = flag[tid];
-      fb = __ballot(f != 0);
-      if (lane == 0) wsum[wave] = __popcll(fb);
-    }
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
-      const int cw = wsum[w];
-      if (w < wave) before += cw;
-      all += cw;
-    }
-    if (tid < NMS_KEPT_MAX && f) {
-      const int pos = before + __popcll(fb & ((1ull << lane) - 1ull));
-      if (pos < o.uniq_cap) o.uniq_rows[pos] = tid;
-    }
-    if (tid == 0 && o.uniq_count) *o.uniq_count = all < o.uniq_cap ? all : o.uniq_cap;
-  }
+  det_write_outputs(kept_key, sh_total, C, cbx, o, flag, wsum);
   EOD_STAMP(sb + 8);
 #ifdef EOD_STAMPS
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -1401,34 +1287,21 @@ __global__ __launch_bounds__(256) void detw_hist_kernel(const float* __restrict_
 // 256 threads, 16 bins each; every workgroup of (b) and the tail workgroup compute the same value from the same histogram.
 // Returns the cut (0..4096; 4096 = no bin fits) and the scene's candidate count through *total.
 __device__ __forceinline__ int detw_cut(const int* __restrict__ hist, int* sh_wsum /*[4]*/, int* sh_out /*[1]*/, int* total) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int h[16], mine = 0;
+  const int tid = threadIdx.x;
+  int h[16];
   if (tid < 256) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      h[j] = hist[tid * 16 + j];
-      mine += h[j];
-    }
+    for (int j = 0; j < 16; ++j) h[j] = hist[tid * 16 + j];
   } else {
 #pragma unroll
     for (int j = 0; j < 16; ++j) h[j] = 0;
   }
-  int inc = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_down(inc, off, 64);
-    if (lane + off < 64) inc += t;
-  }
   if (tid == 0) *sh_out = 4096;
-  if (lane == 0 && wave < 4) sh_wsum[wave] = inc;
-  __syncthreads();
-  int after = 0;
-  for (int w = wave + 1; w < 4; ++w) after += sh_wsum[w];
+  int suf = block_bins_above<16>(h, sh_wsum);                // candidates in the bins above this thread's
   *total = sh_wsum[0] + sh_wsum[1] + sh_wsum[2] + sh_wsum[3];
   if (tid < 256) {
     // suffix counts of this thread's bins; a bin b is "takeable" iff suffix(b) <= DETW_BATCH; the cut is the lowest takeable bin
     // that is still needed: suffix(b + 1) < DETW_WANT
-    int suf = after + inc - mine;                            // candidates in the bins above this thread's
     int best = 4096;
 #pragma unroll
     for (int j = 15; j >= 0; --j) {
@@ -1511,7 +1384,7 @@ __global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, con
   __shared__ int wordpre[DETW_BATCH / 64];
   __shared__ int wsum[16];
   __shared__ unsigned char row_ok[DET_MAX_R];
-  __shared__ int sh_wsum[4], sh_out, sh_n2, sh_nseg, sh_total, sh_done, sh_kept_all;
+  __shared__ int sh_wsum[4], sh_out, sh_n2, sh_nseg, sh_total, sh_done;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int R = detw_rows(count, scene, R_cap);
   const int W = (R + 63) >> 6;
@@ -1527,14 +1400,7 @@ __global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, con
   for (int r = tid; r < DET_MAX_R; r += 1024) {
     const bool in = r < R;
     row_ok[r] = in ? ws.row_ok[(size_t)scene * DET_MAX_R + r] : 0;
-    float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-    if (in) {
-      b0 = boxes[r * 4 + 0]; b1 = boxes[r * 4 + 1]; b2 = boxes[r * 4 + 2]; b3 = boxes[r * 4 + 3];
-    }
-    cbx[r * 4 + 0] = fminf(fmaxf(b0, 0.f), img_w);
-    cbx[r * 4 + 1] = fminf(fmaxf(b1, 0.f), img_h);
-    cbx[r * 4 + 2] = fminf(fmaxf(b2, 0.f), img_w);
-    cbx[r * 4 + 3] = fminf(fmaxf(b3, 0.f), img_h);
+    det_clip_row(boxes, r, in, img_w, img_h, cbx);
   }
   if (tid == 0) {
     sh_total = 0;
@@ -1542,22 +1408,7 @@ __global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, con
   }
   __syncthreads();
   if (tid == 0) ws.cand_cnt[scene] = 0;
-  // IoU bit matrix: all DET_WORDS words of a row are written (zero beyond the rows in use)
-  for (int idx = tid; idx < R * DET_WORDS; idx += 1024) {
-    const int r = idx / DET_WORDS, w = idx - r * DET_WORDS;
-    u64 bits = 0;
-    if (w < W) {
-      const float x1 = cbx[r * 4 + 0], y1 = cbx[r * 4 + 1], x2 = cbx[r * 4 + 2], y2 = cbx[r * 4 + 3];
-      const float area = (x2 - x1) * (y2 - y1);
-      for (int b = 0; b < 64; ++b) {
-        const int r2 = w * 64 + b;
-        if (r2 < R && r2 != r &&
-            iou_over(x1, y1, x2, y2, area, cbx[r2 * 4 + 0], cbx[r2 * 4 + 1], cbx[r2 * 4 + 2], cbx[r2 * 4 + 3], nms_thresh))
-          bits |= 1ull << b;
-      }
-    }
-    Mx[idx] = bits;
-  }
+  det_row_iou_matrix(cbx, R, DET_WORDS, nms_thresh, Mx);     // all words of a row are written
   __syncthreads();
   int processed = 0;                 // candidates of the batches walked so far
   u64 bound = ~0ull;                 // every key of the batches walked so far is >= bound; the next batch lies below it
@@ -1579,22 +1430,10 @@ __global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, con
         __syncthreads();
         // the smallest digit d with acc + suffix(d) <= DETW_BATCH (4096 = none of this interval)
         if (tid == 0) sh_out = 4096;
-        int h4[4], mine = 0;
+        int h4[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          h4[j] = hist[tid * 4 + j];
-          mine += h4[j];
-        }
-        int inc = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int t = __shfl_down(inc, off, 64);
-          if (lane + off < 64) inc += t;
-        }
-        if (lane == 0) wsum[wave] = inc;
-        __syncthreads();
-        int suf = inc - mine;
-        for (int w = wave + 1; w < 16; ++w) suf += wsum[w];
+        for (int j = 0; j < 4; ++j) h4[j] = hist[tid * 4 + j];
+        int suf = block_bins_above<4>(h4, wsum);
         int best = 4096;
 #pragma unroll
         for (int j = 3; j >= 0; --j) {
@@ -1642,9 +1481,7 @@ __global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, con
       __syncthreads();
       if (n2 == 0) break;                                    // cannot happen while candidates are left; never spin
     }
-    if (n2 <= 1024) sort_in_place<1>(buf, n2);
-    else if (n2 <= 2048) sort_in_place<2>(buf, n2);
-    else sort_in_place<4>(buf, n2);
+    block_sort_keys<4>(buf, n2);
     // ---- entries by (class ascending, position ascending): descending sort of ((2047 - class) << 16 | (0xFFFF - position))
     for (int q = tid; q < n2; q += 1024) {
       const int slot = (int)key_index(buf[q]);
@@ -1654,9 +1491,7 @@ __global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, con
     for (int i = tid; i < DETW_BATCH / 64; i += 1024) keptbits[i] = 0;
     if (tid == 0) sh_nseg = 0;
     __syncthreads();
-    if (n2 <= 1024) sort_in_place<1>(comp, n2);
-    else if (n2 <= 2048) sort_in_place<2>(comp, n2);
-    else sort_in_place<4>(comp, n2);
+    block_sort_keys<4>(comp, n2);
     for (int q = tid; q < n2; q += 1024) {
       if (q == 0 || (comp[q] >> 16) != (comp[q - 1] >> 16)) {
         const int pos = atomicAdd(&sh_nseg, 1);
@@ -1696,36 +1531,15 @@ __global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, con
     }
     __syncthreads();
     // ---- rank of every kept entry in list order; the first (topk - total) of them are taken
-    {
-      const int nwords = (n2 + 63) >> 6;                     // <= 64: one wave
-      if (tid < 64) {
-        const int pc = tid < nwords ? __popcll(keptbits[tid]) : 0;
-        int inc = pc;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int t = __shfl_up(inc, off, 64);
-          if (lane >= off) inc += t;
-        }
-        wordpre[tid] = inc - pc;
-        if (lane == 63) sh_kept_all = inc;
-      }
-      __syncthreads();
-      const int total0 = sh_total;
-      for (int q = tid; q < n2; q += 1024) {
-        const u64 wbits = keptbits[q >> 6];
-        if ((wbits >> (q & 63)) & 1ull) {
-          const int pos = total0 + wordpre[q >> 6] + __popcll(wbits & ((1ull << (q & 63)) - 1ull));
-          if (pos < topk && pos < NMS_KEPT_MAX) kept_key[pos] = buf[q];
-        }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int total = total0 + sh_kept_all;
-        const bool full = total >= topk;
-        if (full) total = topk;
-        sh_total = total;
-        sh_done = (full || processed + n2 >= n_all) ? 1 : 0;
-      }
+    const int total0 = sh_total;
+    const int kept_all = block_rank_and_take<DETW_BATCH / 64>(keptbits, n2, total0, topk, buf, kept_key, wordpre, wsum);
+    __syncthreads();
+    if (tid == 0) {
+      int total = total0 + kept_all;
+      const bool full = total >= topk;
+      if (full) total = topk;
+      sh_total = total;
+      sh_done = (full || processed + n2 >= n_all) ? 1 : 0;
     }
     const u64 last = buf[n2 - 1];
     __syncthreads();
@@ -1734,91 +1548,14 @@ __global__ __launch_bounds__(1024) void detw_tail_kernel(const float* boxes, con
     bound = last;
   }
   __syncthreads();
-  int total = sh_total;
-  if (total > o.cap) total = o.cap;
-  if (total > NMS_KEPT_MAX) total = NMS_KEPT_MAX;
-  if (tid == 0 && o.out_count) *o.out_count = total;
-  int my_row = -1;
-  if (tid < total) {
-    const u64 k = kept_key[tid];
-    const int slot = (int)key_index(k);
-    int r = slot / C;
-    const int cl = slot - r * C;
-    r = r < 0 ? 0 : (r >= DET_MAX_R ? DET_MAX_R - 1 : r);
-    my_row = r;
-    if (o.out_boxes) {
-      o.out_boxes[tid * 4 + 0] = cbx[r * 4 + 0];
-      o.out_boxes[tid * 4 + 1] = cbx[r * 4 + 1];
-      o.out_boxes[tid * 4 + 2] = cbx[r * 4 + 2];
-      o.out_boxes[tid * 4 + 3] = cbx[r * 4 + 3];
-    }
-    if (o.out_scores) o.out_scores[tid] = key_score(k);
-    if (o.out_labels) o.out_labels[tid] = cl;
-    if (o.out_rows) o.out_rows[tid] = r;
-  }
-  if (o.rep_of) {
-    // entries of one source row carry the same box: the first of them represents the group (the mask head is class agnostic)
-    if (tid < NMS_KEPT_MAX) flag[tid] = 0x7FFFFFFF;
-    __syncthreads();
-    if (tid < total && my_row >= 0 && my_row < NMS_KEPT_MAX) atomicMin(&flag[my_row], tid);
-    __syncthreads();
-    int is_rep = 0;
-    if (tid < total) {
-      const int rep = (my_row >= 0 && my_row < NMS_KEPT_MAX) ? flag[my_row] : tid;
-      o.rep_of[tid] = rep;
-      is_rep = rep == tid;
-    }
-    u64 rb = 0;
-    if (tid < NMS_KEPT_MAX) {
-      rb = __ballot(is_rep != 0);
-      if (lane == 0) wsum[wave] = __popcll(rb);
-    }
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
-      const int cw = wsum[w];
-      if (w < wave) before += cw;
-      all += cw;
-    }
-    if (tid < NMS_KEPT_MAX && is_rep) o.rep_list[before + __popcll(rb & ((1ull << lane) - 1ull))] = tid;
-    if (tid == 0) *o.rep_count = all;
-    __syncthreads();
-  }
-  if (o.uniq_rows) {
-    // torch.unique of the kept rows: flags over the row ids (< NMS_KEPT_MAX), ballot compaction, ascending
-    if (tid < NMS_KEPT_MAX) flag[tid] = 0;
-    __syncthreads();
-    if (tid < total && my_row >= 0 && my_row < NMS_KEPT_MAX) flag[my_row] = 1;
-    __syncthreads();
-    int f = 0;
-    u64 fb = 0;
-    if (tid < NMS_KEPT_MAX) {
-      f = flag[tid];
-      fb = __ballot(f != 0);
-      if (lane == 0) wsum[wave] = __popcll(fb);
-    }
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NMS_KEPT_MAX / 64; ++w) {
-      const int cw = wsum[w];
-      if (w < wave) before += cw;
-      all += cw;
-    }
-    if (tid < NMS_KEPT_MAX && f) {
-      const int pos = before + __popcll(fb & ((1ull << lane) - 1ull));
-      if (pos < o.uniq_cap) o.uniq_rows[pos] = tid;
-    }
-    if (tid == 0 && o.uniq_count) *o.uniq_count = all < o.uniq_cap ? all : o.uniq_cap;
-  }
+  det_write_outputs(kept_key, sh_total, C, cbx, o, flag, wsum);
 }
 
 
 struct SelWs {
   float* sorted_boxes;
   float* sorted_scores;
-  int* sorted_labels;
+  int* sorted_labels;   // (these two lists are not in use; they stay in the layout, and so in the workspace sizes the library reports)
   int* sorted_rows;
   u64* cand_keys;
   int* cand_cnt;
@@ -1881,39 +1618,52 @@ extern "C" size_t eod_proposals_workspace_bytes(int total_positions, int levels,
   return carve(nullptr, slots * nb, slots, slots * nb).bytes;
 }
 
-// centernet.py:603-745 with lists beyond one workgroup's LDS (see the kernels above)
-static int centernet_proposals_wide(const EodProposalDesc* d, hipStream_t s) {
-  const int total = d->level_off[d->levels];
-  int packed = 0, max_level = 0;
+// What both proposal paths do first: the level sizes are validated and the kernels' argument struct filled from the descriptor, all
+// but the candidate lists (they follow the path's workspace layout).  The per-level candidate lists are packed: level l holds at
+// most min(level size, topk) entries, pk_off[levels] is the packed slot count of a scene.
+static int cn_args(const EodProposalDesc* d, int nb, CnArgs* a) {
+  a->batch = nb;
+  a->head = d->head_out; a->head_stride = d->head_stride; a->levels = d->levels;
+  a->score_thresh = d->score_thresh; a->topk = d->pre_nms_topk;
+  a->pk_off[0] = 0;
   for (int l = 0; l < d->levels; ++l) {
     const int n = d->level_off[l + 1] - d->level_off[l];
     if (n <= 0 || n > EOD_SORT_MAX || d->level_w[l] <= 0 || n % d->level_w[l] != 0) return EOD_ERR_CAPACITY;
-    packed += std::min(n, d->pre_nms_topk);
-    max_level = std::max(max_level, n);
+    a->level_off[l] = d->level_off[l];
+    a->level_w[l] = d->level_w[l];
+    a->level_stride[l] = d->level_stride[l];
+    a->level_scale[l] = d->level_scale[l];
+    a->pk_off[l + 1] = a->pk_off[l] + std::min(n, d->pre_nms_topk);
   }
-  if (packed > WIDE_MAX_SLOTS || d->cap < d->post_nms_topk || d->cap > WIDE_MAX_CAP) return EOD_ERR_CAPACITY;
+  a->level_off[d->levels] = d->level_off[d->levels];
+  return EOD_OK;
+}
+
+// per-level top-k into the lists of `w`: one workgroup per level and scene, sized by the largest level
+static void cn_launch_level_topk(CnArgs* a, const SelWs& w, hipStream_t s) {
+  a->cand_keys = w.cand_keys; a->cand_cnt = w.cand_cnt;
+  int max_level = 0;
+  for (int l = 0; l < a->levels; ++l) max_level = std::max(max_level, a->level_off[l + 1] - a->level_off[l]);
+  if (max_level <= 8192)
+    hipLaunchKernelGGL(cn_level_topk_kernel<8>, dim3(a->levels, a->batch), dim3(1024), 0, s, *a);
+  else
+    hipLaunchKernelGGL(cn_level_topk_kernel<16>, dim3(a->levels, a->batch), dim3(1024), 0, s, *a);
+}
+
+// centernet.py:603-745 with lists beyond one workgroup's LDS (see the kernels above)
+static int centernet_proposals_wide(const EodProposalDesc* d, hipStream_t s) {
+  const int total = d->level_off[d->levels];
   const int nb = d->batch > 1 ? d->batch : 1;
+  CnArgs a{};
+  if (const int err = cn_args(d, nb, &a)) return err;
+  const int packed = a.pk_off[d->levels];
+  if (packed > WIDE_MAX_SLOTS || d->cap < d->post_nms_topk || d->cap > WIDE_MAX_CAP) return EOD_ERR_CAPACITY;
   if (nb > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
   const int ws = std::min(total, d->levels * d->pre_nms_topk);          // >= packed
   const SelWs w = carve(d->workspace, ws * nb, ws, ws * nb);
   const WideWs ww = carve_wide(d->workspace, w.bytes, total, d->levels, d->pre_nms_topk, nb);
   if (d->workspace_bytes < ww.bytes) return EOD_ERR_CAPACITY;
-  CnArgs a{};
-  a.batch = nb;
-  a.head = d->head_out; a.head_stride = d->head_stride; a.levels = d->levels;
-  for (int l = 0; l <= d->levels; ++l) a.level_off[l] = d->level_off[l];
-  for (int l = 0; l < d->levels; ++l) {
-    a.level_w[l] = d->level_w[l];
-    a.level_stride[l] = d->level_stride[l];
-    a.level_scale[l] = d->level_scale[l];
-  }
-  a.score_thresh = d->score_thresh; a.topk = d->pre_nms_topk; a.cand_keys = w.cand_keys; a.cand_cnt = w.cand_cnt;
-  a.pk_off[0] = 0;
-  for (int l = 0; l < d->levels; ++l) a.pk_off[l + 1] = a.pk_off[l] + std::min(d->level_off[l + 1] - d->level_off[l], d->pre_nms_topk);
-  if (max_level <= 8192)
-    hipLaunchKernelGGL(cn_level_topk_kernel<8>, dim3(d->levels, nb), dim3(1024), 0, s, a);
-  else
-    hipLaunchKernelGGL(cn_level_topk_kernel<16>, dim3(d->levels, nb), dim3(1024), 0, s, a);
+  cn_launch_level_topk(&a, w, s);
   // the kernels below address the scenes' lists with the PACKED slot count as their stride
   const int words = (packed + 63) / 64;
   hipLaunchKernelGGL(cn_rank_decode_kernel, dim3((packed + 255) / 256, nb), dim3(256), 0, s, a, w.sorted_boxes, w.sorted_scores, ww.n);
@@ -1930,35 +1680,15 @@ extern "C" int eod_centernet_proposals(const EodProposalDesc* d, eod_stream_t st
   if (d->levels < 1 || d->levels > 5 || d->pre_nms_topk < 1 || d->head_stride < 5) return EOD_ERR_BAD_DIMS;
   const int slots = d->levels * d->pre_nms_topk;
   if (slots > 8192) return centernet_proposals_wide(d, (hipStream_t)stream);
-  for (int l = 0; l < d->levels; ++l) {
-    const int n = d->level_off[l + 1] - d->level_off[l];
-    if (n <= 0 || n > EOD_SORT_MAX || d->level_w[l] <= 0 || n % d->level_w[l] != 0) return EOD_ERR_CAPACITY;
-  }
-  if (d->cap < d->post_nms_topk || d->cap > NMS_KEPT_MAX) return EOD_ERR_CAPACITY;
   const int nb = d->batch > 1 ? d->batch : 1;
+  CnArgs a{};
+  if (const int err = cn_args(d, nb, &a)) return err;
+  if (d->cap < d->post_nms_topk || d->cap > NMS_KEPT_MAX) return EOD_ERR_CAPACITY;
   if (nb > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
   const SelWs w = carve(d->workspace, slots * nb, slots, slots * nb);
   if (d->workspace_bytes < w.bytes) return EOD_ERR_CAPACITY;
   hipStream_t s = (hipStream_t)stream;
-  CnArgs a{};
-  a.batch = nb;
-  a.head = d->head_out; a.head_stride = d->head_stride; a.levels = d->levels;
-  for (int l = 0; l <= d->levels; ++l) a.level_off[l] = d->level_off[l];
-  for (int l = 0; l < d->levels; ++l) {
-    a.level_w[l] = d->level_w[l];
-    a.level_stride[l] = d->level_stride[l];
-    a.level_scale[l] = d->level_scale[l];
-  }
-  a.score_thresh = d->score_thresh; a.topk = d->pre_nms_topk; a.cand_keys = w.cand_keys; a.cand_cnt = w.cand_cnt;
-  // the per-level candidate lists are packed: level l holds at most min(level size, topk) entries
-  a.pk_off[0] = 0;
-  for (int l = 0; l < d->levels; ++l) a.pk_off[l + 1] = a.pk_off[l] + std::min(d->level_off[l + 1] - d->level_off[l], d->pre_nms_topk);
-  int max_level = 0;
-  for (int l = 0; l < d->levels; ++l) max_level = std::max(max_level, d->level_off[l + 1] - d->level_off[l]);
-  if (max_level <= 8192)
-    hipLaunchKernelGGL(cn_level_topk_kernel<8>, dim3(d->levels, nb), dim3(1024), 0, s, a);
-  else
-    hipLaunchKernelGGL(cn_level_topk_kernel<16>, dim3(d->levels, nb), dim3(1024), 0, s, a);
+  cn_launch_level_topk(&a, w, s);
   ScanOut o{d->out_boxes, d->out_scores, nullptr, nullptr, d->out_count, d->cap, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
   if (a.pk_off[d->levels] <= 4096)
     hipLaunchKernelGGL(cn_merge_nms_kernel<4>, dim3(nb), dim3(1024), 0, s, a, w.sorted_boxes, w.sorted_scores, d->nms_thresh,
@@ -1979,23 +1709,30 @@ extern "C" size_t eod_detections_workspace_bytes(int R_cap, int C1) {
   return carve(nullptr, slots, slots, 0).bytes;
 }
 
+// the outputs of a detection call as the kernels take them; the optional lists need their counts (and the unique list a capacity)
+static int det_outputs(const EodDetDesc* d, ScanOut* o) {
+  if (d->out_unique_rows && (!d->out_unique_count || d->unique_cap <= 0)) return EOD_ERR_BAD_DIMS;
+  if (d->out_rep_of && (!d->out_rep_list || !d->out_rep_count)) return EOD_ERR_BAD_DIMS;
+  *o = ScanOut{d->out_boxes, d->out_scores, d->out_classes, d->out_rows, d->out_count, d->topk, d->out_unique_rows, d->out_unique_count,
+               d->unique_cap, d->out_rep_of, d->out_rep_list, d->out_rep_count};
+  return EOD_OK;
+}
+
 extern "C" int eod_fast_rcnn_inference(const EodDetDesc* d, eod_stream_t stream) {
   if (!d || !d->boxes || !d->scores || !d->out_boxes || !d->out_scores || !d->out_classes || !d->out_rows || !d->out_count ||
       !d->workspace)
     return EOD_ERR_NULL;
   if (d->R_cap <= 0 || d->R_cap > DET_MAX_R || d->C1 < 2 || d->C1 - 1 > DETW_MAX_C || d->topk <= 0 || d->topk > NMS_KEPT_MAX)
     return EOD_ERR_BAD_DIMS;
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = d->batch > 1 ? d->batch : 1;
+  ScanOut o{};
   if (det_is_wide(d->R_cap, d->C1)) {
-    const int nb = d->batch > 1 ? d->batch : 1;
     if (nb > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
     const DetwWs w = carve_detw(d->workspace, d->C1 - 1, EOD_MAX_BATCH);
     if (d->workspace_bytes < w.bytes) return EOD_ERR_CAPACITY;
-    if (d->out_unique_rows && (!d->out_unique_count || d->unique_cap <= 0)) return EOD_ERR_BAD_DIMS;
-    if (d->out_rep_of && (!d->out_rep_list || !d->out_rep_count)) return EOD_ERR_BAD_DIMS;
+    if (const int err = det_outputs(d, &o)) return err;
     if (!eod_aligned16(d->workspace)) return EOD_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    ScanOut o{d->out_boxes, d->out_scores, d->out_classes, d->out_rows, d->out_count, d->topk, d->out_unique_rows, d->out_unique_count,
-              d->unique_cap, d->out_rep_of, d->out_rep_list, d->out_rep_count};
     const dim3 grid((d->R_cap + 1) / 2, nb);
     hipLaunchKernelGGL(detw_hist_kernel, grid, dim3(256), 0, s, d->boxes, d->scores, d->count, d->R_cap, d->C1, d->score_thresh, w);
     hipLaunchKernelGGL(detw_compact_kernel, grid, dim3(256), 0, s, d->scores, d->count, d->R_cap, d->C1, d->score_thresh, w);
@@ -2006,13 +1743,11 @@ extern "C" int eod_fast_rcnn_inference(const EodDetDesc* d, eod_stream_t stream)
   const int slots = d->R_cap * (d->C1 - 1);
   const SelWs w = carve(d->workspace, slots, slots, 0);
   if (d->workspace_bytes < w.bytes) return EOD_ERR_CAPACITY;
-  hipStream_t s = (hipStream_t)stream;
-  if (d->out_unique_rows && (!d->out_unique_count || d->unique_cap <= 0 || d->R_cap > NMS_KEPT_MAX)) return EOD_ERR_BAD_DIMS;
-  if (d->out_rep_of && (!d->out_rep_list || !d->out_rep_count || d->R_cap > NMS_KEPT_MAX)) return EOD_ERR_BAD_DIMS;
-  ScanOut o{d->out_boxes, d->out_scores, d->out_classes, d->out_rows, d->out_count, d->topk, d->out_unique_rows, d->out_unique_count,
-            d->unique_cap, d->out_rep_of, d->out_rep_list, d->out_rep_count};
-  if (d->batch > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
-  hipLaunchKernelGGL(det_select_kernel, dim3(d->batch > 1 ? d->batch : 1), dim3(1024), 0, s, d->boxes, d->scores, d->count, d->R_cap, d->C1, d->img_w, d->img_h,
+  // (the single-workgroup kernel's row flags cover NMS_KEPT_MAX rows)
+  if ((d->out_unique_rows || d->out_rep_of) && d->R_cap > NMS_KEPT_MAX) return EOD_ERR_BAD_DIMS;
+  if (const int err = det_outputs(d, &o)) return err;
+  if (nb > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
+  hipLaunchKernelGGL(det_select_kernel, dim3(nb), dim3(1024), 0, s, d->boxes, d->scores, d->count, d->R_cap, d->C1, d->img_w, d->img_h,
                      d->score_thresh, d->nms_thresh, d->topk, o);
   return eod_launch_status();
 }
