@@ -164,6 +164,9 @@ __device__ __forceinline__ void store_wave_tiles(const ConvArgs& p, const f32x16
 void launch_conv_fp32(const ConvArgs& a, int tile, int bk, bool tap4, dim3 grid, hipStream_t s, int lds_reserve = 0, int prefetch2 = 0);
 void launch_conv_bf16x3(const ConvArgs& a, int tile, dim3 grid, hipStream_t s);
 void launch_conv_wavek(const ConvArgs& a, int nw, dim3 grid, hipStream_t s);
+// 1x1 stride-1 fp32 layers with Kpad in {64, 128, 256} (conv_pointwise.hip): a workgroup owns 64 rows x np panels of 64 columns;
+// a.tiles_n = panel groups per row tile
+void launch_conv_pointwise(const ConvArgs& a, int np, dim3 grid, hipStream_t s);
 void launch_split_weights(const float* w, void* out, int Cout, int Kpad, hipStream_t s);
 // f16 operands, fp32 accumulate: tile 3 = 64x64 (4 waves), 4 = 256x128 (8 waves); bk 64 or 32
 void launch_conv_f16(const ConvArgs& a, int tile, int bk, dim3 grid, hipStream_t s);

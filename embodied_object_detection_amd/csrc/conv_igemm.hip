@@ -3,7 +3,7 @@
 //   y[m][n] = act( (sum_k A[m][k] * Wt[n][k] + bias[n]) * out_scale + res[m][n] )
 //
 // A[m][k] is the im2col view of the NHWC input (m = (img, oy, ox), k = (ky, kx, c), c fastest), Wt is [Cout][Kpad].  The kernels
-// live in conv_fp32.hip (fp32 MFMA, default), conv_bf16x3.hip (opt-in split-bf16 arithmetic) and conv_f16.hip (opt-in: operands rounded
+// live in conv_fp32.hip (fp32 MFMA, default), conv_pointwise.hip (the trunk's shallow-K 1x1 layers, fp32), conv_bf16x3.hip (opt-in split-bf16 arithmetic) and conv_f16.hip (opt-in: operands rounded
 // to half, fp32 accumulate); this file picks one, sizes the grid and, for small problems, splits K into fp32 slabs that
 // conv_splitk_reduce_kernel sums in a fixed order before the fused epilogue (deterministic, no atomics).
 #include "conv_common.h"
@@ -141,7 +141,22 @@ struct Plan {
   int glds;  // 2: bf16x3 split kernel (BK = 32); 3: f16 kernel (BK = 32; 64 by force_tile 8x); 0: fp32 MFMA kernel
   int bm, bn, tiles_m, tiles_n, splitk, cps, nchunks;
   int wavek;  // 0, or the number of waves (4 / 8) of the 32x32-tile kernel that splits K over the waves of a workgroup
+  int pw_np;  // 0, or the 64-column panels per workgroup of the pointwise kernel (conv_pointwise.hip; tile 6, bn = 64 * pw_np)
 };
+
+// force_tile code of the pointwise kernel: forces it on a call it can take (pointwise_eligible), EOD_ERR_BAD_DIMS for any other
+constexpr int kForcePointwise = 30;
+
+int effective_math(const EodConvDesc* d) { return d->math > 0 ? d->math - 1 : math_mode().load(std::memory_order_relaxed); }
+
+// What conv_pointwise_kernel takes: fp32 arithmetic, a 1x1 stride-1 image-mode layer whose whole K is 64, 128 or 256, whole
+// 64-column panels, the plain or same-shape-residual epilogue and a static row count.
+bool pointwise_eligible(const EodConvDesc* d) {
+  return effective_math(d) == EOD_MATH_FP32 && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->levels <= 0 && !d->tap4 &&
+         d->Cin == d->Kpad && (d->Cin == 64 || d->Cin == 128 || d->Cin == 256) && d->Cout % 64 == 0 && d->out_mode == 0 &&
+         (d->res_mode == 0 || d->res_mode == 1) && !d->in_relu && !d->gate && !d->m_count && d->split_n == 0 && !d->gn_partial &&
+         d->lds_reserve == 0;
+}
 
 Plan make_plan(const EodConvDesc* d, int M) {
   // 256x128: bf16x3 / f16 8-wave kernels only; 64x256: fused mask-head tail (out_mode 2) only
@@ -163,7 +178,7 @@ Plan make_plan(const EodConvDesc* d, int M) {
   // tile and split-K are decided on `plan_rows` when given (a batch planned like one image: identical K walk, bitwise equal results)
   const int Mp = (d->plan_rows > 0 && d->plan_rows < M) ? d->plan_rows : M;
   // EodConvDesc.math: this call's arithmetic (EOD_MATH_* + 1), 0 = the process-wide mode
-  const int math = d->math > 0 ? d->math - 1 : math_mode().load(std::memory_order_relaxed);
+  const int math = effective_math(d);
   if (d->force_tile == 0 && math == EOD_MATH_F16 && half_ok) {
     pl.glds = 3;
     // like bf16x3: the 8-wave 256x128 tile once it fills the chip, else the finest tile; decided on plan_rows like the slabs
@@ -253,6 +268,41 @@ Plan make_plan(const EodConvDesc* d, int M) {
   if (splitk > nchunks) splitk = nchunks;
   pl.cps = (nchunks + splitk - 1) / splitk;
   pl.splitk = (nchunks + pl.cps - 1) / pl.cps;
+  // The shallow-K pointwise layers of the trunk (conv_pointwise.hip; bitwise the 64x64 kernel's results, so the choice may differ
+  // between a batch and its single images).  The planner's own choice takes the launches the generic plan runs as plain 64x64
+  // tiles that fill the chip (>= 256 tiles on plan_rows, no slabs): measured per class in profiles/r15_pointwise_layers.txt.
+  // K = 256 with one or two 64-column panels (layer1.{1,2}.conv1, layer2.0.conv1) stays generic: a workgroup fetches its whole
+  // 64 KB activation tile before its first MFMA and has 1-2 panels to use it for.  Faster at 25 600 rows (18.5 against 20.0 us,
+  // 28.1 against 29.9) but not at 51 200 (31.4 against 29.9; 46.3 against 46.8, within the parent's spread).  Of K = 256 only the
+  // measured winner goes over: 16 panels and more (layer3's conv3, 17 against 26 us).
+  const bool pw_forced = d->force_tile == kForcePointwise && d->force_splitk <= 1;          // check_desc has refused the others
+  const bool pw_auto = d->force_tile == 0 && d->force_splitk == 0 && pointwise_eligible(d) && pl.splitk == 1 && !pl.wavek && tiles >= 256 &&
+                       !(d->Kpad == 256 && d->Cout < 1024);
+  if (pw_forced || pw_auto) {
+    // panels per workgroup: as many (up to 4: one fetch of the activation tile serves them all) as leave >= 512 workgroups
+    const int panels = d->Cout / 64;
+    const long row_tiles = (Mp + 63) / 64;
+    // (forced below the 256 tiles of the planner's own choice -- tests: no grid target, so that small shapes walk the panel loop)
+    const long want = tiles >= 256 ? 512 : 1;
+    int np = 1;
+    for (int cand = 4; cand > 1; cand >>= 1)
+      if (panels >= cand && row_tiles * ((panels + cand - 1) / cand) >= want) {
+        np = cand;
+        break;
+      }
+    pl.pw_np = np;
+    pl.tile = 6;
+    pl.glds = 0;
+    pl.bk = 32;
+    pl.nchunks = d->Kpad / 32;
+    pl.bm = 64;
+    pl.bn = 64 * np;
+    pl.tiles_m = (M + 63) / 64;
+    pl.tiles_n = (panels + np - 1) / np;
+    pl.splitk = 1;
+    pl.cps = pl.nchunks;
+    pl.wavek = 0;
+  }
   return pl;
 }
 
@@ -313,6 +363,7 @@ int check_desc(const EodConvDesc* d) {
   if (d->math < 0 || d->math > EOD_MATH_F16 + 1) return EOD_ERR_BAD_DIMS;
   if ((d->force_tile / 10 == 8 || d->force_tile / 10 == 9) && d->force_tile % 10 != 3 && d->force_tile % 10 != 4) return EOD_ERR_BAD_DIMS;
   if (d->lds_reserve < 0 || d->lds_reserve > 48 * 1024) return EOD_ERR_BAD_DIMS;
+  if (d->force_tile == kForcePointwise && (!pointwise_eligible(d) || d->force_splitk > 1)) return EOD_ERR_BAD_DIMS;
   if (d->split_n != 0) {
     if (!d->y2) return EOD_ERR_NULL;
     if (d->split_n < 0 || d->split_n >= d->Cout || d->out_mode != 0 || d->res_mode != 0 || d->levels > 0 || d->gn_partial)
@@ -441,7 +492,8 @@ extern "C" int eod_conv2d(const EodConvDesc* d, eod_stream_t stream) {
     if (!d->workspace || d->workspace_bytes < need) return EOD_ERR_CAPACITY;
   }
   dim3 grid(pl.tiles_m * pl.tiles_n, pl.splitk);
-  if (pl.wavek) launch_conv_wavek(a, pl.wavek, grid, s);
+  if (pl.pw_np) launch_conv_pointwise(a, pl.pw_np, grid, s);
+  else if (pl.wavek) launch_conv_wavek(a, pl.wavek, grid, s);
   else if (pl.glds == 3) launch_conv_f16(a, pl.tile, pl.bk, grid, s);
   else if (pl.glds == 2) launch_conv_bf16x3(a, pl.tile, grid, s);
   else launch_conv_fp32(a, pl.tile, pl.bk, d->tap4 != 0, grid, s, d->lds_reserve, d->prefetch2);

@@ -71,7 +71,12 @@ typedef struct EodConvDesc {
                         predictor (see fuse_w below) */
   int32_t tap4;      /* 1: Cin == 4 (stem, RGB padded to 4): one float4 per tap */
   int32_t force_tile; /* 0 auto, else tile + 10 * variant: tile 1=128x128 2=128x64 3=64x64; variant 0 default, 1 BK=32, 2 BK=64,
-                         5 bf16x3 split math; 6 / 7: the 32x32-tile kernel that splits K over 4 / 8 waves (benchmarks/tests) */
+                         5 bf16x3 split math; 6 / 7: the 32x32-tile kernel that splits K over 4 / 8 waves (benchmarks/tests);
+                         30: the pointwise kernel (fp32 arithmetic, 1x1 stride 1 pad 0, image mode, Cin == Kpad in {64, 128, 256},
+                         Cout % 64 == 0, out_mode 0, res_mode 0 / 1, none of in_relu / gate / m_count / split_n / gn_partial /
+                         lds_reserve, force_splitk 0 or 1); EOD_ERR_BAD_DIMS for a call it cannot take.  The planner gives such a
+                         call that kernel by itself when the generic plan has >= 256 tiles of 64x64 (at Kpad 256: and Cout >= 1024); its
+                         results are bitwise those of the 64x64 kernel (force_tile 13) */
   int32_t force_splitk; /* 0 auto */
   float out_scale;
   /* pyramid mode (levels > 0): x / y are [level_off[levels], C] row lists, level l is a level_h[l] x level_w[l] image;
@@ -138,7 +143,8 @@ size_t eod_conv2d_workspace_bytes(const EodConvDesc* d);
 /* The plan eod_conv2d(d) would run, read back without launching anything (tests and tools: which kernel does a layer get at this
  * shape, in the current arithmetic mode?).  The same planner call the launch makes; EOD_ERR_* for a descriptor eod_conv2d refuses. */
 typedef struct EodConvPlan {
-  int32_t tile;             /* 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 256x128 (bf16x3 and f16 only), 5 = 64x256 (out_mode 2 only) */
+  int32_t tile;             /* 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 256x128 (bf16x3 and f16 only), 5 = 64x256 (out_mode 2 only),
+                               6 = pointwise kernel: 64 rows x bn / 64 panels of 64 columns per workgroup, tiles_n = panel groups */
   int32_t bm, bn, bk;       /* rows x columns of a workgroup's output tile (32 x 32 with wavek), K chunk per barrier pair */
   int32_t splitk, cps, nchunks; /* K slabs summed by the reduce launch (1 = none), chunks per slab, Kpad / bk */
   int32_t wavek;            /* 0, or the waves (4 / 8) the 32x32-tile kernel splits K over */
