@@ -25,6 +25,7 @@ _ERR = {-1: "EOD_ERR_BAD_DIMS", -2: "EOD_ERR_ALIGN", -3: "EOD_ERR_LAUNCH", -4: "
 
 MAX_BATCH = 8       # EOD_MAX_BATCH
 MAX_LEVELS = 40     # EOD_MAX_LEVELS
+SEMMAP_SCORES = 0x10000     # EOD_SEMMAP_SCORES: the flag bit on `D` of eod_semmap_labels (any vocabulary, label + confidence)
 
 
 class EodConvDesc(C.Structure):

@@ -64,6 +64,15 @@ class EmbodiedPredictor:
         assert self.input_format in ("RGB", "BGR"), self.input_format
         self.max_size = int(cfg.INPUT.MAX_SIZE_TEST)
 
+    def semantic_map(self, vocabulary: Optional[str] = None, classifier=None, thresh: Optional[float] = None) -> Dict:
+        """The spatial memory as it stands, read as a map: `{"labels": int32 [N], "scores": float32 [N]}`, per cell the most likely
+        class (-1 below `thresh`; None: MEMORY_OBS_SCORE_THRESH) and its softmax probability.  `vocabulary` / `classifier` as in the
+        constructor; neither: the memory's own class matrix.  The model, its heads and the memory are left as they are."""
+        if vocabulary is not None and classifier is None:
+            classifier = resolve_vocabulary(vocabulary)
+        labels, scores = self.model.semantic_map(classifier=classifier, thresh=thresh, scores=True)
+        return {"labels": labels, "scores": scores}
+
     def _resized_hw(self, h: int, w: int):
         """`ResizeShortestEdge([480, 480], max_size).get_output_shape`."""
         scale = 480.0 / min(h, w)

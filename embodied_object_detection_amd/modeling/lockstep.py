@@ -36,7 +36,7 @@ import torch
 
 from .. import _lib, ops
 from ..structures import Boxes, Instances
-from .meta_arch import CustomRCNNRecurrent, _det_stream, _sched_streams
+from .meta_arch import CustomRCNNRecurrent, _det_stream, _sched_streams, _semmap_query
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
 RESULT_SETS = 3
@@ -220,6 +220,19 @@ class LockstepScenes:
 
     def invalidate_memory_snapshot(self):
         self._f16_valid = False
+
+    def semantic_map(self, scene: int, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None,
+                     scores: bool = False):
+        """`CustomRCNNRecurrent.semantic_map` on scene `scene`'s state: the labels, or with `classifier` / `scores=True` the
+        `(labels, scores)` of a query in any vocabulary.  Nothing of the batch model changes."""
+        if not 0 <= int(scene) < self.B:
+            raise IndexError(f"scene {scene} of a lock-step batch of {self.B}")
+        if self.implicit_memory is None:
+            raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
+        mem, obs, m = self.implicit_memory[int(scene)], self.observations[int(scene)], self.model
+        if classifier is None and not scores:
+            return ops.semmap_labels(mem, obs, m.zs_weight, m.obs_score_thresh if thresh is None else float(thresh))
+        return _semmap_query(m, mem, obs, classifier, num_classes, thresh)
 
     def _refresh_snapshot(self):
         """a4 + fp16 cast for the B tables: they are one [B*N,512] table to the kernels."""

@@ -25,6 +25,7 @@ from .. import _lib, ops
 from ..checkpoint import fill_missing, load_checkpoint, load_zs_weight, reset_cls_test, synthetic_state_dict
 from ..registry import BACKBONE_REGISTRY, META_ARCH_REGISTRY, PROPOSAL_GENERATOR_REGISTRY, ROI_HEADS_REGISTRY
 from ..structures import Boxes, Instances
+from .utils import query_classifier
 
 
 # The scheduling streams are created ONCE per device and shared by every model of the process: HIP multiplexes streams onto a
@@ -62,6 +63,16 @@ def _det_stream(device: torch.device) -> torch.cuda.Stream:
     if idx not in _DET_STREAMS:
         _DET_STREAMS[idx] = torch.cuda.Stream(device=device, priority=0)
     return _DET_STREAMS[idx]
+
+
+def _semmap_query(model, mem, obs, classifier, num_classes, thresh):
+    """`semantic_map` in query form on one scene's state (`model`: the single-scene model that holds the configuration)."""
+    if mem is None:
+        raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
+    zs = model.zs_weight
+    if classifier is not None:
+        zs = query_classifier(classifier, num_classes, bool(getattr(model.roi_heads, "norm_weight", True)), model.device)
+    return ops.semmap_query(mem, obs, zs, model.obs_score_thresh if thresh is None else float(thresh))
 
 
 @META_ARCH_REGISTRY.register()
@@ -729,11 +740,19 @@ class CustomRCNNRecurrent:
         P["boxes"] = P["scores"] = P["classes"] = P["masks"] = None
         return inst
 
-    def semantic_map(self) -> torch.Tensor:
+    def semantic_map(self, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None, scores: bool = False):
         """a20, evaluated lazily: the explicit map `self.semmap` the reference recomputes (and syncs to the host) every
-        frame (custom_rcnn.py:756) but only consumes when MODEL.TEST_SAVE_SEMMAP dumps it (518-530)."""
-        self.semmap = ops.semmap_labels(self.implicit_memory, self.observations, self.zs_weight, self.obs_score_thresh)
-        return self.semmap
+        frame (custom_rcnn.py:756) but only consumes when MODEL.TEST_SAVE_SEMMAP dumps it (518-530).
+
+        With `classifier` (a `[C, 512]` .npy path or a `[512, C]` tensor of up to 2047 classes, as `reset_cls_test` takes it) or
+        `scores=True` the memory is read as it stands in that vocabulary (default: the meta-architecture's own) and the call returns
+        `(labels, scores)`: per cell the argmax class, -1 below `thresh` (None: MEMORY_OBS_SCORE_THRESH; 0.0 keeps every cell), and
+        the softmax probability of that class (`max_scores`, custom_rcnn.py:955-958).  Such a query changes nothing in the model."""
+        if classifier is None and not scores:
+            self.semmap = ops.semmap_labels(self.implicit_memory, self.observations, self.zs_weight,
+                                            self.obs_score_thresh if thresh is None else float(thresh))
+            return self.semmap
+        return _semmap_query(self, self.implicit_memory, self.observations, classifier, num_classes, thresh)
 
     # ---- introspection used by tests / bench -----------------------------------------------------------
     def proposals_snapshot(self):

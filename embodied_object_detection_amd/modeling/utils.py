@@ -29,6 +29,17 @@ def load_classifier(cls_path_or_tensor: Union[str, torch.Tensor], num_classes: i
     return w.contiguous()
 
 
+def query_classifier(classifier: Union[str, torch.Tensor], num_classes, norm_weight: bool, device) -> torch.Tensor:
+    """The class matrix of a one-off memory query (`semantic_map(classifier=...)`): `load_classifier` with `num_classes` read off the
+    matrix when not given, on `device`.  Nothing of a model is touched."""
+    if num_classes is None:
+        if isinstance(classifier, torch.Tensor):
+            num_classes = int(classifier.shape[1])
+        else:
+            num_classes = int(np.load(classifier, mmap_mode="r").shape[0])
+    return load_classifier(classifier, int(num_classes), norm_weight).to(device)
+
+
 def reset_cls_test(model, cls_path_or_tensor: Union[str, torch.Tensor], num_classes: int) -> None:
     """Works on the single-scene model and on the lock-step batch model, between two frames of a running sequence: the memory is
     not reset.  Vocabularies of 1 to 2047 classes; up to 23 classes the heads run the narrow kernels they ran before."""

@@ -1339,3 +1339,20 @@ def semmap_labels(mem: torch.Tensor, obs: torch.Tensor, zs: torch.Tensor, thresh
     check(_lib.load().eod_semmap_labels(mem.data_ptr(), obs.data_ptr(), zs.data_ptr(), N, D, zs.shape[1], thresh, labels.data_ptr(),
                                         ws.data_ptr(), _stream()), "eod_semmap_labels")
     return labels
+
+
+def semmap_query(mem: torch.Tensor, obs: torch.Tensor, zs: torch.Tensor, thresh: float):
+    """The map in any vocabulary the heads accept (EOD_SEMMAP_SCORES; `zs` [512, C1], C1 <= 2048, on the fp32 matrix cores):
+    (labels int32 [N] as `semmap_labels` defines them, scores float32 [N]: the softmax probability of the cell's argmax class over
+    the first C1-1 columns, for every cell, thresholded or not).  `scores` is a view into the call's workspace."""
+    N, D = mem.shape
+    if zs.dim() != 2 or zs.shape[0] != 512 or not zs.is_contiguous() or zs.dtype != torch.float32:
+        raise _lib.EodError(f"semmap_query: class matrix {tuple(zs.shape)} {zs.dtype}: expected contiguous float32 [512, C1]")
+    C1 = int(zs.shape[1])
+    if C1 > ZS_WIDE_MAX_C1:
+        raise _lib.EodError(f"semmap_query: {C1 - 1} classes + background exceed the kernel's {ZS_WIDE_MAX_C1} columns")
+    labels = torch.empty((N,), dtype=torch.int32, device=mem.device)
+    ws = torch.empty((2 * N + 4,), dtype=torch.float32, device=mem.device)
+    check(_lib.load().eod_semmap_labels(mem.data_ptr(), obs.data_ptr(), zs.data_ptr(), N, D | _lib.SEMMAP_SCORES, C1, thresh,
+                                        labels.data_ptr(), ws.data_ptr(), _stream()), "eod_semmap_labels")
+    return labels, ws[4 + N:]

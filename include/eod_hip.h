@@ -685,8 +685,16 @@ int eod_memory_write_init(void* workspace, size_t workspace_bytes, int H, int W,
                           eod_stream_t stream);
 
 /* a20: explicit semantic map from the implicit memory (custom_rcnn.py:745-756,938-1017), evaluated lazily (only
- * consumed when TEST_SAVE_SEMMAP): labels[c] = argmax over the first C1-1 classes of (50*mem/|mem|)@zs, or -1 where the
- * min-max normalised observation intensity mean|mem| (/obs if obs>1) is below thresh.  workspace >= n_cells + 4 floats. */
+ * consumed when TEST_SAVE_SEMMAP): labels[c] = argmax over the first C1-1 classes of (50*mem/|mem|)@zs (ties: the lowest class),
+ * or -1 where the min-max normalised observation intensity mean|mem| (/obs if obs>1) is below thresh.  D is 512.
+ * workspace >= n_cells + 4 floats; the intensities are left at workspace + 4.
+ *
+ * D = 512 | EOD_SEMMAP_SCORES reads the map in any vocabulary the heads accept, with a confidence: 2 <= C1 <= 2048
+ * (EOD_ERR_CAPACITY beyond), the product runs as a GEMM on the fp32 matrix cores, `labels` means the same (labels of near-tied
+ * classes may differ from the plain call's by summation order; the -1 set and the intensities are the plain call's bits), and
+ * workspace >= 2*n_cells + 4 floats: workspace + 4 + n_cells receives scores[n_cells], the softmax probability of the cell's argmax
+ * class over those C1-1 columns, for every cell (the threshold touches `labels` only).  Without the bit nothing changes. */
+#define EOD_SEMMAP_SCORES 0x10000
 int eod_semmap_labels(const float* mem, const float* obs, const float* zs, int n_cells, int D, int C1, float thresh,
                       int32_t* labels, float* workspace, eod_stream_t stream);
 
