@@ -4,6 +4,7 @@
 // conv_operands.h, which includes this file.  Planning, argument checks and the C ABI live in conv_igemm.hip.
 #pragma once
 #include "eod_common.h"
+#include "conv_border_order.h"
 #include "../../include/eod_hip.h"
 
 namespace eodconv {
@@ -41,6 +42,10 @@ struct ConvArgs {
   float* y2;                   // optional second output: columns [split_n, Cout) go to y2 [M, Cout - split_n] (with the ReLU), columns
   int split_n;                 // [0, split_n) to y [M, split_n] (never with the ReLU): two linear layers on one input as one GEMM
   FastDiv div_ow, div_oh, div_cd, div_row;
+  // border-major row order of the 64x64 fp32 kernel (conv_fp32.hip): set by the planner, with the divisors OH - 2, OW - 2 and
+  // (OH - 2) * (OW - 2) of border_row()
+  int border;
+  FastDiv div_bh, div_bw, div_bi;
 };
 
 // Rows that hold work under the device-side count.  One count: rows [0, count * m_unit).  m_segs > 1 (independent ROI lists back to
@@ -68,6 +73,18 @@ __device__ __forceinline__ bool conv_tile_active(const ConvArgs& p, int m0, int 
   for (int s = s0 + 1; s <= s1; ++s)
     if (p.m_count[s] > 0) return true;
   return false;
+}
+
+// ---- border-major row order: conv_border_order.h; what follows reads it from the launch arguments ------------------------
+// live maps of a border-order launch: conv_row_limit() / m_unit (m_unit == OH * OW, one count: make_plan)
+__device__ __forceinline__ int border_rois(const ConvArgs& p) {
+  const int c = *p.m_count;
+  return c < p.N ? c : p.N;
+}
+// storage row (pixel index) of logical row m
+__device__ __forceinline__ int border_storage_row(const ConvArgs& p, int m, int rois) {
+  const BorderRow b = border_row(m, rois, p.OH, p.OW, p.div_ow, p.div_bh, p.div_bw, p.div_bi);
+  return (b.img * p.OH + b.oy) * p.OW + b.ox;
 }
 
 // GATE: the kernel honours ConvArgs.gate (the 64x64 fp32 tile, the wave-K kernel and the slab reduces: the plans a gated layer is
@@ -132,11 +149,13 @@ __device__ __forceinline__ unsigned long long tap_mask(int iy0, int ix0, int hh,
 }
 
 // Stores one wave's accumulators (TM x TN tiles of 32x32, MFMA C/D layout: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5))
-// through the fused epilogue, or as a split-K slab.
-template <int TM, int TN, bool GATE = false>
+// through the fused epilogue, or as a split-K slab.  BORDER: m is a logical row of the border-major order (plain epilogue, no
+// slabs: make_plan), stored at its pixel's row.
+template <int TM, int TN, bool GATE = false, bool BORDER = false>
 __device__ __forceinline__ void store_wave_tiles(const ConvArgs& p, const f32x16 (&acc)[TM][TN], int m_base, int n_base, int M, int z,
                                                  int lane) {
   const int half = lane >> 5;
+  const int rois = BORDER ? border_rois(p) : 0;
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -148,7 +167,9 @@ __device__ __forceinline__ void store_wave_tiles(const ConvArgs& p, const f32x16
         const int m = m_base + i * 32 + row;
         if (m < M && n < p.Cout && conv_row_active(p, m)) {
           const float v = acc[i][j][r];
-          if (p.splitk > 1) {
+          if (BORDER) {
+            epilogue_store<GATE>(p, v, border_storage_row(p, m, rois), n);
+          } else if (p.splitk > 1) {
             p.partial[((size_t)z * p.M + m) * p.Cout + n] = v;
           } else {
             epilogue_store<GATE>(p, v, m, n);

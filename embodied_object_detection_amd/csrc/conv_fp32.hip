@@ -18,6 +18,13 @@
 // remap so that the workgroups sharing an L2 walk neighbouring tiles (same weight panel / same pixel rows).
 // Small problems are split along K (grid.y) into fp32 slabs reduced by a second kernel that also applies the
 // epilogue: deterministic, no atomics.
+//
+// BORDER (the mask head's 3x3 convs: 64x64 tile, BK 32, a ROI list under a device-side count): the launch's rows are dealt in the
+// border-major order of conv_border_order.h, so that most tiles of the four border regions hold only rows for which the same three filter
+// taps lie in the zero padding.  The workgroup ORs the tap masks of its rows into one "live taps" word and walks only the chunks of
+// live taps.  A chunk that is left out would have added fma(0, w, acc) to every element of the tile: for finite weights (0 * w is
+// a zero, and an accumulator that starts at +0 never becomes -0) the result is bitwise that of the pixel-major order.  With an
+// infinite or NaN weight under a padding tap the pixel-major kernel gives NaN where this order gives the sum of the live taps.
 #include "conv_operands.h"
 
 namespace eodconv {
@@ -28,8 +35,11 @@ namespace {
 // MFMAs; one more chunk of prefetch hides it.
 // PIPE 2: the operand tiles are double buffered in LDS -- chunk c+1 is written to the other buffer while chunk c is multiplied: ONE
 // workgroup barrier per chunk instead of two, at twice the LDS (36 KB for 64x64: 4 workgroups per CU).
+// PIPE 3: the default pipeline (PIPE 0) with the border-major row order (BORDER above).
 template <int BM, int BN, int BK, bool TAP4, bool MULTI, int PIPE = 0>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
+  constexpr bool BORDER = PIPE == 3;
+  static_assert(!BORDER || (BM == 64 && BN == 64 && BK == 32 && !TAP4 && !MULTI), "border-major order: the plain 64x64 kernel");
   constexpr bool PF2 = PIPE == 1;
   constexpr bool DB = PIPE == 2;
   constexpr int LS = BK + 4;  // LDS row stride in floats (+4: conflict-free 16-lane groups of ds_read_b128)
@@ -48,11 +58,15 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  int M;
-  const int t = conv_first_tile<BM>(p, M);
-  if (t < 0) return;
-  const int tile_m = t / p.tiles_n;
-  const int tile_n = t - tile_m * p.tiles_n;
+  int M, tile_m, tile_n;
+  if constexpr (BORDER) {
+    if (!conv_claim_tile_border<BM>(p, M, tile_m, tile_n)) return;
+  } else {
+    const int t = conv_first_tile<BM>(p, M);
+    if (t < 0) return;
+    tile_m = t / p.tiles_n;
+    tile_n = t - tile_m * p.tiles_n;
+  }
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   if (!conv_tile_active(p, m0, BM)) return;
   const int z = blockIdx.y;
@@ -65,11 +79,14 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
   unsigned a_voff[AR];
   unsigned long long a_mask[AR];
   unsigned a_pitch[MULTI ? AR : 1];
+  const int rois = BORDER ? border_rois(p) : 0;
 #pragma unroll
   for (int i = 0; i < AR; ++i) {
     const int m = m0 + lr + RPP * i;
     const bool rowok = m < M;
-    const RowOrigin o = conv_row_origin<MULTI>(p, m, rowok);
+    RowOrigin o;
+    if constexpr (BORDER) o = conv_row_origin_border(p, m, rowok, rois);
+    else o = conv_row_origin<MULTI>(p, m, rowok);
     a_iy[i] = rowok ? o.iy0 : -(1 << 28);
     a_ix[i] = o.ix0;
     a_off[i] = o.off;
@@ -81,13 +98,38 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
   const __amdgpu_buffer_rsrc_t rsrc_x = conv_buffer(p.x, p.x_bytes);
   const __amdgpu_buffer_rsrc_t rsrc_w = conv_buffer(p.w, p.w_bytes);
 
+  // BORDER: the taps that are inside the image for at least one row of the tile (rows at or past M have an empty mask), one word
+  // for the workgroup: per wave with ballots, across the waves through the not yet used tile memory.  The loop below then runs over
+  // the chunks of the live taps only: c_end counts them (one slab: c_begin is 0), the walker supplies their positions.
+  unsigned live = 0;
+  if constexpr (BORDER) {
+    unsigned mine = 0;
+#pragma unroll
+    for (int i = 0; i < AR; ++i) mine |= (unsigned)a_mask[i];
+    unsigned wv = 0;
+#pragma unroll
+    for (int tp = 0; tp < 9; ++tp) wv |= (__ballot((mine >> tp) & 1u) != 0ull ? 1u : 0u) << tp;
+    if (lane == 0) lds[wave] = __uint_as_float(wv);
+    __syncthreads();
+    live = __float_as_uint(lds[0]) | __float_as_uint(lds[1]) | __float_as_uint(lds[2]) | __float_as_uint(lds[3]);
+    live = __builtin_amdgcn_readfirstlane(live);
+    __syncthreads();        // read by everybody before the first chunk is staged over it
+    c_end = c_begin + __popc(live) * (p.Cin / BK);
+  }
+
   f32x4 ar0[AR], br0[BR];
   f32x4 ar1[PF2 ? AR : 1], br1[PF2 ? BR : 1];
   ChunkWalker<BK, MULTI> walk(p, c_begin);      // unused by the stem
   auto load_chunk = [&](int chunk, auto& ar, auto& br) {
-    const int k0 = chunk * BK;
+    int k0 = chunk * BK;
     if (!TAP4) {
+      if constexpr (BORDER) {
+        // at the first chunk of a tap that is dead for the whole tile: on to the next live one (there is one: c_end)
+        const unsigned rest = live >> walk.tap;
+        if (walk.c0 == 0 && !(rest & 1u)) walk.seek(p, walk.tap + __builtin_ctz(rest));
+      }
       const TapInfo ti = walk.next(p);
+      if constexpr (BORDER) k0 = (int)(ti.k0b >> 2);
 #pragma unroll
       for (int i = 0; i < AR; ++i) ar[i] = conv_load_a<MULTI>(rsrc_x, ti, a_voff[i], a_mask[i], a_pitch[MULTI ? i : 0]);
     } else {
@@ -269,7 +311,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
       return;
     }
   }
-  store_wave_tiles<TM, TN, BM == 64 && BN == 64>(p, acc, m0 + wm * TM * 32, n0 + wn * TN * 32, M, z, lane);
+  store_wave_tiles<TM, TN, BM == 64 && BN == 64, BORDER>(p, acc, m0 + wm * TM * 32, n0 + wn * TN * 32, M, z, lane);
 }
 
 
@@ -419,6 +461,10 @@ static void launch_fp32_tile(const ConvArgs& a, bool tap4, int bk, dim3 grid, hi
 // `lds_reserve`: dynamic LDS the launch allocates and the kernel never touches (EodConvDesc.lds_reserve): caps the workgroups per CU
 void launch_conv_fp32(const ConvArgs& a, int tile, int bk, bool tap4, dim3 grid, hipStream_t s, int lds_reserve, int prefetch2) {
   const int dyn = lds_reserve > 0 ? lds_reserve : 0;
+  if (a.border) {                                                              // make_plan: 64x64, BK 32, image mode, one slab
+    hipLaunchKernelGGL((conv_igemm_kernel<64, 64, 32, false, false, 3>), grid, dim3(256), dyn, s, a);
+    return;
+  }
   if (prefetch2 == 1 && !tap4 && a.nlv == 0 && bk == 32 && tile == 3) {      // 64x64 only: the 64x256 tail would need 256 VGPRs
     hipLaunchKernelGGL((conv_igemm_kernel<64, 64, 32, false, false, 1>), grid, dim3(256), dyn, s, a);
     return;

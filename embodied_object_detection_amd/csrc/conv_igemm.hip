@@ -142,6 +142,7 @@ struct Plan {
   int bm, bn, tiles_m, tiles_n, splitk, cps, nchunks;
   int wavek;  // 0, or the number of waves (4 / 8) of the 32x32-tile kernel that splits K over the waves of a workgroup
   int pw_np;  // 0, or the 64-column panels per workgroup of the pointwise kernel (conv_pointwise.hip; tile 6, bn = 64 * pw_np)
+  int border; // 1: the 64x64 fp32 kernel deals its rows in the border-major order and skips all-padding K chunks (conv_fp32.hip)
 };
 
 // force_tile code of the pointwise kernel: forces it on a call it can take (pointwise_eligible), EOD_ERR_BAD_DIMS for any other
@@ -156,6 +157,21 @@ bool pointwise_eligible(const EodConvDesc* d) {
          d->Cin == d->Kpad && (d->Cin == 64 || d->Cin == 128 || d->Cin == 256) && d->Cout % 64 == 0 && d->out_mode == 0 &&
          (d->res_mode == 0 || d->res_mode == 1) && !d->in_relu && !d->gate && !d->m_count && d->split_n == 0 && !d->gn_partial &&
          d->lds_reserve == 0;
+}
+
+// force_tile code of the border-major row order: forces it on a call it can take (border_eligible), EOD_ERR_BAD_DIMS for any other.
+// force_tile 13 stays the pixel-major order on every call (the A/B switch and the tests' reference).
+constexpr int kForceBorder = 43;
+// Whether the planner gives an eligible call the border-major order by itself (profiles/r16_border_order.md: the measurement the
+// default rests on).
+constexpr bool kBorderAuto = true;
+
+// What the border-major order takes: fp32 arithmetic, a 3x3 / stride 1 / pad 1 image-mode layer over maps of at least 3x3 pixels
+// whose row count is ONE device-side count of whole maps, the plain epilogue and the default pipeline.
+bool border_eligible(const EodConvDesc* d) {
+  return effective_math(d) == EOD_MATH_FP32 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->levels <= 0 && !d->tap4 &&
+         d->m_count && d->m_segments <= 1 && d->m_unit == d->OH * d->OW && d->OH >= 3 && d->OW >= 3 && d->Cin % 32 == 0 &&
+         d->out_mode == 0 && d->res_mode == 0 && !d->in_relu && !d->gate && d->split_n == 0 && !d->gn_partial && d->prefetch2 == 0;
 }
 
 Plan make_plan(const EodConvDesc* d, int M) {
@@ -303,6 +319,17 @@ Plan make_plan(const EodConvDesc* d, int M) {
     pl.cps = pl.nchunks;
     pl.wavek = 0;
   }
+  // The mask head's 3x3 convs (a ROI list of 14x14 maps under a device-side count): same tile, same plan fields, another row order
+  // inside the launch.  The planner's own choice needs the generic plan to be the plain 64x64 / BK 32 kernel without slabs; the
+  // forced code takes the slabs away (tests: small shapes).
+  const bool border_forced = d->force_tile == kForceBorder && d->force_splitk <= 1;         // check_desc has refused the others
+  const bool border_auto = kBorderAuto && d->force_tile == 0 && border_eligible(d) && pl.glds == 0 && pl.tile == 3 && pl.bk == 32 &&
+                           pl.splitk == 1 && !pl.wavek;
+  if (border_forced) {
+    pl.splitk = 1;
+    pl.cps = pl.nchunks;
+  }
+  pl.border = (border_forced || border_auto) ? 1 : 0;
   return pl;
 }
 
@@ -364,6 +391,7 @@ int check_desc(const EodConvDesc* d) {
   if ((d->force_tile / 10 == 8 || d->force_tile / 10 == 9) && d->force_tile % 10 != 3 && d->force_tile % 10 != 4) return EOD_ERR_BAD_DIMS;
   if (d->lds_reserve < 0 || d->lds_reserve > 48 * 1024) return EOD_ERR_BAD_DIMS;
   if (d->force_tile == kForcePointwise && (!pointwise_eligible(d) || d->force_splitk > 1)) return EOD_ERR_BAD_DIMS;
+  if (d->force_tile == kForceBorder && (!border_eligible(d) || d->force_splitk > 1)) return EOD_ERR_BAD_DIMS;
   if (d->split_n != 0) {
     if (!d->y2) return EOD_ERR_NULL;
     if (d->split_n < 0 || d->split_n >= d->Cout || d->out_mode != 0 || d->res_mode != 0 || d->levels > 0 || d->gn_partial)
@@ -460,6 +488,9 @@ extern "C" int eod_conv2d(const EodConvDesc* d, eod_stream_t stream) {
   a.div_oh = eod_make_fastdiv((unsigned)(d->OH > 0 ? d->OH : 1));
   a.div_row = eod_make_fastdiv((unsigned)(d->Cout % 4 == 0 ? d->Cout / 4 : d->Cout));   // split-K reduce: work items per output row
   a.div_cd = eod_make_fastdiv((unsigned)((d->Cout >> 2) > 0 ? (d->Cout >> 2) : 1));
+  a.div_bh = eod_make_fastdiv((unsigned)(d->OH > 2 ? d->OH - 2 : 1));                        // border-major order: border_row()
+  a.div_bw = eod_make_fastdiv((unsigned)(d->OW > 2 ? d->OW - 2 : 1));
+  a.div_bi = eod_make_fastdiv((unsigned)(d->OH > 2 && d->OW > 2 ? (d->OH - 2) * (d->OW - 2) : 1));
   {
     const size_t xe = d->levels > 0 ? (size_t)d->level_off[d->levels] * d->Cin : (size_t)d->N * d->H * d->W * d->Cin;
     a.x_bytes = (unsigned)(xe * sizeof(float));
@@ -487,11 +518,13 @@ extern "C" int eod_conv2d(const EodConvDesc* d, eod_stream_t stream) {
   if (d->gn_partial && pl.splitk <= 1) return EOD_ERR_BAD_DIMS;      // the statistics ride on the slab reduce (see eod_conv2d_gn_fused)
   a.nchunks = pl.nchunks;
   a.splitk = pl.splitk; a.cps = pl.cps; a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n;
+  a.border = pl.border;
   if (pl.splitk > 1) {
     const size_t need = (size_t)pl.splitk * a.M * a.Cout * sizeof(float);
     if (!d->workspace || d->workspace_bytes < need) return EOD_ERR_CAPACITY;
   }
   dim3 grid(pl.tiles_m * pl.tiles_n, pl.splitk);
+  if (pl.border) grid.x = (pl.tiles_m + 7) / 8 * 8 * pl.tiles_n;        // row tiles dealt over the XCDs in groups of 8 (conv_claim_tile_border)
   if (pl.pw_np) launch_conv_pointwise(a, pl.pw_np, grid, s);
   else if (pl.wavek) launch_conv_wavek(a, pl.wavek, grid, s);
   else if (pl.glds == 3) launch_conv_f16(a, pl.tile, pl.bk, grid, s);

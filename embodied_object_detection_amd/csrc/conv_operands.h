@@ -23,6 +23,23 @@ __device__ __forceinline__ int conv_first_tile(const ConvArgs& p, int& M) {
   return xcd_remap(blockIdx.x, ntiles);
 }
 
+// The border-major order (conv_border_order.h) claims its tiles differently.  Its cheap tiles (the border regions: 6 of 9 taps) are
+// the first row tiles of the launch; under the contiguous ranges of xcd_remap() the first two XCDs would get all of them and finish
+// early while the others take as long as before (measured: 1.4 % slower than pixel-major).  Here row tile r goes to XCD r % 8, its column tiles
+// with it (they read the same activation rows), and the LAST row tile is dispatched first: the full interior tiles start first and
+// the cheap ones fill the tail.  The grid is rounded up to whole groups of 8 row tiles (eod_conv2d).
+template <int BM>
+__device__ __forceinline__ bool conv_claim_tile_border(const ConvArgs& p, int& M, int& tile_m, int& tile_n) {
+  M = conv_row_limit(p, p.M);
+  const int live = (M + BM - 1) / BM;
+  const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+  const int g = k / p.tiles_n;
+  const int r = g * 8 + xcd;
+  tile_n = k - g * p.tiles_n;
+  tile_m = live - 1 - r;
+  return r < live;
+}
+
 // Chunks [c_begin, c_end) of share `idx` when the K chunks are dealt out `per` at a time (split-K slab z: per = p.cps; wave-K: a
 // wave's share).
 __device__ __forceinline__ int conv_chunk_range(const ConvArgs& p, int per, int idx, int& c_end) {
@@ -64,6 +81,20 @@ __device__ __forceinline__ RowOrigin conv_row_origin(const ConvArgs& p, int m, b
       o.hh = p.H;
       o.ww = p.W;
     }
+  }
+  return o;
+}
+
+// Logical row m of the border-major order (conv_border_order.h: image mode, `rois` live maps) as a window into its map.
+__device__ __forceinline__ RowOrigin conv_row_origin_border(const ConvArgs& p, int m, bool rowok, int rois) {
+  RowOrigin o = {0, 0, 0, 1, 1};
+  if (rowok) {
+    const BorderRow b = border_row(m, rois, p.OH, p.OW, p.div_ow, p.div_bh, p.div_bw, p.div_bi);
+    o.iy0 = b.oy * p.stride - p.pad;
+    o.ix0 = b.ox * p.stride - p.pad;
+    o.off = b.img * p.H * p.W;
+    o.hh = p.H;
+    o.ww = p.W;
   }
   return o;
 }
@@ -112,7 +143,8 @@ struct TapInfo {
 // re-derived with two divisions per chunk (Cin is a multiple of BK, or the chunk never straddles two taps: make_plan).  The fp32
 // kernels fetch chunk c + 1 only when it exists; the bf16x3 / f16 pipelines call next() once or twice past c_end: those chunks are
 // fetched (range-checked buffer loads) and never used, and `tap` is clamped to 63 so that the shift of the 64-bit row mask stays
-// defined for them.
+// defined for them.  seek() continues the walk at the first chunk of a given tap (image mode; Cin a multiple of BK): the
+// border-major order leaves out the taps that are padding for a whole tile.
 template <int BK, bool MULTI>
 struct ChunkWalker {
   int tap, c0, ky, kx, k0;
@@ -122,6 +154,13 @@ struct ChunkWalker {
     c0 = k0 - tap * p.Cin;
     ky = tap / p.KW;
     kx = tap - ky * p.KW;
+  }
+  __device__ __forceinline__ void seek(const ConvArgs& p, int t) {
+    tap = t;
+    c0 = 0;
+    k0 = t * p.Cin;
+    ky = t / p.KW;
+    kx = t - ky * p.KW;
   }
   __device__ __forceinline__ TapInfo next(const ConvArgs& p) {
     TapInfo ti;

@@ -76,7 +76,16 @@ typedef struct EodConvDesc {
                          Cout % 64 == 0, out_mode 0, res_mode 0 / 1, none of in_relu / gate / m_count / split_n / gn_partial /
                          lds_reserve, force_splitk 0 or 1); EOD_ERR_BAD_DIMS for a call it cannot take.  The planner gives such a
                          call that kernel by itself when the generic plan has >= 256 tiles of 64x64 (at Kpad 256: and Cout >= 1024); its
-                         results are bitwise those of the 64x64 kernel (force_tile 13) */
+                         results are bitwise those of the 64x64 kernel (force_tile 13);
+                         43: the 64x64 BK 32 kernel with the border-major row order (fp32 arithmetic, 3x3 stride 1 pad 1, image mode,
+                         OH, OW >= 3, m_count with m_segments <= 1 and m_unit == OH * OW, out_mode 0, res_mode 0, none of in_relu /
+                         gate / split_n / gn_partial / prefetch2, force_splitk 0 or 1; never slabs); EOD_ERR_BAD_DIMS for a call it
+                         cannot take.  Inside the launch the rows of all live maps are dealt border class by border class and a
+                         tile skips the K chunks of the filter taps that are zero padding for all its rows; inputs and outputs keep
+                         their layout and the plan reads tile 3 as before.  For finite weights the results are bitwise those of
+                         force_tile 13 (a skipped chunk multiplies zeros only), which keeps the pixel-major order on every call.
+                         The planner gives an eligible call this order by itself when its plan is the 64x64 BK 32 kernel without
+                         slabs */
   int32_t force_splitk; /* 0 auto */
   float out_scale;
   /* pyramid mode (levels > 0): x / y are [level_off[levels], C] row lists, level l is a level_h[l] x level_w[l] image;

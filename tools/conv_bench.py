@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmark of the implicit-GEMM conv kernel on the shapes of the hot path (GPU box only).  `modes`: the per-layer table of
-the three arithmetic modes (fp32 / bf16x3 / f16) with the planner's own choice."""
+the three arithmetic modes (fp32 / bf16x3 / f16) with the planner's own choice.  `border`: the mask head's 3x3 GEMM under a device-side
+ROI count in the pixel-major (force_tile 13) and the border-major row order (force_tile 43), back to back."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -109,7 +110,55 @@ def backward(name, N, H, W, Cin, Cout, k, stride, pad, iters=20):
           f"({kern(p32)})  f16 {t['f16'][1]:7.1f} us ({kern(p16)})  x{t[None][1] / t['f16'][1]:.2f}", flush=True)
 
 
+def border_skipped_share(rois, oh=14, ow=14):
+    """Share of a border-order launch's (tile, tap) pairs whose tap is zero padding for every row of the 64-row tile = the share of
+    MFMA work it leaves out, counted from the order itself (csrc/conv_border_order.h)."""
+    import numpy as np
+    oy, ox = [], []
+    for y in (0, oh - 1):                                   # top rows of all maps, then bottom rows
+        oy.append(np.full(rois * ow, y)); ox.append(np.tile(np.arange(ow), rois))
+    for x in (0, ow - 1):                                   # left columns without corners, then right columns
+        oy.append(np.tile(np.arange(1, oh - 1), rois)); ox.append(np.full(rois * (oh - 2), x))
+    iy, ix = np.divmod(np.arange((oh - 2) * (ow - 2)), ow - 2)
+    oy.append(np.tile(iy + 1, rois)); ox.append(np.tile(ix + 1, rois))
+    oy, ox = np.concatenate(oy), np.concatenate(ox)
+    ky, kx = np.divmod(np.arange(9), 3)
+    live = ((oy[:, None] - 1 + ky >= 0) & (oy[:, None] - 1 + ky < oh) & (ox[:, None] - 1 + kx >= 0) & (ox[:, None] - 1 + kx < ow))
+    tiles = [live[m0:m0 + 64].any(axis=0) for m0 in range(0, len(oy), 64)]
+    return 1.0 - float(np.mean(tiles))
+
+
+def border(rois, cap, Cin=256, Cout=256, iters=50, rounds=5):
+    """mask_fcn GEMM (14x14 maps, 3x3, Cin -> Cout) on `rois` of `cap` ROI slots: both row orders alternating, `rounds` times."""
+    x = torch.randn((cap, 14, 14, Cin), generator=g).to(dev)
+    conv = ops.Conv(torch.randn((Cout, Cin, 3, 3), generator=g) * 0.02, torch.zeros(Cout), stride=1, pad=1, device=dev)
+    count = torch.tensor([rois], dtype=torch.int32, device=dev)
+    out = torch.empty((cap, 14, 14, Cout), device=dev)
+    t = {13: [], 43: []}
+    for _ in range(rounds):
+        for ft in (13, 43):
+            for _w in range(5):
+                conv(x, cap, 14, 14, relu=True, m_count=count, m_unit=196, out=out, force_tile=ft, force_splitk=1)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _i in range(iters):
+                conv(x, cap, 14, 14, relu=True, m_count=count, m_unit=196, out=out, force_tile=ft, force_splitk=1)
+            e1.record()
+            torch.cuda.synchronize()
+            t[ft].append(e0.elapsed_time(e1) / iters * 1e3)
+    a, b = sorted(t[13])[rounds // 2], sorted(t[43])[rounds // 2]
+    flops = 2.0 * rois * 196 * Cout * Cin * 9
+    print(f"mask_fcn {rois:3d} of {cap:3d} rois  pixel-major {a:7.1f} us ({min(t[13]):.1f}-{max(t[13]):.1f}, {flops / a / 1e6:5.1f} TFLOP/s)  "
+          f"border-major {b:7.1f} us ({min(t[43]):.1f}-{max(t[43]):.1f})  measured -{(1 - b / a) * 100:4.1f} %  "
+          f"skipped chunk share {border_skipped_share(rois) * 100:4.1f} %", flush=True)
+
+
 which = sys.argv[1] if len(sys.argv) > 1 else "all"
+if which == "border":
+    for rois, cap in ((43, 128), (88, 300), (300, 300)):
+        border(rois, cap)
+    sys.exit(0)
 if which == "backward":
     # the backbone's layers of one 640x640 training step: weight gradient and gated input gradient, fp32 against f16 arithmetic
     for sh in [("l1 conv1 1x1 256->64", 1, 160, 160, 256, 64, 1, 1, 0), ("l1 conv2 3x3 64->64", 1, 160, 160, 64, 64, 3, 1, 1),
