@@ -26,6 +26,9 @@ _ERR = {-1: "EOD_ERR_BAD_DIMS", -2: "EOD_ERR_ALIGN", -3: "EOD_ERR_LAUNCH", -4: "
 MAX_BATCH = 8       # EOD_MAX_BATCH
 MAX_LEVELS = 40     # EOD_MAX_LEVELS
 SEMMAP_SCORES = 0x10000     # EOD_SEMMAP_SCORES: the flag bit on `D` of eod_semmap_labels (any vocabulary, label + confidence)
+SEMMAP_LOCATE = 0x40000     # EOD_SEMMAP_LOCATE: SCORES + the probability maps of Q queried classes (Q in the field at Q_SHIFT)
+SEMMAP_PEAKS = 0x80000      # EOD_SEMMAP_PEAKS: the second call of a locate, the K best local maxima of each map
+SEMMAP_K_SHIFT, SEMMAP_RADIUS_SHIFT, SEMMAP_Q_SHIFT = 12, 20, 24     # K - 1 (4 bits), radius (2 bits), Q (6 bits)
 
 
 class EodConvDesc(C.Structure):

@@ -78,6 +78,12 @@ class RobotFrontEnd:
         q = np.rint(p).astype(np.int64)
         return int(q[0]), int(q[1])
 
+    def cell_center(self, cell) -> Tuple[float, float]:
+        """The inverse of `robot_cell`: the (x, y) in metres of the middle of a cell, given as the pair `robot_cell` returns or as the
+        memory's index `x * map_h + y` (a peak of `locate` with `map_shape=(map_w, map_h)`)."""
+        cx, cy = divmod(int(cell), self.map_h) if np.ndim(cell) == 0 else (int(cell[0]), int(cell[1]))
+        return (float(cx * self.res + float(self.map_shift[0])), float(cy * self.res + float(self.map_shift[2])))
+
 
 def read_depth_mm(path: str) -> np.ndarray:
     """`cv2.imread(path, cv2.IMREAD_ANYDEPTH)` (robot_demo.py:498): the 16-bit depth PNG as uint16 millimetres, via Pillow."""

@@ -73,6 +73,15 @@ class EmbodiedPredictor:
         labels, scores = self.model.semantic_map(classifier=classifier, thresh=thresh, scores=True)
         return {"labels": labels, "scores": scores}
 
+    def locate(self, classes, vocabulary: Optional[str] = None, classifier=None, thresh: Optional[float] = None, map_shape=None,
+               radius: int = 1, topk: int = 8) -> Dict:
+        """Where on the map the queried classes are: the dict of `CustomRCNNRecurrent.locate` (`labels`, `scores`, `prob`, `peaks`,
+        `peak_scores`).  `classes`: indices into the vocabulary that `vocabulary` / `classifier` name as in the constructor;
+        neither: the memory's own class matrix.  The model, its heads and the memory are left as they are."""
+        if vocabulary is not None and classifier is None:
+            classifier = resolve_vocabulary(vocabulary)
+        return self.model.locate(classes, classifier=classifier, thresh=thresh, map_shape=map_shape, radius=radius, topk=topk)
+
     def _resized_hw(self, h: int, w: int):
         """`ResizeShortestEdge([480, 480], max_size).get_output_shape`."""
         scale = 480.0 / min(h, w)

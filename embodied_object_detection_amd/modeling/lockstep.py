@@ -36,7 +36,7 @@ import torch
 
 from .. import _lib, ops
 from ..structures import Boxes, Instances
-from .meta_arch import CustomRCNNRecurrent, _det_stream, _sched_streams, _semmap_query
+from .meta_arch import CustomRCNNRecurrent, _det_stream, _sched_streams, _semmap_locate, _semmap_query
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
 RESULT_SETS = 3
@@ -233,6 +233,16 @@ class LockstepScenes:
         if classifier is None and not scores:
             return ops.semmap_labels(mem, obs, m.zs_weight, m.obs_score_thresh if thresh is None else float(thresh))
         return _semmap_query(m, mem, obs, classifier, num_classes, thresh)
+
+    def locate(self, scene: int, classes, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None,
+               map_shape=None, radius: int = 1, topk: int = 8):
+        """`CustomRCNNRecurrent.locate` on scene `scene`'s state.  Nothing of the batch model changes."""
+        if not 0 <= int(scene) < self.B:
+            raise IndexError(f"scene {scene} of a lock-step batch of {self.B}")
+        if self.implicit_memory is None:
+            raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
+        return _semmap_locate(self.model, self.implicit_memory[int(scene)], self.observations[int(scene)], classes, classifier,
+                              num_classes, thresh, map_shape, radius, topk)
 
     def _refresh_snapshot(self):
         """a4 + fp16 cast for the B tables: they are one [B*N,512] table to the kernels."""

@@ -65,14 +65,33 @@ def _det_stream(device: torch.device) -> torch.cuda.Stream:
     return _DET_STREAMS[idx]
 
 
-def _semmap_query(model, mem, obs, classifier, num_classes, thresh):
-    """`semantic_map` in query form on one scene's state (`model`: the single-scene model that holds the configuration)."""
+def _query_matrix(model, mem, classifier, num_classes):
+    """The class matrix a read of the memory uses (`model`: the single-scene model that holds the configuration): the
+    meta-architecture's own, or `classifier` as `reset_cls_test` takes it.  Refuses a memory that no frame has filled."""
     if mem is None:
         raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
-    zs = model.zs_weight
-    if classifier is not None:
-        zs = query_classifier(classifier, num_classes, bool(getattr(model.roi_heads, "norm_weight", True)), model.device)
+    if classifier is None:
+        return model.zs_weight
+    return query_classifier(classifier, num_classes, bool(getattr(model.roi_heads, "norm_weight", True)), model.device)
+
+
+def _semmap_query(model, mem, obs, classifier, num_classes, thresh):
+    """`semantic_map` in query form on one scene's state."""
+    zs = _query_matrix(model, mem, classifier, num_classes)
     return ops.semmap_query(mem, obs, zs, model.obs_score_thresh if thresh is None else float(thresh))
+
+
+def _semmap_locate(model, mem, obs, classes, classifier, num_classes, thresh, map_shape, radius, topk):
+    """`locate` on one scene's state.  `map_shape` (rows, cols) names the grid the cell index r * cols + c runs over; None: no grid,
+    the peaks are the plain top-k."""
+    zs = _query_matrix(model, mem, classifier, num_classes)
+    cols = None
+    if map_shape is not None:
+        rows, cols = int(map_shape[0]), int(map_shape[1])
+        if rows * cols != mem.shape[0]:
+            raise _lib.EodError(f"locate: map_shape {tuple(map_shape)} does not hold the memory's {mem.shape[0]} cells")
+    return ops.semmap_locate(mem, obs, zs, classes, model.obs_score_thresh if thresh is None else float(thresh), cols=cols,
+                             radius=radius, topk=topk)
 
 
 @META_ARCH_REGISTRY.register()
@@ -753,6 +772,16 @@ class CustomRCNNRecurrent:
                                             self.obs_score_thresh if thresh is None else float(thresh))
             return self.semmap
         return _semmap_query(self, self.implicit_memory, self.observations, classifier, num_classes, thresh)
+
+    def locate(self, classes, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None, map_shape=None,
+               radius: int = 1, topk: int = 8):
+        """Where on the map the classes `classes` (1 to 32 indices into the vocabulary; `classifier`, `num_classes`, `thresh` as in
+        `semantic_map`) are most likely, as `ops.semmap_locate` returns it: `labels`, `scores`, `prob` [Q, N] (each class's softmax
+        probability per cell, 0 below the threshold), `peaks` / `peak_scores` [Q, topk] (the best local maxima within `radius`
+        cells on the grid `map_shape` = (rows, cols), cell = r * cols + c; without it the plain top-k).  Changes nothing in the
+        model."""
+        return _semmap_locate(self, self.implicit_memory, self.observations, classes, classifier, num_classes, thresh, map_shape,
+                              radius, topk)
 
     # ---- introspection used by tests / bench -----------------------------------------------------------
     def proposals_snapshot(self):

@@ -1356,3 +1356,72 @@ def semmap_query(mem: torch.Tensor, obs: torch.Tensor, zs: torch.Tensor, thresh:
     check(_lib.load().eod_semmap_labels(mem.data_ptr(), obs.data_ptr(), zs.data_ptr(), N, D | _lib.SEMMAP_SCORES, C1, thresh,
                                         labels.data_ptr(), ws.data_ptr(), _stream()), "eod_semmap_labels")
     return labels, ws[4 + N:]
+
+
+SEMMAP_LOCATE_MAX_Q, SEMMAP_LOCATE_MAX_K, SEMMAP_LOCATE_MAX_RADIUS = 32, 16, 3
+
+
+def semmap_locate_workspace(N: int, Q: int, K: int) -> int:
+    """Floats of a `semmap_locate` workspace (EOD_SEMMAP_LOCATE_FLOATS): the SCORES call's 4 + 2 N, 32 query indices, prob [Q, N],
+    the peak step's candidates [Q, N], peaks and peak_scores [Q, K]."""
+    return 4 + 2 * N + 32 + 2 * Q * N + 2 * Q * K
+
+
+def semmap_locate(mem: torch.Tensor, obs: torch.Tensor, zs: torch.Tensor, classes, thresh: float, cols: Optional[int] = None,
+                  radius: int = 1, topk: int = 8, workspace: Optional[torch.Tensor] = None) -> dict:
+    """Where on the map the queried classes are (EOD_SEMMAP_LOCATE, then EOD_SEMMAP_PEAKS on the same workspace).  `classes`: Q
+    class indices (1 <= Q <= 32, each in [0, C1-2], duplicates allowed), a sequence or an integer tensor.  Returns
+      labels int32 [N], scores float32 [N]     what `semmap_query` returns, bit for bit
+      prob float32 [Q, N]                      the softmax probability of class q in cell i over the whole vocabulary; 0 where the
+                                               threshold labels the cell -1
+      peaks int32 [Q, topk], peak_scores       the best local maxima of each map by (prob descending, cell ascending), padded with
+                                               (-1, 0.0): cell i = r * cols + c is a peak iff prob > 0 and no cell of its
+                                               (2 radius + 1)^2 window, clipped at the edge, has a larger value or an equal value
+                                               and a lower index.  `cols=None`: the plain top-k of the positive cells (radius 0).
+    Everything but `labels` is a view into the workspace (`workspace`: float32, at least `semmap_locate_workspace(N, Q, topk)`)."""
+    N, D = mem.shape
+    if zs.dim() != 2 or zs.shape[0] != 512 or not zs.is_contiguous() or zs.dtype != torch.float32:
+        raise _lib.EodError(f"semmap_locate: class matrix {tuple(zs.shape)} {zs.dtype}: expected contiguous float32 [512, C1]")
+    C1 = int(zs.shape[1])
+    if C1 > ZS_WIDE_MAX_C1:
+        raise _lib.EodError(f"semmap_locate: {C1 - 1} classes + background exceed the kernel's {ZS_WIDE_MAX_C1} columns")
+    if isinstance(classes, torch.Tensor):
+        if classes.dim() != 1 or classes.dtype.is_floating_point or classes.dtype == torch.bool:
+            raise _lib.EodError(f"semmap_locate: classes {tuple(classes.shape)} {classes.dtype}: expected a 1-d integer tensor")
+        classes = classes.tolist()
+    classes = [int(c) for c in classes]
+    Q, K = len(classes), int(topk)
+    if not 1 <= Q <= SEMMAP_LOCATE_MAX_Q:
+        raise _lib.EodError(f"semmap_locate: {Q} queried classes; one call takes 1 to {SEMMAP_LOCATE_MAX_Q}")
+    bad = [c for c in classes if not 0 <= c <= C1 - 2]
+    if bad:
+        raise _lib.EodError(f"semmap_locate: class indices {bad} outside [0, {C1 - 2}] (column {C1 - 1} is the background)")
+    if not 1 <= K <= SEMMAP_LOCATE_MAX_K:
+        raise _lib.EodError(f"semmap_locate: topk {topk} outside 1..{SEMMAP_LOCATE_MAX_K}")
+    if cols is None:
+        cols, radius = N, 0
+    cols, radius = int(cols), int(radius)
+    if not 0 <= radius <= SEMMAP_LOCATE_MAX_RADIUS:
+        raise _lib.EodError(f"semmap_locate: radius {radius} outside 0..{SEMMAP_LOCATE_MAX_RADIUS}")
+    if cols < 1 or N % cols != 0:
+        raise _lib.EodError(f"semmap_locate: {N} cells are no whole number of rows of {cols}")
+    need = semmap_locate_workspace(N, Q, K)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.float32, device=mem.device)
+    elif (workspace.dtype != torch.float32 or workspace.dim() != 1 or not workspace.is_contiguous() or workspace.numel() < need
+          or workspace.device != mem.device):
+        raise _lib.EodError(f"semmap_locate: workspace {tuple(workspace.shape)} {workspace.dtype}: expected {need} contiguous float32 "
+                            "on the memory's device")
+    ws = workspace
+    q0, p0 = 4 + 2 * N, 4 + 2 * N + 32
+    ws[q0:q0 + Q].view(torch.int32).copy_(torch.tensor(classes, dtype=torch.int32), non_blocking=False)
+    labels = torch.empty((N,), dtype=torch.int32, device=mem.device)
+    lib, qbits = _lib.load(), Q << _lib.SEMMAP_Q_SHIFT
+    check(lib.eod_semmap_labels(mem.data_ptr(), obs.data_ptr(), zs.data_ptr(), N, D | _lib.SEMMAP_LOCATE | qbits, C1, thresh,
+                                labels.data_ptr(), ws.data_ptr(), _stream()), "eod_semmap_labels")
+    pbits = _lib.SEMMAP_PEAKS | qbits | (K - 1) << _lib.SEMMAP_K_SHIFT | radius << _lib.SEMMAP_RADIUS_SHIFT
+    check(lib.eod_semmap_labels(mem.data_ptr(), obs.data_ptr(), zs.data_ptr(), N, D | pbits, cols, thresh, labels.data_ptr(),
+                                ws.data_ptr(), _stream()), "eod_semmap_labels")
+    k0 = p0 + 2 * Q * N
+    return {"labels": labels, "scores": ws[4 + N:4 + 2 * N], "prob": ws[p0:p0 + Q * N].view(Q, N),
+            "peaks": ws[k0:k0 + Q * K].view(torch.int32).view(Q, K), "peak_scores": ws[k0 + Q * K:k0 + 2 * Q * K].view(Q, K)}

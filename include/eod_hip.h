@@ -702,8 +702,38 @@ int eod_memory_write_init(void* workspace, size_t workspace_bytes, int H, int W,
  * (EOD_ERR_CAPACITY beyond), the product runs as a GEMM on the fp32 matrix cores, `labels` means the same (labels of near-tied
  * classes may differ from the plain call's by summation order; the -1 set and the intensities are the plain call's bits), and
  * workspace >= 2*n_cells + 4 floats: workspace + 4 + n_cells receives scores[n_cells], the softmax probability of the cell's argmax
- * class over those C1-1 columns, for every cell (the threshold touches `labels` only).  Without the bit nothing changes. */
+ * class over those C1-1 columns, for every cell (the threshold touches `labels` only).  Without the bit nothing changes.
+ *
+ * D = 512 | EOD_SEMMAP_LOCATE | Q << EOD_SEMMAP_Q_SHIFT (the SCORES bit may be set as well; it is implied) is the SCORES call and, in
+ * the same launches, the probability maps of Q queried classes, 1 <= Q <= 32.  The caller lays the workspace out, in floats:
+ *   [0, 4 + 2*n_cells)                      as in the SCORES call: min/max, intensities, scores
+ *   EOD_SEMMAP_LOCATE_QUERY(n_cells) + 32   int32 class indices, the first Q read; in: each in [0, C1-2] (the background column is
+ *                                           not a class; duplicates allowed; the kernel clamps what it reads into that range)
+ *   EOD_SEMMAP_LOCATE_PROB(n_cells)         out: prob[Q][n_cells], prob[q][i] = softmax over the C1-1 columns of cell i's logits at
+ *                                           class q: bitwise scores[i] where labels[i] == that class; 0 where the threshold sets -1
+ *   + Q*n_cells                             cand[Q][n_cells], scratch of the PEAKS call
+ *   + 2*Q*n_cells                           out of the PEAKS call: peaks int32 [Q][K], then peak_scores float [Q][K]
+ * EOD_SEMMAP_LOCATE_FLOATS(n_cells, Q, K) floats in all.
+ *
+ * D = 512 | EOD_SEMMAP_PEAKS | Q << EOD_SEMMAP_Q_SHIFT | (K-1) << EOD_SEMMAP_K_SHIFT | radius << EOD_SEMMAP_RADIUS_SHIFT, with the
+ * grid's column count in `C1` (cell = r * cols + c; n_cells % cols == 0), 1 <= K <= 16, 0 <= radius <= 3, is the second call of a
+ * locate on the same workspace and n_cells; it reads only `workspace` (the other pointers must still be non-null).  Cell i is a peak
+ * of class q iff prob[q][i] > 0 and no other cell j of its (2 radius + 1)^2 window, clipped at the grid's edge, has
+ * prob[q][j] > prob[q][i], or an equal value and j < i.  peaks[q] / peak_scores[q]: the K best peaks by (prob descending, cell
+ * ascending), padded with (-1, 0.0).  Comparisons only: two calls give the same bits.
+ *
+ * Every other combination of bits (both modes at once, PEAKS with SCORES, a field without its mode, Q outside 1..32, a bit not
+ * named here) is EOD_ERR_BAD_DIMS before any launch. */
 #define EOD_SEMMAP_SCORES 0x10000
+#define EOD_SEMMAP_LOCATE 0x40000
+#define EOD_SEMMAP_PEAKS 0x80000
+#define EOD_SEMMAP_K_SHIFT 12       /* 4 bits: K - 1 */
+#define EOD_SEMMAP_RADIUS_SHIFT 20  /* 2 bits */
+#define EOD_SEMMAP_Q_SHIFT 24       /* 6 bits: Q */
+#define EOD_SEMMAP_LOCATE_QUERY(n_cells) ((size_t)4 + 2 * (size_t)(n_cells))
+#define EOD_SEMMAP_LOCATE_PROB(n_cells) (EOD_SEMMAP_LOCATE_QUERY(n_cells) + 32)
+#define EOD_SEMMAP_LOCATE_FLOATS(n_cells, Q, K) \
+  (EOD_SEMMAP_LOCATE_PROB(n_cells) + 2 * (size_t)(Q) * (size_t)(n_cells) + 2 * (size_t)(Q) * (size_t)(K))
 int eod_semmap_labels(const float* mem, const float* obs, const float* zs, int n_cells, int D, int C1, float thresh,
                       int32_t* labels, float* workspace, eod_stream_t stream);
 
