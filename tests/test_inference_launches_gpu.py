@@ -29,14 +29,20 @@ Replayed here, at the recorded shapes, capacities, flags and `batch`, outputs pr
     (which is what proves the kernel's workgroup remap is a permutation of the grid), the rows behind P5 untouched.
   * `preprocess_image` at the recorded sizes, in the allocating form and into `out` as recorded.
 
-NOT replayed here (recorded and printed only; the tests named hold them at TOY shapes, not at these -- that gap stays open): `groupnorm_relu` inference form
-(test_kernels_gpu.py::test_groupnorm_statistics_ride_on_the_conv_slab_reduce), `roi_align` with `box_rows` / `refine` / `batch`
-(test_batch_abi_gpu.py::test_roi_align_over_the_images_of_a_batch, test_kernels_gpu.py::test_box_head_glue), `zs_classify` /
-`cascade_stage_tail` / `apply_deltas` / `memory_scores` (test_box_head_glue, test_vocab_kernels_gpu.py), `mask_predictor_sigmoid`
-(test_mask_predictor), `detector_postprocess` (test_postprocess_and_paste_masks), `MemoryWriter` (test_memory_write_matches_oracle,
-_write_parity.py at full size on the frame's own masks), `unproject_grid_index` (test_unproject_grid_index_bit_exact),
-`semmap_labels` (test_semmap_labels_match_oracle).  Lock-step is recorded in its `launches` kind (modeling/lockstep.py); the
-`streams` kind (modeling/batched.py) is recorded once and asserted to make no call the single-scene episode has not made.
+NOT replayed here (recorded and printed only), but held against float64 with derived bounds (`detector_postprocess`: exactly) at
+their own tile and loop edges rather than at the recorded shapes, in test_head_launches_gpu.py: `zs_classify` narrow and wide with
+its fused `zs_mem` re-score and `final_inv_stages` fusion (test_narrow_classifier, test_wide_classifier), `cascade_stage_tail`
+(test_cascade_stage_tail), `apply_deltas` (test_apply_deltas), `cascade_scores` (test_cascade_scores), `memory_scores`
+(test_narrow_memory_scores, test_wide_memory_scores), `mask_predictor_sigmoid` (test_mask_predictor), `detector_postprocess`
+(test_detector_postprocess).
+
+NOT replayed here and not covered there either (recorded and printed only; the tests named hold them at TOY shapes, not at these --
+that gap stays open): `groupnorm_relu` inference form (test_kernels_gpu.py::test_groupnorm_statistics_ride_on_the_conv_slab_reduce),
+`roi_align` with `box_rows` / `refine` / `batch` (test_batch_abi_gpu.py::test_roi_align_over_the_images_of_a_batch,
+test_kernels_gpu.py::test_box_head_glue), `MemoryWriter` (test_memory_write_matches_oracle, _write_parity.py at full size on the
+frame's own masks), `unproject_grid_index` (test_unproject_grid_index_bit_exact), `semmap_labels`
+(test_semmap_labels_match_oracle).  Lock-step is recorded in its `launches` kind (modeling/lockstep.py); the `streams` kind
+(modeling/batched.py) is recorded once and asserted to make no call the single-scene episode has not made.
 """
 import os
 import sys
