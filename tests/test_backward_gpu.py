@@ -486,7 +486,8 @@ def test_centernet_loss_matches_the_reference_functions():
     """`eod_centernet_loss` (CenterNet.losses of the recurrent configuration, centernet.py:241-318) against the fixture made by the
     reference's OWN binary_heatmap_focal_loss_jit / IOULoss (tests/golden/gen_golden_losses.py): the three losses and the gradient with
     respect to the head's raw output rows (agnostic logit; bbox_pred before the level's Scale and the ReLU).  Then a second, larger
-    case against the oracle's restatement with autograd through relu(scale * raw)."""
+    case against the oracle's restatement with autograd through relu(scale * raw).  tests/test_loss_launches_gpu.py holds every
+    element of the same kernels to float64 at their loop edges and decision points."""
     import numpy as np
     from embodied_object_detection_amd import ops
     from oracle import losses as OL
@@ -558,7 +559,8 @@ def test_fast_rcnn_loss_matches_the_reference_methods():
     """`eod_fast_rcnn_loss` (one cascade stage's sigmoid CE + class-agnostic L1 / smooth-L1 box loss, detic_fast_rcnn.py:157-303) against
     the fixture made by the reference's OWN `sigmoid_cross_entropy_loss` / `box_reg_loss` methods (gen_golden_losses.py::main_box), with
     and without a class-weight mask; then beta > 0 and LVIS width (1 203 classes, zero-shot logits padded to a 1 216-column row)
-    against the oracle with autograd."""
+    against the oracle with autograd.  tests/test_loss_launches_gpu.py holds every element of the same kernels to float64 at their
+    loop edges and decision points."""
     from embodied_object_detection_amd import ops
     from oracle import losses as OL
     from test_losses_golden import load_box_fixture
@@ -601,7 +603,8 @@ def test_centernet_targets_match_the_reference():
     """`eod_centernet_targets` against the reference's own `_get_ground_truth` / `_get_label_inds` (centernet.py:342-479; fixture by
     gen_golden_losses.py::main_targets): positive locations and regression targets bit for bit, the heatmap within 2 ulp (expf), the
     image without objects; then a 640x640 pyramid with 300 boxes (two LDS chunks) against the oracle; and the targets feed
-    `eod_centernet_loss` directly."""
+    `eod_centernet_loss` directly.  tests/test_loss_launches_gpu.py runs the kernel at its chunk and wave edges and holds the heat map
+    to float64."""
     import numpy as np
     from embodied_object_detection_amd import ops
     from oracle import losses as OL

@@ -33,14 +33,27 @@ def _boxes(g, n_gt, n_rand, W=640.0, H=640.0):
     return gt.contiguous(), props[torch.randperm(props.shape[0], generator=g)].contiguous()
 
 
-@pytest.mark.parametrize("n_gt,n_rand,thr", [(24, 1500, 0.6), (300, 700, 0.7), (1, 63, 0.8), (0, 100, 0.6)])
-def test_match_label_bit_exact(n_gt, n_rand, thr):
+_MATCH_EDGES = [(G, 40, 0.6 if (G + R) % 2 else 0.7, R) for G in (255, 256, 257) for R in (255, 256, 257)]
+
+
+@pytest.mark.parametrize("n_gt,n_rand,thr,R", [(24, 1500, 0.6, None), (300, 700, 0.7, None), (1, 63, 0.8, None), (0, 100, 0.6, None)] + _MATCH_EDGES,
+                         ids=["24-1500-0.6", "300-700-0.7", "1-63-0.8", "0-100-0.6"] + [f"G{e[0]}-R{e[3]}-{e[2]}" for e in _MATCH_EDGES])
+def test_match_label_bit_exact(n_gt, n_rand, thr, R):
+    """`R` given: exactly R proposals against n_gt objects at the edges of the kernel's chunks of 256 (threads per workgroup, objects
+    per LDS chunk); the last two objects are one box twice -- with 257 objects the twins sit on both sides of the chunk boundary --
+    and proposal 0 is that box: the FIRST of the two maximal IoUs must win."""
     from embodied_object_detection_amd import ops
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(11 + n_gt)
     gt, props = _boxes(g, n_gt, n_rand)
     if n_gt >= 24:
         gt[5] = gt[2]                                                      # two identical objects: the FIRST maximum wins
+    if R is not None:
+        gt[n_gt - 1] = gt[n_gt - 2]
+        props = props[:R].contiguous()
+        props[0] = gt[n_gt - 2]
+        if R > 1:
+            props[1] = gt[n_gt - 2] + torch.tensor([0.5, -0.25, 0.75, 0.5])
     gc = torch.randint(0, 20, (n_gt,), generator=g)
     ridx, riou, rcls, rgtb = OL.match_label(props, gt, gc, thr, 20)
     midx, miou, cls, gtb = ops.match_label(props.to(dev), gt.to(dev), gc.int().to(dev), thr, 20)
@@ -48,7 +61,10 @@ def test_match_label_bit_exact(n_gt, n_rand, thr):
     assert torch.equal(miou.cpu(), riou), float((miou.cpu() - riou).abs().max())
     assert torch.equal(cls.cpu().long(), rcls)
     assert torch.equal(gtb.cpu(), rgtb)
-    if n_gt:
+    if R is not None:
+        assert props.shape[0] == R and int(midx[0]) == n_gt - 2 and float(miou[0]) == 1.0
+        assert int((rcls < 20).sum()) > 0 and int((rcls == 20).sum()) > 0
+    elif n_gt:
         assert int((rcls < 20).sum()) >= n_gt // 2 and int((rcls == 20).sum()) > 0      # both kinds present
 
 
@@ -82,8 +98,12 @@ def test_match_label_proposals_with_the_count_on_the_device(n_gt, cap, count, ap
 
 
 @pytest.mark.parametrize("R,n_fg,batch,ties", [(2300, 400, 512, False), (2300, 40, 512, True), (300, 10, 512, False), (8192, 3000, 512, True),
-                                               (64, 0, 16, False)])
+                                               (64, 0, 16, False),
+                                               (1023, 300, 512, "all"), (1024, 300, 512, "all"), (1025, 300, 512, "all"),
+                                               (8191, 3000, 512, "all"), (8192, 3000, 512, "all")])
 def test_sample_proposals_matches_oracle(R, n_fg, batch, ties):
+    """`ties` "all": every key is equal, so one bucket holds every row of a kind and the row index alone decides -- at the edges of
+    the kernel's 1024 threads and of its capacity of 8192 rows."""
     from embodied_object_detection_amd import ops
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(R + n_fg)
@@ -92,7 +112,9 @@ def test_sample_proposals_matches_oracle(R, n_fg, batch, ties):
     cls[perm[:n_fg]] = torch.randint(0, 20, (n_fg,), generator=g)
     cls[perm[n_fg:n_fg + R // 50]] = -1                                    # ignored rows (a Matcher with three labels would emit them)
     keys = torch.rand((R,), generator=g)
-    if ties:
+    if ties == "all":
+        keys = torch.full((R,), 0.5)
+    elif ties:
         keys = (keys * 64).floor() / 64                                    # many equal keys: the row index breaks the tie
     ref = OL.sample_by_keys(cls, keys, 20, batch, 0.25)
     idx, counts = ops.sample_proposals(cls.int().to(dev), keys.to(dev), 20, batch, 0.25)

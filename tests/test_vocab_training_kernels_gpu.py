@@ -203,7 +203,8 @@ def test_fed_loss_class_choice_ties_and_too_few_eligible(dev):
 @pytest.mark.parametrize("C,fed", [(1203, False), (1203, True), (2047, False)])
 def test_loss_with_a_zero_one_class_weight_matches_the_oracle(dev, C, fed):
     """`eod_fast_rcnn_loss` at LVIS width with a 0 / 1 class weight (given, or chosen by the call itself) against the oracle's
-    sigmoid_cross_entropy_loss in float64 under autograd."""
+    sigmoid_cross_entropy_loss in float64 under autograd.  tests/test_loss_launches_gpu.py holds the kernel to float64 element by
+    element at its loop edges."""
     from embodied_object_detection_amd import ops
     B, ld = 512, C + 1
     g = torch.Generator().manual_seed(C + int(fed))
