@@ -97,6 +97,7 @@ class EodDetDesc(C.Structure):
         ("out_rows", C.c_void_p), ("out_count", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
         ("out_unique_rows", C.c_void_p), ("out_unique_count", C.c_void_p), ("unique_cap", C.c_int32),
         ("out_rep_of", C.c_void_p), ("out_rep_list", C.c_void_p), ("out_rep_count", C.c_void_p), ("batch", C.c_int32),
+        ("row_matrix", C.c_void_p), ("row_matrix_out", C.c_void_p),
     ]
 
 

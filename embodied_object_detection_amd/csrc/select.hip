@@ -993,12 +993,57 @@ __device__ __forceinline__ void det_write_outputs(const u64* kept_key, int total
   }
 }
 
+// det_row_iou_matrix as a launch of its own: the same bit matrix into a caller-owned [R_cap, words] array (words = ceil(R_cap / 64):
+// every word is written, zero beyond the rows in use), from the same clipped boxes and the same comparison, so that a selection that is
+// handed the matrix (EodDetDesc.row_matrix) keeps the same detections.  The matrix needs the boxes only, not the scores: it can be
+// built while the launches that produce the scores still run.  Workgroup (w, t, scene): the 64 rows of tile t against the 64 partner
+// rows of word w; four neighbouring lanes take 16 partners each of one row and OR their bits together.
+__global__ __launch_bounds__(256) void det_row_matrix_kernel(const float* __restrict__ boxes, const int* __restrict__ count, int R_cap,
+                                                               int words, float img_w, float img_h, float nms_thresh,
+                                                               u64* __restrict__ out) {
+  const int scene = blockIdx.z;
+  boxes += (size_t)scene * R_cap * 4;
+  out += (size_t)scene * R_cap * words;
+  __shared__ float rowb[64 * 4];      // the tile's rows, clipped
+  __shared__ float parb[64 * 4];      // the word's partner rows, clipped
+  int R = R_cap;
+  if (count) {
+    const int c = count[scene];
+    R = c < R ? c : R;
+  }
+  const int tid = threadIdx.x, w = blockIdx.x, r0 = blockIdx.y * 64;
+  if (tid < 64) {
+    det_clip_row(boxes + (size_t)r0 * 4, tid, r0 + tid < R, img_w, img_h, rowb);
+  } else if (tid < 128) {
+    const int b = tid - 64;
+    det_clip_row(boxes + (size_t)w * 64 * 4, b, w * 64 + b < R, img_w, img_h, parb);
+  }
+  __syncthreads();
+  const int lr = tid >> 2, quarter = tid & 3, r = r0 + lr;
+  u64 bits = 0;
+  if (r < R) {
+    const float x1 = rowb[lr * 4 + 0], y1 = rowb[lr * 4 + 1], x2 = rowb[lr * 4 + 2], y2 = rowb[lr * 4 + 3];
+    const float area = (x2 - x1) * (y2 - y1);
+#pragma unroll 4
+    for (int k = 0; k < 16; ++k) {
+      const int b = quarter * 16 + k, r2 = w * 64 + b;
+      if (r2 < R && r2 != r && iou_over(x1, y1, x2, y2, area, parb[b * 4 + 0], parb[b * 4 + 1], parb[b * 4 + 2], parb[b * 4 + 3], nms_thresh))
+        bits |= 1ull << b;
+    }
+  }
+  bits |= __shfl_xor(bits, 1, 64);
+  bits |= __shfl_xor(bits, 2, 64);
+  if (quarter == 0 && r < R_cap) out[(size_t)r * words + w] = bits;
+}
+
 __global__ __launch_bounds__(1024) void det_select_kernel(const float* boxes, const float* scores, const int* count, int R_cap, int C1,
-                                                           float img_w, float img_h, float thr, float nms_thresh, int topk, ScanOut o) {
+                                                           float img_w, float img_h, float thr, float nms_thresh, int topk, ScanOut o,
+                                                           const u64* __restrict__ row_matrix) {
   EOD_CHAIN_PRIO();
   constexpr int EMAX = 8;
   {
     const int scene = blockIdx.x;      // one workgroup per scene of a batch
+    if (row_matrix) row_matrix += (size_t)scene * R_cap * ((R_cap + 63) >> 6);
     boxes += (size_t)scene * R_cap * 4;
     scores += (size_t)scene * R_cap * C1;
     if (count) count += scene;
@@ -1055,7 +1100,16 @@ __global__ __launch_bounds__(1024) void det_select_kernel(const float* boxes, co
   }
   __syncthreads();
   EOD_STAMP(sb + 1);
-  det_row_iou_matrix(cbx, R, W, nms_thresh, Mx);
+  if (row_matrix) {
+    // built ahead by det_row_matrix_kernel from these boxes, this size and this threshold: the words that are read
+    const int words = (R_cap + 63) >> 6;
+    for (int idx = tid; idx < R * W; idx += 1024) {
+      const int r = idx / W, w = idx - r * W;
+      Mx[r * DET_WORDS + w] = row_matrix[(size_t)r * words + w];
+    }
+  } else {
+    det_row_iou_matrix(cbx, R, W, nms_thresh, Mx);
+  }
   EOD_STAMP(sb + 2);
   // candidates: score > thr on a finite row; histogram of their score bits
   u64 key[EMAX];
@@ -1718,7 +1772,20 @@ static int det_outputs(const EodDetDesc* d, ScanOut* o) {
   return EOD_OK;
 }
 
+// EodDetDesc.row_matrix_out: the call is the matrix launch alone
+static int det_build_row_matrix(const EodDetDesc* d, hipStream_t s) {
+  if (!d->boxes) return EOD_ERR_NULL;
+  const int nb = d->batch > 1 ? d->batch : 1;
+  if (d->R_cap <= 0 || d->R_cap > DET_MAX_R || nb > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
+  if ((uintptr_t)d->row_matrix_out & 7) return EOD_ERR_ALIGN;
+  const int words = (d->R_cap + 63) >> 6;
+  hipLaunchKernelGGL(det_row_matrix_kernel, dim3(words, words, nb), dim3(256), 0, s, d->boxes, d->count, d->R_cap, words, d->img_w,
+                     d->img_h, d->nms_thresh, (u64*)d->row_matrix_out);
+  return eod_launch_status();
+}
+
 extern "C" int eod_fast_rcnn_inference(const EodDetDesc* d, eod_stream_t stream) {
+  if (d && d->row_matrix_out) return det_build_row_matrix(d, (hipStream_t)stream);
   if (!d || !d->boxes || !d->scores || !d->out_boxes || !d->out_scores || !d->out_classes || !d->out_rows || !d->out_count ||
       !d->workspace)
     return EOD_ERR_NULL;
@@ -1728,7 +1795,7 @@ extern "C" int eod_fast_rcnn_inference(const EodDetDesc* d, eod_stream_t stream)
   const int nb = d->batch > 1 ? d->batch : 1;
   ScanOut o{};
   if (det_is_wide(d->R_cap, d->C1)) {
-    if (nb > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
+    if (nb > EOD_MAX_BATCH || d->row_matrix) return EOD_ERR_BAD_DIMS;      // the wide tail builds its matrix itself
     const DetwWs w = carve_detw(d->workspace, d->C1 - 1, EOD_MAX_BATCH);
     if (d->workspace_bytes < w.bytes) return EOD_ERR_CAPACITY;
     if (const int err = det_outputs(d, &o)) return err;
@@ -1747,8 +1814,9 @@ extern "C" int eod_fast_rcnn_inference(const EodDetDesc* d, eod_stream_t stream)
   if ((d->out_unique_rows || d->out_rep_of) && d->R_cap > NMS_KEPT_MAX) return EOD_ERR_BAD_DIMS;
   if (const int err = det_outputs(d, &o)) return err;
   if (nb > EOD_MAX_BATCH) return EOD_ERR_BAD_DIMS;
+  if (d->row_matrix && ((uintptr_t)d->row_matrix & 7)) return EOD_ERR_ALIGN;
   hipLaunchKernelGGL(det_select_kernel, dim3(nb), dim3(1024), 0, s, d->boxes, d->scores, d->count, d->R_cap, d->C1, d->img_w, d->img_h,
-                     d->score_thresh, d->nms_thresh, d->topk, o);
+                     d->score_thresh, d->nms_thresh, d->topk, o, (const u64*)d->row_matrix);
   return eod_launch_status();
 }
 

@@ -12,8 +12,9 @@ by stage, on buffers that hold the B scenes back to back (the batch convention o
   -> P6 / P7, N = B -> CenterNet tower + GroupNorm on the 5 B level images of the batch as one row list (`centernet_head.py:141-161`)
   -> proposal decoding, one workgroup per (level, scene) and per scene (`centernet.py:603-745`)
   -> cascade: ROIAlign over B x R boxes, the FC layers as ONE GEMM over B x R rows (per-scene counts: EodConvDesc.m_segments),
-     classifier / deltas over B x R rows, detection selection one workgroup per scene (`detic_roi_heads.py:88-222`)
-  -> memory selection, one workgroup per scene (`custom_rcnn.py:825-875`)
+     classifier / deltas over B x R rows, detection selection one workgroup per scene (`detic_roi_heads.py:88-222`); stages 1-2
+     and the detection selection on the side stream, beside what follows
+  -> memory selection behind stage 0, one workgroup per scene (`custom_rcnn.py:825-875`)
   -> mask head on the memory instances and on the detection groups of ALL scenes: the scenes' lists are concatenated
      (eod_concat_lists) and each pass is one ROIAlign + 4 convs + the fused tail over the concatenation (`detic_roi_heads.py:257-268`)
   -> memory write: three launches for the B states (`custom_rcnn.py:884-936`) -> post-processing + paste, grid = scene.
@@ -92,6 +93,7 @@ class LockstepScenes:
         self._ev_trunk = torch.cuda.Event()
         self._ev_start = torch.cuda.Event()
         self._ev_box = torch.cuda.Event()
+        self._ev_s0 = torch.cuda.Event()     # stage 0 of the cascade is enqueued: the memory chain and stages 1-2 part here
         self._ev_det = [None] * RESULT_SETS
         self._pyr_reader = {}
         self._slot = 0
@@ -315,6 +317,10 @@ class LockstepScenes:
             self.set_classifier_width()
         self._step_no += 1
         self._mark("start")
+        # The previous step's stages 1-2 and detection selection run on the side stream.  They read the proposal decoder's boxes,
+        # scores and count (one buffer set, rewritten by this step's decode) and the cascade's buffers (rewritten by this step's
+        # stage 0): the step's stream joins them before anything of this step is enqueued.  They are long over by then.
+        cur.wait_event(self._ev_box)
         for b, f in enumerate(frames):
             p = m._device_proj(f)
             if tuple(p.shape) != (H, W):
@@ -372,7 +378,10 @@ class LockstepScenes:
         boxes = prop_boxes
         seg = dict(m_count=prop_count, m_unit=1, m_segments=B, plan_rows=self._pr(R))
         pending = None
-        for s_i, st in enumerate(rh.stages):
+
+        def stage(s_i):
+            nonlocal boxes, pending
+            st = rh.stages[s_i]
             if pending is None:
                 ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, prop_count, B * R, 7, out=self.pool7, batch=B,
                               boxes_per_image=R)
@@ -397,7 +406,7 @@ class LockstepScenes:
                                        mem_scores_out=self.mem_scores if rescore else None,
                                        final_inv_stages=1.0 / rh.num_stages if last else 0.0, deltas_out=self.deltas, batch=B, wide=True)
                 boxes = self.boxes[s_i + 1]
-                continue
+                return
             ops.zs_classify(feat, st["zs"], self.prob, s_i > 0, self.featn0 if s_i == 0 else None, prop_count, R, C1, rh.norm_temp,
                             zs_mem=m.zs_weight if rescore else None, prop_scores=prop_scores if (last or rescore) else None,
                             mem_scores_out=self.mem_scores if rescore else None,
@@ -409,6 +418,12 @@ class LockstepScenes:
                 ops.apply_deltas(self.deltas, 4, boxes, self.boxes[s_i + 1], prop_count, R, rh.cascade_weights[s_i], not last, float(W),
                                  float(H), batch=B)
                 boxes = self.boxes[s_i + 1]
+
+        # Stage 0 on the step's stream; everything the memory side reads (`featn0`, `mem_scores`, the proposal boxes) is final behind
+        # it and stages 1-2 write none of it, so the step's critical chain (memory selection -> proposal masks -> memory write) goes on
+        # from here while stages 1-2 and the detection selection, which only the detections need, run beside it on the side stream.
+        stage(0)
+        self._ev_s0.record(cur)
         if not rh.fuses_mem_rescore(m.zs_weight):
             for b in range(B):
                 ops.memory_scores(self.featn0[b * R:(b + 1) * R], m.zs_weight, prop_scores[b * R:(b + 1) * R],
@@ -422,10 +437,16 @@ class LockstepScenes:
                 _lib.check(_lib.load().eod_fill_i32(mem_cnt[b:b + 1].data_ptr(), 0, 1, s_raw), "fill")
                 _lib.check(_lib.load().eod_fill_i32(msel.uniq_count[b:b + 1].data_ptr(), 0, 1, s_raw), "fill")
         self._mark("cascade+mem_select")
+        side = _sched_streams(dev)[0]
+        side.wait_event(self._ev_s0)
         sel = self.selectors[k]
-        det_boxes, det_scores, det_classes, det_rows, det_count = sel(boxes, self.prob, prop_count, float(W), float(H), rh.score_thresh,
-                                                                     rh.nms_thresh)
-        self._ev_box.record(cur)
+        with torch.cuda.stream(side):
+            for s_i in range(1, rh.num_stages):
+                stage(s_i)
+            det_boxes, det_scores, det_classes, det_rows, det_count = sel(boxes, self.prob, prop_count, float(W), float(H),
+                                                                         rh.score_thresh, rh.nms_thresh)
+            self._ev_box.record(side)
+            self._mark("cascade+det_select", side)
 
         # detection mask pass + post-processing + paste (detic_roi_heads.py:257, custom_rcnn.py:579-580)
         post = d["posts"][k]
@@ -442,6 +463,7 @@ class LockstepScenes:
                 self._mark("det_pass", ds)
             self._pyr_reader[which] = self._ev_det[k]
         else:
+            cur.wait_event(self._ev_box)
             self._detection_pass(views, h3, w3, sel, k, H, W, post)
 
         # mask head on the memory instances of all scenes (custom_rcnn.py:573-574, only the proposals 875-880 read), memory write

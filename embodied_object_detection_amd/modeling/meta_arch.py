@@ -8,7 +8,7 @@ Mirrors `Detic/detic/modeling/meta_arch/custom_rcnn.py`: `forward` eval branch (
 
 Call convention: `model(batched_inputs: List[List[dict]]) -> List[dict]`; the module is stateful
 between calls.  A frame is enqueued with no host synchronisation on the current HIP stream plus three scheduling streams
-(box cascade + memory selection + memory write; the coming frames' memory-independent trunk; the detection mask pass + paste,
+(box cascade + detection selection + memory write; the coming frames' memory-independent trunk; the detection mask pass + paste,
 which may trail under the next frame of a call) -- or, with `overlap_branches = False`, in order on the current stream alone.
 The only sync per frame is the read-back of the final detection count when the result `Instances` are materialised.
 """
@@ -37,11 +37,12 @@ _SCHED_STREAMS: Dict[int, Tuple[torch.cuda.Stream, ...]] = {}
 # t+2 has been enqueued, so that the host never waits for a detection pass that still trails on the GPU (the host needs ~3.7 ms
 # to enqueue a frame, about as long as the GPU needs to run one).
 RESULT_SETS = 3
+MEMORY_NMS_THRESH = 0.5     # `inference_with_proposals`' per-class NMS (custom_rcnn.py:869)
 PYRAMID_SETS = 6        # current frame, the frame before (its detection pass may trail), and up to four frames computed ahead
 
 
 def _sched_streams(device: torch.device) -> Tuple[torch.cuda.Stream, ...]:
-    """(side: box cascade + memory selection + memory write, look-ahead trunk, main chain): the high-priority streams.  The device
+    """(side: box cascade + detection selection + memory write, look-ahead trunk, main chain): the high-priority streams.  The device
     offers two priority levels (0 and -1); the detection pass that trails under the next frame runs at 0, everything latency-bound
     at -1."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
@@ -135,16 +136,18 @@ class CustomRCNNRecurrent:
         # one-ROI-per-detection pass (bench.py reports it beside the headline).
         self.dedup_detection_masks = True
         # The frame has two schedules.  `overlap_branches = False`: every launch in order on the current stream (`_frame_in_order`).
-        # True (`_frame_pipelined`): the proposal mask pass (custom_rcnn.py:573) needs only the proposals and the FPN features, not the
-        # box cascade, so the cascade's small latency-bound launches (15 FC GEMMs, 3 ROIAligns, the selection sorts) and the memory
-        # write-back go to a second, high-priority stream beside the pass's large GEMMs; and nothing of frame t+1 depends on frame
-        # t's DETECTION masks (the memory write needs the proposal masks only), so the detection mask pass + post-processing + paste
-        # run on a normal-priority stream of their own, inside `forward([episode])` underneath frame t+1's memory read, tower,
-        # proposal decoding and box cascade (short chains that leave most of the chip idle).  PYRAMID_SETS pyramid sets and
-        # RESULT_SETS detection-list sets make the overlap hazard free.  Same kernels, same inputs, bitwise the same results.
+        # True (`_frame_pipelined`): the proposal mask pass (custom_rcnn.py:573) needs the FPN features, the proposals and -- lazily --
+        # the memory selection, which reads what cascade stage 0 leaves and nothing of stages 1-2: the cascade's small latency-bound
+        # launches (15 FC GEMMs, 3 ROIAligns, the detection selection) and the memory write-back go to a second, high-priority
+        # stream, and behind stage 0 the main stream runs the memory selection and the pass's large GEMMs beside stages 1-2; and
+        # nothing of frame t+1 depends on frame t's DETECTION masks (the memory write needs the proposal masks only), so the
+        # detection mask pass + post-processing + paste run on a normal-priority stream of their own, inside
+        # `forward([episode])` underneath frame t+1's memory read, tower, proposal decoding and box cascade (short chains that
+        # leave most of the chip idle).  PYRAMID_SETS pyramid sets and RESULT_SETS detection-list sets make the overlap hazard
+        # free.  Same kernels, same inputs, bitwise the same results.
         self.overlap_branches = True
         self._side_stream = None
-        self._ev_props = self._ev_pm = self._ev_box = self._ev_mem = self._ev_sel = None
+        self._ev_props = self._ev_pm = self._ev_box = self._ev_mem = self._ev_s0 = None
         # Look-ahead: the ResNet trunk does not read the memory, so the NEXT frames' bottom-up pass and FPN top-down convs (known from
         # the inner frame list of `forward`, or passed as `next_frame`) are enqueued on a third stream from the start of this frame
         # on; they write pyramid sets of their own.
@@ -578,62 +581,71 @@ class CustomRCNNRecurrent:
 
     def _frame_pipelined(self, frame: dict, image_hw, views, shapes, props, proj, trailing_detection_pass: bool):
         """`overlap_branches`: the rest of the frame over three streams, in the order the host enqueues it.
-        main (the current stream): proposal masks; joins the memory write -- and the detection pass unless it may trail.
-        side: box cascade -> memory selection -> detection selection -> memory write.
+        main (the current stream): the memory selection's suppression matrix; behind cascade stage 0 the memory selection and the
+        proposal masks; joins the memory write -- and the detection pass unless it may trail.
+        side: box cascade (stage 0 | stages 1-2) -> detection selection -> memory write.
         detection stream: detection masks + post-processing + paste, behind `detection_pass_after`."""
         H, W = image_hw
         prop_boxes, prop_scores, prop_count = props
         main = torch.cuda.current_stream(self.device)
         if self._side_stream is None:
             self._side_stream = _sched_streams(self.device)[0]     # high priority: the small launches go first
-            self._ev_props, self._ev_pm, self._ev_box, self._ev_mem, self._ev_sel = (torch.cuda.Event() for _ in range(5))
+            self._ev_props, self._ev_pm, self._ev_box, self._ev_mem, self._ev_s0 = (torch.cuda.Event() for _ in range(5))
         side = self._side_stream
         self._ev_props.record(main)
         self._mark("proposals", main)
         lazy = self.lazy_proposal_masks
-        # Host enqueue order matters (the GPU runs behind the host here): first the large launches of the main stream, then
-        # the side stream's ~45 small ones -- they all execute beside the two mask passes.
+        # Host enqueue order matters (the GPU runs behind the host here): a stream's launches are enqueued in the order the GPU
+        # gets to them -- stage 0, then the main stream's selection and large mask launches (`memory_chain`), then the side
+        # stream's other ~35 small ones; they all execute beside the two mask passes.
         if not lazy:
             prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count,
                                                             bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop_all", self._frame_no))
             self._ev_pm.record(main)
         mem_sel = None
+        # the memory selection's suppression matrix needs the proposal boxes only: built here, on the main stream, which has nothing
+        # else to do until stage 0 is over, it is off the chain
+        if lazy and self.mem_selector.takes_row_matrix:
+            self.mem_selector.build_row_matrix(prop_boxes, prop_count, float(W), float(H), MEMORY_NMS_THRESH)
 
-        def select_memory():
-            nonlocal mem_sel
-            mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
-            self._ev_sel.record(side)
-            self._mark("mem_select", side)
+        def memory_chain():
+            # Called by the cascade between stage 0 and stage 1 (side stream current).  The frame's critical chain (memory selection
+            # -> proposal masks -> memory write -> next frame's memory read) starts here: all it reads -- `mem_scores` and `featn0`
+            # (stage 0's classifier launch), the proposal boxes and count -- is final, and stages 1-2 write none of it (their
+            # outputs: pool7, h1, h2, hb, feat, deltas, prob, boxes[2..3]).  The refined boxes feed the detections only, which have
+            # slack.  The mask head runs only on the proposals the selection keeps (same results: the other proposals' masks are
+            # never read, custom_rcnn.py:875-880); its large launches are enqueued here, ahead of the ~20 small ones of stages 1-2,
+            # the detection selection and the detection pass, because the GPU gets to them first.
+            nonlocal mem_sel, prop_masks
+            self._ev_s0.record(side)
+            main.wait_event(self._ev_s0)
+            with torch.cuda.stream(main):
+                mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
+                self._mark("mem_select", main)
+                prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, rows=self._uniq_rows,
+                                                                rows_count=self._uniq_count,
+                                                                bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop", self._frame_no))
+                self._ev_pm.record(main)
+                self._mark("prop_masks", main)
 
         side.wait_event(self._ev_props)
         with torch.cuda.stream(side):
             k = self._post_slot
             if self._ev_det[k] is not None:
                 side.wait_event(self._ev_det[k])     # the detection list set k is still read by frame t-2's pass
-            # The frame's critical chain (proposal masks -> memory write -> next frame's memory read) waits for the MEMORY
-            # selection; the detection selection feeds the detection pass, which has slack: the memory selection goes between
-            # the cascade and the detection selection.
             det = self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W), sel=k,
                                              mem_rescore=(self.zs_weight, self.mem_scores),
-                                             after_cascade=select_memory if lazy else None)
+                                             after_stage0=memory_chain if lazy else None)
             self._ev_box.record(side)
             self._mark("cascade+det_select", side)
         det_after = self.detection_pass_after if lazy else "cascade"
         if det_after == "cascade":
             self._enqueue_detection_pass(views, shapes, det, (H, W), frame)
-        if lazy:
-            # the mask head runs only on the proposals the memory selection keeps (same results: the other proposals' masks are
-            # never read, custom_rcnn.py:875-880)
-            main.wait_event(self._ev_sel)
-            prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, rows=self._uniq_rows,
-                                                            rows_count=self._uniq_count,
-                                                            bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop", self._frame_no))
-            self._ev_pm.record(main)
-            self._mark("prop_masks", main)
         if det_after == "proposal_masks":
             self._enqueue_detection_pass(views, shapes, det, (H, W), frame, after=self._ev_pm)
-        # memory update (custom_rcnn.py:515): it needs the proposal masks (main stream) and the selection (side stream) and runs
-        # on the side stream beside the detection mask pass; the main stream joins below
+        # memory update (custom_rcnn.py:515): it needs the proposal masks and the selection (main stream, both before `_ev_pm`) and
+        # runs on the side stream beside the detection mask pass -- behind this frame's stages 1-2 and ahead of the next frame's
+        # stage 0, which overwrites `featn0` and `mem_scores`; the main stream joins below
         with torch.cuda.stream(side):
             if not lazy:
                 mem_sel = self.select_memory_instances(prop_boxes, prop_scores, prop_count, (H, W))
@@ -707,12 +719,14 @@ class CustomRCNNRecurrent:
 
     def select_memory_instances(self, prop_boxes, prop_scores, prop_count, image_hw):
         """`inference_with_proposals` up to the NMS (custom_rcnn.py:825-875): CLIP re-score of the proposals, threshold
-        MEMORY_CLS_SCORE_THRESH, per-class NMS 0.5, top 100 -> (proposal row of every kept detection, count)."""
+        MEMORY_CLS_SCORE_THRESH, per-class NMS 0.5, top 100 -> (proposal row of every kept detection, count).
+        The selector reads the suppression matrix of these boxes when `mem_selector.build_row_matrix` has built it ahead."""
         H, W = image_hw
         R = self.proposal_generator.cap
         if self._mem_scores_frame != self._frame_no:        # not written by this frame's cascade (forward_box without mem_rescore)
             ops.memory_scores(self.roi_heads.featn0, self.zs_weight, prop_scores, self.mem_scores, prop_count, R, self.C1)
-        _, _, _, rows, cnt = self.mem_selector(prop_boxes, self.mem_scores, prop_count, float(W), float(H), self.cls_score_thresh, 0.5)
+        _, _, _, rows, cnt = self.mem_selector(prop_boxes, self.mem_scores, prop_count, float(W), float(H), self.cls_score_thresh,
+                                               MEMORY_NMS_THRESH)
         return rows, cnt
 
     def update_implicit_memory(self, prop_boxes, prop_scores, prop_count, prop_masks, proj, image_hw, mem_sel=None):

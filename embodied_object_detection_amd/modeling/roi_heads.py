@@ -111,9 +111,10 @@ class DeticCascadeROIHeads:
         # results).  Measured in the frame (tools/knob_ab.py, same call): 287.1 frames/s against 288.6 with apply_deltas as its own
         # 5 us launch -- every one of the ROIAlign's 12 544 waves redoes the box arithmetic behind a dependent load: off.
         self.fold_deltas = False
-        # experiment: the cascade's 21 launches as a captured hipGraph, replayed (see forward_box).  Measured in the frame
-        # (tools/knob_ab.py, same call): 286.0 frames/s against 286.1 with stream launches -- the launch boundaries on the GPU are
-        # drain + dispatch beside the other streams' kernels, which a graph does not remove, and the host is not the limit: off.
+        # experiment: the cascade's 21 launches as two captured hipGraphs (stage 0, stages 1-2), replayed (see forward_box).
+        # Measured in the frame (tools/knob_ab.py, same call, then as one graph): 286.0 frames/s against 286.1 with stream
+        # launches -- the launch boundaries on the GPU are drain + dispatch beside the other streams' kernels, which a graph
+        # does not remove, and the host is not the limit: off.
         self.graph_cascade = False
         self._graphs = {}
         # three detection-list sets: the detection mask pass of frame t may still read set t % 3 while the cascades of the next
@@ -143,31 +144,39 @@ class DeticCascadeROIHeads:
 
     # ---- cascade box heads ------------------------------------------------------------------------
     def forward_box(self, views: List[torch.Tensor], shapes, prop_boxes: torch.Tensor, prop_scores: torch.Tensor, count: torch.Tensor,
-                    image_hw: Tuple[int, int], sel: int = 0, mem_rescore=None, after_cascade=None):
+                    image_hw: Tuple[int, int], sel: int = 0, mem_rescore=None, after_stage0=None):
         """`mem_rescore = (zs_weight of the meta-architecture, out [R, C1])`: stage 0's classifier launch also writes the memory
         update's CLIP re-score of the proposals (custom_rcnn.py:838-861).
-        `after_cascade` (optional callable): enqueued between the cascade and the detection selection (the frame's critical chain
-        waits for the memory selection, not for the detections)."""
+        `after_stage0` (optional callable): called once stage 0's classifier launch is enqueued, before stages 1-2.  Everything the
+        memory side reads (`featn0`, the re-score, the proposal boxes) is final there and no later stage writes it, so the frame's
+        critical chain (memory selection -> proposal masks -> memory write) branches off at this point and does not wait for the
+        refined boxes, which only the detections need."""
         h3, w3 = shapes[0]
         H, W = image_hw
         R = self.R
         if self.graph_cascade:
-            # Experiment (`graph_cascade`): the cascade's 21 launches as ONE hipGraph per (pyramid set, inputs) combination, captured on
-            # first use and replayed.  Every buffer of the segment is static; the events around it stay outside the graph.
+            # Experiment (`graph_cascade`): the cascade's 21 launches as TWO hipGraphs per (pyramid set, inputs) combination -- stage 0
+            # and stages 1-2, so that `after_stage0` fires between the replays as it does between the launches -- captured on first
+            # use and replayed.  Every buffer of the segments is static; the events around them stay outside the graphs.
             key = (views[0].data_ptr(), prop_boxes.data_ptr(), prop_scores.data_ptr(), count.data_ptr(), mem_rescore is not None, H, W)
-            g = self._graphs.get(key)
-            if g is None:
+            gs = self._graphs.get(key)
+            if gs is None:
                 self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore)     # eager once: workspaces exist
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore)
-                self._graphs[key] = g
-            g.replay()
+                gs = []
+                carry = (prop_boxes, None)
+                for part in (range(0, 1), range(1, self.num_stages)):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        carry = self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore, part, carry)
+                    gs.append(g)
+                self._graphs[key] = gs
+            gs[0].replay()
+            if after_stage0 is not None:
+                after_stage0()
+            gs[1].replay()
             boxes = self.boxes[self.num_stages]
         else:
-            boxes = self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore)
-        if after_cascade is not None:
-            after_cascade()
+            boxes, _ = self._cascade(views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore, after_stage0=after_stage0)
         self.last_selector = self.selectors[sel]
         return self.selectors[sel](boxes, self.prob, count, float(W), float(H), self.score_thresh, self.nms_thresh)
 
@@ -176,16 +185,18 @@ class DeticCascadeROIHeads:
         equally wide (the narrow kernel stages one after the other in the same LDS); otherwise `ops.memory_scores` runs."""
         return self.C1 <= ops.ZS_MAX_C1 and int(zs_mem.shape[1]) == self.C1
 
-    def _cascade(self, views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore):
-        """The three cascade stages (detic_roi_heads.py:88-175) -> the final boxes buffer; scores land in `self.prob`."""
+    def _cascade(self, views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore, part=None, carry=None, after_stage0=None):
+        """The cascade stages `part` (default: all three; detic_roi_heads.py:88-175) -> (the boxes buffer they end on, `pending`), which
+        is also the `carry` a later part starts from; scores land in `self.prob`.  `after_stage0`: see `forward_box`."""
         h3, w3 = shapes[0]
         H, W = image_hw
         R = self.R
         if mem_rescore is not None and not self.fuses_mem_rescore(mem_rescore[0]):
             mem_rescore = None
-        boxes = prop_boxes
-        pending = None      # `fold_deltas`: regression weights of the deltas that the next ROIAlign applies to `boxes` on load
-        for k, st in enumerate(self.stages):
+        # pending (`fold_deltas`): regression weights of the deltas that the next ROIAlign applies to `boxes` on load
+        boxes, pending = carry if carry is not None else (prop_boxes, None)
+        for k in (part if part is not None else range(self.num_stages)):
+            st = self.stages[k]
             if pending is None:
                 ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, count, R, 7, out=self.pool7)
             else:
@@ -213,6 +224,8 @@ class DeticCascadeROIHeads:
                                        mem_scores_out=mem_rescore[1] if (k == 0 and mem_rescore is not None) else None,
                                        final_inv_stages=1.0 / self.num_stages if last else 0.0, deltas_out=self.deltas, wide=True)
                 boxes = self.boxes[k + 1]
+                if k == 0 and after_stage0 is not None:
+                    after_stage0()
                 continue
             # the last stage's launch also fuses the cascade's scores: sqrt(mean_k(prob) * proposal score) (detic_roi_heads.py:164-173)
             ops.zs_classify(feat, st["zs"], self.prob, k > 0, self.featn0 if k == 0 else None, count, R, self.C1, self.norm_temp,
@@ -220,6 +233,8 @@ class DeticCascadeROIHeads:
                             prop_scores=prop_scores if (last or (k == 0 and mem_rescore is not None)) else None,
                             mem_scores_out=mem_rescore[1] if (k == 0 and mem_rescore is not None) else None,
                             final_inv_stages=1.0 / self.num_stages if last else 0.0, wide=True)
+            if k == 0 and after_stage0 is not None:
+                after_stage0()      # bbox_pred.2 and apply_deltas of stage 0 feed stage 1 only
             if not self.merge_cls_bb0:
                 st["bb0"](self.h2, R, 1, 1, relu=True, m_count=count, m_unit=1, out=self.hb)
             st["bb2"](self.hb, R, 1, 1, m_count=count, m_unit=1, out=self.deltas)
@@ -230,7 +245,7 @@ class DeticCascadeROIHeads:
             else:
                 ops.apply_deltas(self.deltas, 4, boxes, self.boxes[k + 1], count, R, self.cascade_weights[k], not last, float(W), float(H))
                 boxes = self.boxes[k + 1]
-        return boxes
+        return boxes, pending
 
     # ---- mask head ----------------------------------------------------------------------------------
     def forward_mask(self, views, shapes, boxes: torch.Tensor, count: torch.Tensor, cap: int, out: torch.Tensor,

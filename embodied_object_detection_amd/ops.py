@@ -443,12 +443,38 @@ class DetectionSelector:
             self.rep_count = torch.zeros((B,), dtype=torch.int32, device=device)
             d.out_rep_of, d.out_rep_list, d.out_rep_count = self.rep_of.data_ptr(), self.rep_list.data_ptr(), self.rep_count.data_ptr()
         self.desc = d
+        # the one-workgroup kernel (at most 24 classes and 8192 slots) can be handed the boxes' suppression matrix: `build_row_matrix`
+        self.takes_row_matrix = C1 - 1 <= 24 and R_cap * (C1 - 1) <= 8192
+        self.row_matrix = None
+        self._matrix_for = None       # arguments of the `build_row_matrix` launch that the next call may use
+
+    def build_row_matrix(self, boxes: torch.Tensor, count: Optional[torch.Tensor], img_w: float, img_h: float, nms_thresh: float):
+        """The selection's R x R suppression bit matrix as a launch of its own (several workgroups), on the current stream.  It reads
+        the boxes only: enqueued while the scores are still being computed, the matrix is ready before the selection starts.  The
+        NEXT call of the selector -- same boxes, count, image size and NMS threshold, anything else is an error -- reads the matrix
+        instead of building it, on a stream that is ordered behind this launch.  Same results."""
+        if not self.takes_row_matrix:
+            raise _lib.EodError("eod_fast_rcnn_inference: the wide selection path builds its suppression matrix itself")
+        if self.row_matrix is None:
+            self.row_matrix = torch.zeros((self.batch * self.R_cap, (self.R_cap + 63) // 64), dtype=torch.int64, device=self.boxes.device)
+            m = EodDetDesc()          # the matrix mode of the entry point: a descriptor of its own
+            m.R_cap, m.C1, m.batch, m.row_matrix_out = self.R_cap, self.C1, self.batch, self.row_matrix.data_ptr()
+            self._matrix_desc = m
+        m = self._matrix_desc
+        m.boxes, m.count, m.img_w, m.img_h, m.nms_thresh = boxes.data_ptr(), _ptr(count), img_w, img_h, nms_thresh
+        check(self.lib.eod_fast_rcnn_inference(C.byref(m), _stream()), "eod_fast_rcnn_inference (row matrix)")
+        self._matrix_for = (boxes.data_ptr(), _ptr(count), float(img_w), float(img_h), float(nms_thresh))
+        return self.row_matrix
 
     def __call__(self, boxes: torch.Tensor, scores: torch.Tensor, count: Optional[torch.Tensor], img_w: float, img_h: float,
                  score_thresh: float, nms_thresh: float):
         d = self.desc
         d.boxes, d.scores, d.count = boxes.data_ptr(), scores.data_ptr(), _ptr(count)
         d.img_w, d.img_h, d.score_thresh, d.nms_thresh = img_w, img_h, score_thresh, nms_thresh
+        built, self._matrix_for = self._matrix_for, None
+        if built is not None and built != (d.boxes, d.count, float(img_w), float(img_h), float(nms_thresh)):
+            raise _lib.EodError("eod_fast_rcnn_inference: the suppression matrix was built for other boxes, count, image size or threshold")
+        d.row_matrix = None if built is None else self.row_matrix.data_ptr()
         check(self.lib.eod_fast_rcnn_inference(C.byref(d), _stream()), "eod_fast_rcnn_inference")
         return self.boxes, self.scores, self.classes, self.rows, self.count
 

@@ -482,6 +482,15 @@ typedef struct EodDetDesc {
   int32_t* out_rep_list;   /* [topk] */
   int32_t* out_rep_count;  /* [1] */
   int32_t batch;           /* 0 / 1, or B scenes (batch convention: every buffer above B x, one workgroup per scene; indices stay scene-local) */
+  /* The suppression matrix of per-class NMS over class-agnostic boxes: bit b of M[r][w] = IoU(box r, box 64 w + b) > nms_thresh,
+   * boxes clipped to the image, zero for the rows at and beyond count; [R_cap, ceil(R_cap / 64)] words per scene, 8-byte aligned.
+   * It needs the boxes only, which are known before the scores are: built ahead, it is off the chain that waits for the selection.
+   * row_matrix_out (NULL = off): the call is a MODE of its own, not a selection -- it fills the matrix from boxes, count, R_cap,
+   * img_w, img_h, nms_thresh and batch in one launch over several workgroups and reads or writes nothing else of the descriptor.
+   * row_matrix (NULL = the selection builds the matrix itself): what such a call wrote for the same seven values; the results are
+   * the same bit for bit.  Single-workgroup path only (at most 24 classes and 8192 slots): EOD_ERR_BAD_DIMS on the wide path. */
+  const uint64_t* row_matrix;
+  uint64_t* row_matrix_out;
 } EodDetDesc;
 size_t eod_detections_workspace_bytes(int R_cap, int C1);
 int eod_fast_rcnn_inference(const EodDetDesc* d, eod_stream_t stream);
