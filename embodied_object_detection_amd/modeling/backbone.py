@@ -120,65 +120,57 @@ class CustomRecurrentFPN:
         h7, w7 = self.p7.out_hw(h6, w6)
         return hw + [(h6, w6), (h7, w7)]
 
-    def _plan(self, H: int, W: int, which: int = 0):
-        """Buffers of one pyramid; `which` in {0, 1}: two sets, so that the next frame's top-down pass can be written while the
-        current frame's ROI passes still read theirs."""
-        key = (H, W, which)
+    def _plan(self, H: int, W: int, which: int = 0, batch: int = 1):
+        """Buffers of one pyramid; `which`: the set, so that the next frame's top-down pass can be written while the current frame's
+        ROI passes still read theirs.  `batch` > 1: the pyramid of a lock-step batch, LEVEL MAJOR over the scenes ([level][scene]
+        [h*w] rows: views[l] is the [batch,h,w,256] image the N = batch convs write); `off` stays one scene's."""
+        key = (H, W, which, batch)
         if key not in self._plans:
             shapes = self.level_shapes(H, W)
             off = [0]
             for (h, w) in shapes:
                 off.append(off[-1] + h * w)
-            feats = torch.empty((off[-1], 256), dtype=torch.float32, device=self.device)
-            views = [feats[off[i]:off[i + 1]].view(1, shapes[i][0], shapes[i][1], 256) for i in range(5)]
-            pooled = torch.empty((ops.pooled_rows(H, W), 512), dtype=torch.float16, device=self.device)
+            feats = torch.empty((batch * off[-1], 256), dtype=torch.float32, device=self.device)
+            views = [feats[batch * off[i]:batch * off[i + 1]].view(batch, shapes[i][0], shapes[i][1], 256) for i in range(5)]
+            pooled = torch.empty((batch * ops.pooled_rows(H, W), 512), dtype=torch.float16, device=self.device)
             self._plans[key] = (shapes, off, feats, views, pooled)
         return self._plans[key]
 
-    def top_down(self, c: dict, H: int, W: int, which: int = 0):
-        """Memory-independent half (timm.py:118-136): lateral 1x1, + nearest x2 of the coarser level, 3x3 output -> P3..P5 of
-        buffer set `which`."""
-        shapes, off, feats, views, pooled = self._plan(H, W, which)
+    def top_down(self, c: dict, N: int = 1, views=None, planned: bool = False):
+        """Memory-independent half (timm.py:118-136) for N images in one launch per layer: lateral 1x1, + nearest x2 of the coarser
+        level, 3x3 output -> [P3, P4, P5], each [N,h,w,256], written into `views[0..2]` (a pyramid set's level views) when given.
+        `planned`: every layer planned like one image (`plan_rows`), so each image's result is bitwise that of an N = 1 call."""
         (c5, h5, w5), (c4, h4, w4), (c3, h3, w3) = c["layer5"], c["layer4"], c["layer3"]
-        assert (h3, w3) == shapes[0] and (h5, w5) == shapes[2]
-        lat5 = self.lateral[5](c5, 1, h5, w5)
-        self.output[5](lat5, 1, h5, w5, out=views[2])
-        lat4 = self.lateral[4](c4, 1, h4, w4, res=lat5, res_mode=2)
-        self.output[4](lat4, 1, h4, w4, out=views[1])
-        lat3 = self.lateral[3](c3, 1, h3, w3, res=lat4, res_mode=2)
-        self.output[3](lat3, 1, h3, w3, out=views[0])
-
-    def top_down_batched(self, c: dict, H: int, W: int, N: int):
-        """`top_down` for N images in one launch per layer -> level-major tensors (P3 [N,h3,w3,256], P4, P5); planned like one
-        image.  The caller copies each image's slices into that scene's own pyramid set (modeling/batched.py)."""
-        (c5, h5, w5), (c4, h4, w4), (c3, h3, w3) = c["layer5"], c["layer4"], c["layer3"]
-        lat5 = self.lateral[5](c5, N, h5, w5, plan_rows=h5 * w5)
-        p5 = self.output[5](lat5, N, h5, w5, plan_rows=h5 * w5)
-        lat4 = self.lateral[4](c4, N, h4, w4, res=lat5, res_mode=2, plan_rows=h4 * w4)
-        p4 = self.output[4](lat4, N, h4, w4, plan_rows=h4 * w4)
-        lat3 = self.lateral[3](c3, N, h3, w3, res=lat4, res_mode=2, plan_rows=h3 * w3)
-        p3 = self.output[3](lat3, N, h3, w3, plan_rows=h3 * w3)
+        o3, o4, o5 = views[:3] if views is not None else (None, None, None)
+        r5, r4, r3 = (h5 * w5, h4 * w4, h3 * w3) if planned else (0, 0, 0)
+        lat5 = self.lateral[5](c5, N, h5, w5, plan_rows=r5)
+        p5 = self.output[5](lat5, N, h5, w5, out=o5, plan_rows=r5)
+        lat4 = self.lateral[4](c4, N, h4, w4, res=lat5, res_mode=2, plan_rows=r4)
+        p4 = self.output[4](lat4, N, h4, w4, out=o4, plan_rows=r4)
+        lat3 = self.lateral[3](c3, N, h3, w3, res=lat4, res_mode=2, plan_rows=r3)
+        p3 = self.output[3](lat3, N, h3, w3, out=o3, plan_rows=r3)
         return [p3, p4, p5]
 
     def fuse_memory_and_top(self, H: int, W: int, memory_f16: Optional[torch.Tensor], proj: Optional[torch.Tensor], which: int = 0,
-                            err: Optional[torch.Tensor] = None):
-        """Memory read + fusion into P3..P5 (timm.py:142-192), then P6/P7 on the fused P5 (timm.py:200-205, 359-364)."""
-        shapes, off, feats, views, pooled = self._plan(H, W, which)
-        h5, w5 = shapes[2]
+                            err: Optional[torch.Tensor] = None, batch: int = 1, planned: bool = False):
+        """Memory read + fusion into P3..P5 (timm.py:142-192), then P6/P7 on the fused P5 (timm.py:200-205, 359-364), on pyramid set
+        `which` of `batch` scenes (`memory_f16` [batch,N,512], `proj` [batch,H,W]); `planned` as in `top_down`."""
+        shapes, off, feats, views, pooled = self._plan(H, W, which, batch)
+        (h5, w5), (h6, w6), (h7, w7) = shapes[2], shapes[3], shapes[4]
         if self.memory_type == "implicit_memory" and self.feat_fusion != "image_only":
             if memory_f16 is None or proj is None:
                 raise ValueError("implicit_memory needs the fp16 memory table and proj_indices")
             # P3..P5 are the first rows of the pyramid's row list, in the order the pooled rows are written
-            ops.memory_gather_pool(memory_f16, proj, H, W, out=pooled, err=err, torch_order=self.pool_in_torch_order)
-            self.merge(pooled, feats, H, W, self.map_feature_weight, self.feat_fusion)
-        self.p6(views[2], 1, h5, w5, out=views[3])
-        self.p7(views[3], 1, shapes[3][0], shapes[3][1], in_relu=True, out=views[4])
+            ops.memory_gather_pool(memory_f16, proj, H, W, out=pooled, err=err, torch_order=self.pool_in_torch_order, batch=batch)
+            self.merge(pooled, feats, H, W, self.map_feature_weight, self.feat_fusion, batch=batch)
+        self.p6(views[2], batch, h5, w5, out=views[3], plan_rows=h6 * w6 if planned else 0)
+        self.p7(views[3], batch, h6, w6, in_relu=True, out=views[4], plan_rows=h7 * w7 if planned else 0)
         return feats, views, shapes, off
 
     def forward(self, x4: torch.Tensor, H: int, W: int, memory_f16: Optional[torch.Tensor], proj: Optional[torch.Tensor],
                 which: int = 0, err: Optional[torch.Tensor] = None):
         """-> (feats [P_total,256], level views, level shapes, level offsets)."""
-        self.top_down(self.bottom_up.forward(x4, H, W), H, W, which)
+        self.top_down(self.bottom_up.forward(x4, H, W), 1, self._plan(H, W, which)[3])
         return self.fuse_memory_and_top(H, W, memory_f16, proj, which, err)
 
 

@@ -105,7 +105,7 @@ class BatchedSequences:
             xs.append(x4)
         x = torch.cat(xs, dim=0)                 # [B,Hp,Wp,4] (a device copy; no arithmetic)
         c = m0.backbone.bottom_up.forward(x, Hp, Wp, N=B)
-        p345 = m0.backbone.top_down_batched(c, Hp, Wp, B)
+        p345 = m0.backbone.top_down(c, B, planned=True)
         for b, (m, f) in enumerate(zip(scenes, frames)):
             nxt = (m._pyramid + 1) % PYRAMID_SETS
             shapes, off, feats, views, pooled = m.backbone._plan(Hp, Wp, nxt)

@@ -51,33 +51,39 @@ class CenterNet:
         # (tools/knob_ab.py, same call): 288.6 frames/s with the planner's slabs + reduce, 287.7 / 287.2 with 6 / 7: stays 0
         self.out_conv_tile = 0
 
-    def _plan(self, shapes: List[Tuple[int, int]], off: List[int]):
-        key = tuple(shapes)
+    def _plan(self, shapes: List[Tuple[int, int]], off: List[int], batch: int = 1):
+        """Tower buffers, decoder and GroupNorm workspace for `batch` scenes of the pyramid `shapes`, and the row list the shared
+        weights run over: the 5 * batch level images of the batch, level major over the scenes (for one scene: `off`, `shapes`)."""
+        key = (tuple(shapes), batch)
         if key not in self._plans:
-            P = off[-1]
+            P = batch * off[-1]
             a = torch.empty((P, 256), dtype=torch.float32, device=self.device)
             b = torch.empty((P, 256), dtype=torch.float32, device=self.device)
             head = torch.empty((P, 5), dtype=torch.float32, device=self.device)
             dec = ops.ProposalDecoder(shapes, self.strides, self.scales, self.score_thresh, self.pre_nms_topk, self.post_nms_topk,
-                                      self.nms_thresh, self.cap, self.device, head_stride=5)
-            self._plans[key] = (a, b, head, dec, ops.groupnorm_workspace(off, self.device))
+                                      self.nms_thresh, self.cap, self.device, head_stride=5, batch=batch)
+            row_off, row_shapes = [0], []
+            for (h, w) in shapes:
+                for _ in range(batch):
+                    row_off.append(row_off[-1] + h * w)
+                    row_shapes.append((h, w))
+            self._plans[key] = (a, b, head, dec, ops.groupnorm_workspace(row_off, self.device), (row_off, row_shapes))
         return self._plans[key]
 
-    def _per_level(self, conv, src: torch.Tensor, dst: torch.Tensor, shapes, off, cout: int, gn_stats=None, force_tile: int = 0):
-        # one launch over the whole pyramid (weights are shared across levels, centernet_head.py:144-160)
-        conv(src, 1, 0, 0, out=dst, levels=(off, shapes), gn_stats=gn_stats, force_tile=force_tile)
-
-    def forward(self, feats: torch.Tensor, shapes, off):
-        """feats [P_total,256] -> (boxes [cap,4], scores [cap], count [1]) device buffers, sorted by score."""
-        a, b, head, dec, gn_ws = self._plan(shapes, off)
+    def forward(self, feats: torch.Tensor, shapes, off, batch: int = 1, planned: bool = False):
+        """feats [batch * P_total,256] (level major over the scenes) -> (boxes [batch * cap,4], scores [batch * cap], count [batch])
+        device buffers, sorted by score.  `planned`: every layer planned like ONE scene's pyramid (`plan_rows`)."""
+        a, b, head, dec, gn_ws, levels = self._plan(shapes, off, batch)
+        pr = off[-1] if planned else 0
         src = feats
         for (conv, gamma, beta) in self.tower:
+            # one launch over the whole pyramid (weights are shared across levels, centernet_head.py:144-160).
             # `fuse_gn_stats`: the conv's slab reduce also writes GroupNorm's partial sums (one launch less per tower layer on the
             # frame's critical chain: +0.6 % frames/s in a same-call A/B, tools/knob_ab.py).  The reduce keeps its coalesced float4
             # mapping and accumulates the sums per thread in double (a first version that walked one channel per thread took 44 us
             # against 12 + 11 for the separate launches and was off).
-            self._per_level(conv, src, a, shapes, off, 256, gn_stats=gn_ws if self.fuse_gn_stats else None)
-            ops.groupnorm_relu(a, gamma, beta, off, 256, gn_ws, out=b, partial_ready=conv.gn_fused)   # stream order: `a` is free again
+            conv(src, 1, 0, 0, out=a, levels=levels, plan_rows=pr, gn_stats=gn_ws if self.fuse_gn_stats else None)
+            ops.groupnorm_relu(a, gamma, beta, levels[0], 256, gn_ws, out=b, partial_ready=conv.gn_fused)   # stream order: `a` is free again
             src = b
-        self._per_level(self.out_conv, src, head, shapes, off, 5, force_tile=self.out_conv_tile)
+        self.out_conv(src, 1, 0, 0, out=head, levels=levels, plan_rows=pr, force_tile=self.out_conv_tile)
         return dec(head)

@@ -19,6 +19,12 @@ by stage, on buffers that hold the B scenes back to back (the batch convention o
      (eod_concat_lists) and each pass is one ROIAlign + 4 convs + the fused tail over the concatenation (`detic_roi_heads.py:257-268`)
   -> memory write: three launches for the B states (`custom_rcnn.py:884-936`) -> post-processing + paste, grid = scene.
 
+This module holds the step's SCHEDULE only (streams, events, the look-ahead trunk, the idle slots) and the B memory states.  Every
+stage above is the function the single-scene model calls, handed the batch: `backbone.top_down / fuse_memory_and_top`,
+`CenterNet.forward`, and the heads' `_cascade`, `forward_mask_memory`, `detection_pass` on a `RoiBuffers` for B scenes
+(modeling/roi_heads.py); result sets, ticket and `Instances` come from meta_arch.  The heads' knobs therefore mean here what they
+mean for one scene.
+
 Every layer is planned like ONE scene (`plan_rows`), so it walks K exactly as the single-scene call: the results of every scene
 are bitwise those of its own `CustomRCNNRecurrent` run (tests/test_fullsize_gpu.py).  Pyramids are LEVEL MAJOR over the scenes
 ([level][scene][h*w] rows: the [B,h,w,256] images the N = B convs write), which is the one layout change against the single-scene
@@ -32,15 +38,14 @@ from __future__ import annotations
 import time as _time
 from typing import Dict, List, Optional
 
-import numpy as np
 import torch
 
 from .. import _lib, ops
-from ..structures import Boxes, Instances
-from .meta_arch import CustomRCNNRecurrent, _det_stream, _sched_streams, _semmap_locate, _semmap_query
+from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _det_stream, _instances, _result_sets, _sched_streams, _semmap_locate,
+                        _semmap_query, _ticket)
+from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
-RESULT_SETS = 3
 
 
 class _SceneView:
@@ -74,12 +79,6 @@ class LockstepScenes:
         self.scenes = [_SceneView(self, b) for b in range(self.B)]
         self.trunk_lookahead = True          # step t + 1's memory-independent trunk on its own stream beside step t's chain
         self.trail_detection_pass = True     # step t's detection mask pass + paste under step t + 1's latency-bound front
-        # True: every layer is planned like ONE scene (same split-K slabs / wave split, same summation order): each scene's results are
-        # bitwise those of its own single-scene run.  False: layers are planned for the rows the batched launch really has (fewer
-        # slabs and reduce launches, 64x64 tiles instead of the wave-split kernel on the B x R rows of the FC layers): the same
-        # arithmetic in another summation order -- results agree with the single-scene run like two fp32 implementations do
-        # (tests/test_fullsize_gpu.py::test_lockstep_planned_for_the_batch_agrees_within_tolerance)
-        self.plan_like_single = True
         self.implicit_memory: Optional[torch.Tensor] = None     # [B,N,512]
         self.observations: Optional[torch.Tensor] = None        # [B,N]
         self._mem_f16 = self._dirty = None
@@ -105,34 +104,24 @@ class LockstepScenes:
             raise NotImplementedError("MODEL.TEST_SAVE_SEMMAP is served by the single-scene model (custom_rcnn.py:518-530)")
         R, dev, B = m.proposal_generator.cap, self.device, self.B
         rh = m.roi_heads
-        C1 = rh.C1                                    # the heads' vocabulary; the memory's matrix (m.C1 columns) may differ
-        f32 = dict(dtype=torch.float32, device=dev)
         self.R, self.D = R, rh.topk
-        # cascade buffers, B x the single-scene ones
-        self.pool7 = torch.empty((B * R, 7, 7, 256), **f32)
-        self.h1 = torch.empty((B * R, 1, 1, 1024), **f32)
-        self.h2 = torch.empty((B * R, 1, 1, 1024), **f32)
-        self.hb = torch.empty((B * R, 1, 1, 1024), **f32)
-        self.feat = torch.empty((B * R, 1, 1, 512), **f32)
-        self.feat0 = torch.empty((B * R, 1, 1, 512), **f32)
-        self.featn0 = torch.zeros((B * R, 512), **f32)
-        self.deltas = torch.empty((B * R, 1, 1, 4), **f32)
-        self.prob = torch.zeros((B * R, C1), **f32)
-        self.boxes = [torch.zeros((B * R, 4), **f32) for _ in range(rh.num_stages + 1)]
-        self.mem_scores = torch.zeros((B * R, m.C1), **f32)
-        self.selectors = [ops.DetectionSelector(R, C1, rh.topk, dev, groups=True, batch=B) for _ in range(RESULT_SETS)]
+        # the ROI half's buffers, B x the single-scene ones, under the same names (`ls.feat0`, `ls.prob`, `ls.boxes`, ...)
+        self.roi = RoiBuffers(rh, B, lockstep=True)
+        self.roi.expose_on(self)
+        self.roi.proposal_pass_buffers()
+        # rh.C1: the heads' vocabulary; the memory's matrix (m.C1 columns) may differ
+        self.mem_scores = torch.zeros((B * R, m.C1), dtype=torch.float32, device=dev)
+        self.selectors = [ops.DetectionSelector(R, rh.C1, rh.topk, dev, groups=True, batch=B) for _ in range(RESULT_SETS)]
         self.mem_selector = ops.DetectionSelector(R, m.C1, 100, dev, unique=True, batch=B)
-        # mask passes over the concatenated lists of all scenes
-        self.Pcap = min(R, 128)                       # memory instances per scene: <= 100 unique rows
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.glist_p = torch.zeros((B * R,), **i32)
-        self.total_p = torch.zeros((1,), **i32)
-        self.glist_d = [torch.zeros((B * rh.topk,), **i32) for _ in range(RESULT_SETS)]
-        self.total_d = [torch.zeros((1,), **i32) for _ in range(RESULT_SETS)]
-        self.pm_bufs = (torch.empty((B * self.Pcap, 14, 14, 256), **f32), torch.empty((B * self.Pcap, 14, 14, 256), **f32))
-        self.dm_bufs = (torch.empty((B * rh.topk, 14, 14, 256), **f32), torch.empty((B * rh.topk, 14, 14, 256), **f32))
-        self.prop_masks = torch.zeros((B * R, 28, 28), **f32)
-        self.det_masks = torch.zeros((B * rh.topk, 28, 28), **f32)
+
+    @property
+    def plan_like_single(self) -> bool:
+        """`RoiBuffers.plan_like_single`: every layer of the frame planned like ONE scene (bitwise the single-scene results)."""
+        return self.roi.plan_like_single
+
+    @plan_like_single.setter
+    def plan_like_single(self, value: bool):
+        self.roi.plan_like_single = bool(value)
 
     # nn.Module surface of the drivers
     def eval(self):
@@ -143,9 +132,6 @@ class LockstepScenes:
 
     def __call__(self, episodes):
         return self.forward(episodes)
-
-    def _pr(self, rows: int) -> int:
-        return rows if self.plan_like_single else 0
 
     def _mark(self, name: str, stream=None):
         if self.trace is None:
@@ -161,39 +147,15 @@ class LockstepScenes:
             return self._bufs
         m, B, dev = self.model, self.B, self.device
         bb, pg = m.backbone, m.proposal_generator
-        shapes = bb.level_shapes(H, W)
-        off = [0]
-        for (h, w) in shapes:
-            off.append(off[-1] + h * w)
-        P = off[-1]
-        # level-major row list of the batch: level l holds the B images [B,h,w,256] at rows [B*off[l], B*off[l+1])
-        offB, shapesB = [0], []
-        for l, (h, w) in enumerate(shapes):
-            for _b in range(B):
-                offB.append(offB[-1] + h * w)
-                shapesB.append((h, w))
-        pyr = []
-        for _ in range(PYRAMID_SETS):
-            feats = torch.empty((B * P, 256), dtype=torch.float32, device=dev)
-            views = [feats[B * off[i]:B * off[i + 1]].view(B, shapes[i][0], shapes[i][1], 256) for i in range(5)]
-            pyr.append((feats, views))
-        d = dict(key=key, shapes=shapes, off=off, P=P, offB=offB, shapesB=shapesB, pyr=pyr)
+        # the pyramid sets (level major over the scenes), the tower's buffers and the decoder are the backbone's and the proposal
+        # generator's own plans for a batch of B
+        plans = [bb._plan(H, W, i, B) for i in range(PYRAMID_SETS)]
+        shapes, off = plans[0][:2]
+        d = dict(key=key, shapes=shapes, off=off, pyr=[p[2:4] for p in plans], dec=pg._plan(shapes, off, B)[3])
         d["x"] = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
         d["proj"] = torch.zeros((B, H, W), dtype=torch.int32, device=dev)
-        d["pooled"] = torch.empty((B * ops.pooled_rows(H, W), 512), dtype=torch.float16, device=dev)
-        d["tower_a"] = torch.empty((B * P, 256), dtype=torch.float32, device=dev)
-        d["tower_b"] = torch.empty((B * P, 256), dtype=torch.float32, device=dev)
-        d["head"] = torch.empty((B * P, 5), dtype=torch.float32, device=dev)
-        d["gn_ws"] = ops.groupnorm_workspace(offB, dev)
-        d["dec"] = ops.ProposalDecoder(shapes, pg.strides, pg.scales, pg.score_thresh, pg.pre_nms_topk, pg.post_nms_topk, pg.nms_thresh,
-                                       pg.cap, dev, head_stride=5, batch=B)
         d["writer"] = ops.MemoryWriter(H, W, n_cells, 100, self.R, dev, mask_thresh=0.5, batch=B)
-        D = self.D
-        d["posts"] = [dict(hw=(H, W), boxes=None, scores=None, classes=None, masks=None,
-                           src=torch.zeros((B * D,), dtype=torch.int32, device=dev), count=torch.zeros((B,), dtype=torch.int32, device=dev),
-                           count_host=torch.zeros((B,), dtype=torch.int32).pin_memory(),
-                           err_host=torch.zeros((1,), dtype=torch.int32).pin_memory(), ready=torch.cuda.Event(),
-                           err_ready=torch.cuda.Event()) for _ in range(RESULT_SETS)]
+        d["posts"] = _result_sets(B, self.D, (H, W), dev)
         self._bufs = d
         self._prefetched = None
         return d
@@ -268,14 +230,7 @@ class LockstepScenes:
         for b, f in enumerate(frames):
             ops.preprocess_image(m._device_image(f), m.pixel_mean, m.pixel_std, out=x[b:b + 1])
         c = bb.bottom_up.forward(x, H, W, N=B, plan_like_single=self.plan_like_single)
-        (c5, h5, w5), (c4, h4, w4), (c3, h3, w3) = c["layer5"], c["layer4"], c["layer3"]
-        views = d["pyr"][which][1]
-        lat5 = bb.lateral[5](c5, B, h5, w5, plan_rows=self._pr(h5 * w5))
-        bb.output[5](lat5, B, h5, w5, out=views[2], plan_rows=self._pr(h5 * w5))
-        lat4 = bb.lateral[4](c4, B, h4, w4, res=lat5, res_mode=2, plan_rows=self._pr(h4 * w4))
-        bb.output[4](lat4, B, h4, w4, out=views[1], plan_rows=self._pr(h4 * w4))
-        lat3 = bb.lateral[3](c3, B, h3, w3, res=lat4, res_mode=2, plan_rows=self._pr(h3 * w3))
-        bb.output[3](lat3, B, h3, w3, out=views[0], plan_rows=self._pr(h3 * w3))
+        bb.top_down(c, B, d["pyr"][which][1], planned=self.plan_like_single)
 
     def _enqueue_trunk_ahead(self, frames: List[dict], H: int, W: int):
         if self._trunk_stream is None:
@@ -298,7 +253,8 @@ class LockstepScenes:
         The memory side (`mem_scores`, `mem_selector`, the tables) is not touched."""
         rh, B = self.model.roi_heads, self.B
         torch.cuda.synchronize(self.device)           # results of earlier steps still read the old selectors' buffers
-        self.prob = torch.zeros((B * self.R, rh.C1), dtype=torch.float32, device=self.device)
+        self.roi.set_width(rh.C1)
+        self.roi.expose_on(self)
         self.selectors = [ops.DetectionSelector(self.R, rh.C1, rh.topk, self.device, groups=True, batch=B) for _ in range(RESULT_SETS)]
 
     def _step(self, frames: List[dict], active: List[bool], refresh: bool, next_frames: Optional[List[dict]], trailing: bool):
@@ -312,8 +268,8 @@ class LockstepScenes:
         n_cells = self.implicit_memory.shape[1]
         d = self._frame_buffers(H, W, n_cells)
         cur = torch.cuda.current_stream(dev)
-        R, D, C1 = self.R, self.D, rh.C1
-        if self.prob.shape[1] != C1:                  # `reset_cls_test` on the model since the last step: follow the heads' width
+        R, g = self.R, self.roi
+        if self.prob.shape[1] != rh.C1:               # `reset_cls_test` on the model since the last step: follow the heads' width
             self.set_classifier_width()
         self._step_no += 1
         self._mark("start")
@@ -342,87 +298,30 @@ class LockstepScenes:
             if which in self._pyr_reader:
                 cur.wait_event(self._pyr_reader[which])
             self._trunk(frames, H, W, which)
-        feats, views = d["pyr"][which]
-        shapes, off, P = d["shapes"], d["off"], d["P"]
         look = next_frames is not None and self.trunk_lookahead
         if look:
             self._ev_start.record(cur)
 
-        # memory read + fusion (timm.py:142-192), P6 / P7 (timm.py:359-364)
-        if use_mem and bb.feat_fusion != "image_only":
-            ops.memory_gather_pool(self._mem_f16, d["proj"], H, W, out=d["pooled"], err=self._err, torch_order=bb.pool_in_torch_order,
-                                   batch=B)
-            bb.merge(d["pooled"], feats, H, W, bb.map_feature_weight, bb.feat_fusion, batch=B)
-        (h5, w5), (h6, w6), (h7, w7) = shapes[2], shapes[3], shapes[4]
-        bb.p6(views[2], B, h5, w5, out=views[3], plan_rows=self._pr(h6 * w6))
-        bb.p7(views[3], B, h6, w6, in_relu=True, out=views[4], plan_rows=self._pr(h7 * w7))
-
-        # CenterNet tower + proposals (centernet_head.py:141-161, centernet.py:603-745)
-        lv = (d["offB"], d["shapesB"])
-        src = feats
-        for (conv, gamma, beta) in pg.tower:
-            conv(src, 1, 0, 0, out=d["tower_a"], levels=lv, plan_rows=self._pr(P), gn_stats=d["gn_ws"] if pg.fuse_gn_stats else None)
-            ops.groupnorm_relu(d["tower_a"], gamma, beta, d["offB"], 256, d["gn_ws"], out=d["tower_b"], partial_ready=conv.gn_fused)
-            src = d["tower_b"]
-        pg.out_conv(src, 1, 0, 0, out=d["head"], levels=lv, plan_rows=self._pr(P))
-        prop_boxes, prop_scores, prop_count = d["dec"](d["head"])
+        # memory read + fusion (timm.py:142-192), P6 / P7 (timm.py:359-364); CenterNet tower + proposals (centernet_head.py:141-161,
+        # centernet.py:603-745)
+        planned = self.plan_like_single
+        feats, views, shapes, off = bb.fuse_memory_and_top(H, W, self._mem_f16, d["proj"], which, self._err, batch=B, planned=planned)
+        prop_boxes, prop_scores, prop_count = pg.forward(feats, shapes, off, batch=B, planned=planned)
         self._mark("proposals")
         if look:
             self._enqueue_trunk_ahead(next_frames, H, W)
 
         # cascade (detic_roi_heads.py:88-222)
-        h3, w3 = shapes[0]
         k = self._slot
         if self._ev_det[k] is not None:
             cur.wait_event(self._ev_det[k])                     # detection list set k is still read by the pass of RESULT_SETS steps ago
-        boxes = prop_boxes
-        seg = dict(m_count=prop_count, m_unit=1, m_segments=B, plan_rows=self._pr(R))
-        pending = None
-
-        def stage(s_i):
-            nonlocal boxes, pending
-            st = rh.stages[s_i]
-            if pending is None:
-                ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, prop_count, B * R, 7, out=self.pool7, batch=B,
-                              boxes_per_image=R)
-            else:       # the previous stage's deltas are applied by the ROIAlign launch itself (roi_heads.fold_deltas)
-                ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, prop_count, B * R, 7, out=self.pool7, batch=B,
-                              boxes_per_image=R, refine=(self.deltas, 4, pending, True, float(W), float(H), self.boxes[s_i]))
-                boxes = self.boxes[s_i]
-                pending = None
-            st["fc1"](self.pool7, B * R, 1, 1, relu=True, out=self.h1, **seg)
-            st["fc2"](self.h1, B * R, 1, 1, relu=True, out=self.h2, **seg)
-            feat = self.feat0 if s_i == 0 else self.feat
-            st["cls_bb0"](self.h2, B * R, 1, 1, relu=True, out=feat, split=(512, self.hb), **seg)
-            last = s_i == rh.num_stages - 1
-            # the memory update's CLIP re-score: for every MEMORY_TYPE, as in the reference (custom_rcnn.py:515,573); in stage 0's
-            # launch when both class matrices are narrow and equally wide, else a launch per scene behind the cascade
-            rescore = s_i == 0 and rh.fuses_mem_rescore(m.zs_weight)
-            if rh.fuse_stage_tail and not rh.fold_deltas:
-                # classifier tail + bbox_pred.2 + apply_deltas in one launch, as the single-scene model runs them (roi_heads._cascade)
-                ops.cascade_stage_tail(feat, st["zs"], self.prob, s_i > 0, self.featn0 if s_i == 0 else None, prop_count, R, C1, rh.norm_temp,
-                                       self.hb, st["bb2"], boxes, self.boxes[s_i + 1], rh.cascade_weights[s_i], not last, float(W), float(H),
-                                       zs_mem=m.zs_weight if rescore else None, prop_scores=prop_scores if (last or rescore) else None,
-                                       mem_scores_out=self.mem_scores if rescore else None,
-                                       final_inv_stages=1.0 / rh.num_stages if last else 0.0, deltas_out=self.deltas, batch=B, wide=True)
-                boxes = self.boxes[s_i + 1]
-                return
-            ops.zs_classify(feat, st["zs"], self.prob, s_i > 0, self.featn0 if s_i == 0 else None, prop_count, R, C1, rh.norm_temp,
-                            zs_mem=m.zs_weight if rescore else None, prop_scores=prop_scores if (last or rescore) else None,
-                            mem_scores_out=self.mem_scores if rescore else None,
-                            final_inv_stages=1.0 / rh.num_stages if last else 0.0, batch=B, wide=True)
-            st["bb2"](self.hb, B * R, 1, 1, out=self.deltas, **seg)
-            if rh.fold_deltas and not last:
-                pending = rh.cascade_weights[s_i]
-            else:
-                ops.apply_deltas(self.deltas, 4, boxes, self.boxes[s_i + 1], prop_count, R, rh.cascade_weights[s_i], not last, float(W),
-                                 float(H), batch=B)
-                boxes = self.boxes[s_i + 1]
-
         # Stage 0 on the step's stream; everything the memory side reads (`featn0`, `mem_scores`, the proposal boxes) is final behind
         # it and stages 1-2 write none of it, so the step's critical chain (memory selection -> proposal masks -> memory write) goes on
         # from here while stages 1-2 and the detection selection, which only the detections need, run beside it on the side stream.
-        stage(0)
+        # The memory update's CLIP re-score: for every MEMORY_TYPE, as in the reference (custom_rcnn.py:515,573); in stage 0's launch
+        # when both class matrices are narrow and equally wide, else a launch per scene behind it.
+        cascade = (views, shapes, prop_boxes, prop_scores, prop_count, (H, W), (m.zs_weight, self.mem_scores))
+        carry = rh._cascade(*cascade, part=range(0, 1), g=g)
         self._ev_s0.record(cur)
         if not rh.fuses_mem_rescore(m.zs_weight):
             for b in range(B):
@@ -441,15 +340,14 @@ class LockstepScenes:
         side.wait_event(self._ev_s0)
         sel = self.selectors[k]
         with torch.cuda.stream(side):
-            for s_i in range(1, rh.num_stages):
-                stage(s_i)
-            det_boxes, det_scores, det_classes, det_rows, det_count = sel(boxes, self.prob, prop_count, float(W), float(H),
-                                                                         rh.score_thresh, rh.nms_thresh)
+            boxes, _ = rh._cascade(*cascade, part=range(1, rh.num_stages), carry=carry, g=g)
+            sel(boxes, self.prob, prop_count, float(W), float(H), rh.score_thresh, rh.nms_thresh)
             self._ev_box.record(side)
             self._mark("cascade+det_select", side)
 
         # detection mask pass + post-processing + paste (detic_roi_heads.py:257, custom_rcnn.py:579-580)
         post = d["posts"][k]
+        det_pass = (g, views, shapes, sel, k, post, (H, W), m.mask_threshold, m.dedup_detection_masks, 0, ("det", self._step_no))
         if self.trail_detection_pass:
             if self._det_stream is None:
                 self._det_stream = _det_stream(dev)
@@ -458,18 +356,17 @@ class LockstepScenes:
             ds.wait_event(self._ev_box)
             with torch.cuda.stream(ds):
                 self._mark("det_pass_begin", ds)
-                self._detection_pass(views, h3, w3, sel, k, H, W, post)
+                rh.detection_pass(*det_pass)
                 self._ev_det[k].record(ds)
                 self._mark("det_pass", ds)
             self._pyr_reader[which] = self._ev_det[k]
         else:
             cur.wait_event(self._ev_box)
-            self._detection_pass(views, h3, w3, sel, k, H, W, post)
+            rh.detection_pass(*det_pass)
 
         # mask head on the memory instances of all scenes (custom_rcnn.py:573-574, only the proposals 875-880 read), memory write
-        ops.concat_lists(msel.uniq_rows, msel.uniq_count, R, R, B, self.glist_p, self.total_p)
-        self._mask_pass(views, h3, w3, prop_boxes, self.glist_p, self.total_p, B * self.Pcap, R, self.prop_masks, self.pm_bufs,
-                        plan_rois=self.Pcap, tag=("prop", self._step_no))
+        rh.forward_mask_memory(views, shapes, prop_boxes, prop_count, rows=msel.uniq_rows, rows_count=msel.uniq_count,
+                               bufs=g.proposal_pass_buffers(), tag=("prop", self._step_no), g=g, lds_reserve=0)
         self._mark("prop_masks")
         follow = m.snapshot_follows_write if m.snapshot_follows_write is not None else m.test_type in ("default", "episodic")
         wr = d["writer"]
@@ -490,82 +387,9 @@ class LockstepScenes:
             else:
                 cnt = post["count"].clone()
             self.stats_log.append((prop_count.clone(), cnt, d["writer"].k_out.clone(), msel.uniq_count.clone(), sel.rep_count.clone()))
-        return self._ticket(post, k)
-
-    def _mask_pass(self, views, h3, w3, boxes, glist, total, cap, boxes_per_image, out, bufs, plan_rois, tag=None):
-        """The mask head (4 convs + deconv + predictor + sigmoid) once over the concatenated ROI lists of all scenes: ROI i pools box
-        glist[i] (a global index b * boxes_per_image + row) from image b and its 28x28 probabilities go to out[glist[i]]."""
-        rh = self.model.roi_heads
-        B = self.B
-        src, dst = bufs
-        ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, total, cap, 14, out=src, box_rows=glist, batch=B,
-                      boxes_per_image=boxes_per_image)
-        for conv in rh.mask_convs:
-            conv.event_tag = tag
-            conv(src, cap, 14, 14, relu=True, m_count=total, m_unit=196, out=dst, plan_rows=self._pr(plan_rois * 196))
-            src, dst = dst, src
-        rh.deconv(src, cap, 14, 14, relu=True, m_count=total, m_unit=196, out=out, fuse=(rh.pred_w, rh.pred_b, glist),
-                  plan_rows=self._pr(plan_rois * 196))
-
-    def _detection_pass(self, views, h3, w3, sel, k, H, W, post):
-        m, B, D, dev = self.model, self.B, self.D, self.device
-        ops.concat_lists(sel.rep_list, sel.rep_count, D, D, B, self.glist_d[k], self.total_d[k])
-        self._mask_pass(views, h3, w3, sel.boxes, self.glist_d[k], self.total_d[k], B * D, D, self.det_masks, self.dm_bufs, plan_rois=D,
-                        tag=("det", self._step_no))
-        post["boxes"] = torch.empty((B * D, 4), dtype=torch.float32, device=dev)
-        post["scores"] = torch.empty((B * D,), dtype=torch.float32, device=dev)
-        post["classes"] = torch.empty((B * D,), dtype=torch.int32, device=dev)
-        post["masks"] = torch.empty((B, D, H, W), dtype=torch.uint8, device=dev)
-        ops.detector_postprocess(sel.boxes, sel.scores, sel.classes, sel.count, D, 1.0, 1.0, float(W), float(H), post["boxes"],
-                                 post["scores"], post["classes"], post["src"], post["count"], remap=sel.rep_of, batch=B)
-        ops.paste_masks(self.det_masks, post["boxes"], post["src"], post["count"], D, H, W, m.mask_threshold, post["masks"], batch=B,
-                        prob_units=D)
-
-    def _ticket(self, post, k):
-        """Async read-back of the step's detection counts into pinned host memory + an event; flips the result set."""
-        cur = torch.cuda.current_stream(self.device)
-        post["err_host"].copy_(self._err, non_blocking=True)
-        if self.trail_detection_pass:
-            ds = self._det_stream
-            post["err_ready"].record(cur)
-            ds.wait_event(post["err_ready"])
-            with torch.cuda.stream(ds):
-                post["count_host"].copy_(post["count"], non_blocking=True)
-                post["ready"].record(ds)
-        else:
-            post["count_host"].copy_(post["count"], non_blocking=True)
-            post["ready"].record(cur)
+        # async read-back of the step's detection counts; flips the result set
         self._slot = (self._slot + 1) % RESULT_SETS
-        return post
-
-    def _materialize(self, post, active: List[bool]) -> List[Optional[Instances]]:
-        t0 = _time.perf_counter()
-        post["ready"].synchronize()
-        self.host_profile["wait_s"] += _time.perf_counter() - t0
-        flags = int(post["err_host"][0])
-        if flags:
-            self._err.zero_()
-            raise _lib.EodError(
-                f"device error flags {flags:#x}: proj_indices holds cell indices outside [0, {self.implicit_memory.shape[1]}) "
-                "(an index image written for another map size?); they were clamped, the step's results are not trustworthy")
-        cur = torch.cuda.current_stream(self.device)
-        for key in ("boxes", "scores", "classes", "masks"):
-            post[key].record_stream(cur)
-        D = self.D
-        out = []
-        for b in range(self.B):
-            if not active[b]:
-                out.append(None)
-                continue
-            n = int(post["count_host"][b])
-            inst = Instances(post["hw"])
-            inst.pred_boxes = Boxes(post["boxes"][b * D:b * D + n])
-            inst.scores = post["scores"][b * D:b * D + n]
-            inst.pred_classes = post["classes"][b * D:b * D + n].to(torch.int64)
-            inst.pred_masks = post["masks"][b, :n].view(torch.bool)
-            out.append(inst)
-        post["boxes"] = post["scores"] = post["classes"] = post["masks"] = None
-        return out
+        return _ticket(post, self._err, cur, self._det_stream if self.trail_detection_pass else None)
 
     # ---- forward ---------------------------------------------------------------------------------------------------------------
     def forward(self, episodes: List[Optional[List[dict]]]):
@@ -595,6 +419,12 @@ class LockstepScenes:
                 fr.append(e[t] if t < len(e) else (e[-1] if e else idle))
             return fr, act
 
+        def hand_out(post, act):
+            insts = _instances(post, self._err, self.host_profile, self.implicit_memory.shape[1], self.device, act)
+            for b, inst in enumerate(insts):
+                if inst is not None:
+                    outs[b].append({"instances": inst})
+
         pending = []
         with torch.cuda.stream(ms):
             for t in range(T):
@@ -612,18 +442,13 @@ class LockstepScenes:
                 pending.append((self._step(frames, active, refresh, nxt, trailing=t + 1 < T), active))
                 t1 = _time.perf_counter()
                 if len(pending) == RESULT_SETS:
-                    post, act = pending.pop(0)
-                    for b, inst in enumerate(self._materialize(post, act)):
-                        if inst is not None:
-                            outs[b].append({"instances": inst})
+                    hand_out(*pending.pop(0))
                 hp = self.host_profile
                 hp["frames"] += sum(active)
                 hp["enqueue_s"] += t1 - t0
                 hp["materialize_s"] += _time.perf_counter() - t1
             for post, act in pending:
-                for b, inst in enumerate(self._materialize(post, act)):
-                    if inst is not None:
-                        outs[b].append({"instances": inst})
+                hand_out(post, act)
             ev_out.record(ms)
         caller.wait_event(ev_out)
         return outs

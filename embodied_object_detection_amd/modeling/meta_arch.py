@@ -36,7 +36,8 @@ _SCHED_STREAMS: Dict[int, Tuple[torch.cuda.Stream, ...]] = {}
 # Result sets (post-processed detections + pasted masks, detection lists): `forward` hands frame t's Instances out after frame
 # t+2 has been enqueued, so that the host never waits for a detection pass that still trails on the GPU (the host needs ~3.7 ms
 # to enqueue a frame, about as long as the GPU needs to run one).
-RESULT_SETS = 3
+from .roi_heads import RESULT_SETS  # noqa: E402
+
 MEMORY_NMS_THRESH = 0.5     # `inference_with_proposals`' per-class NMS (custom_rcnn.py:869)
 PYRAMID_SETS = 6        # current frame, the frame before (its detection pass may trail), and up to four frames computed ahead
 
@@ -93,6 +94,69 @@ def _semmap_locate(model, mem, obs, classes, classifier, num_classes, thresh, ma
             raise _lib.EodError(f"locate: map_shape {tuple(map_shape)} does not hold the memory's {mem.shape[0]} cells")
     return ops.semmap_locate(mem, obs, zs, classes, model.obs_score_thresh if thresh is None else float(thresh), cols=cols,
                              radius=radius, topk=topk)
+
+
+def _result_sets(B: int, D: int, hw: Tuple[int, int], dev) -> List[dict]:
+    """RESULT_SETS result sets of B scenes with up to D detections each.  boxes / scores / classes / masks of a set are allocated anew
+    for every frame (`roi_heads.postprocess_and_paste`) and handed to the caller as they are: no copy of the 0/1 byte masks
+    ([300,H,W]: 123 MB at 640x640) when the Instances are built."""
+    return [dict(hw=hw, boxes=None, scores=None, classes=None, masks=None,
+                 src=torch.zeros((B * D,), dtype=torch.int32, device=dev), count=torch.zeros((B,), dtype=torch.int32, device=dev),
+                 count_host=torch.zeros((B,), dtype=torch.int32).pin_memory(), err_host=torch.zeros((1,), dtype=torch.int32).pin_memory(),
+                 ready=torch.cuda.Event(), err_ready=torch.cuda.Event()) for _ in range(RESULT_SETS)]
+
+
+def _ticket(P: dict, err: torch.Tensor, cur: torch.cuda.Stream, det_stream: Optional[torch.cuda.Stream], after=None) -> dict:
+    """Async read-back of result set P's detection counts (and the device error word) into pinned host memory + an event.
+    `det_stream`: the detection pass of this frame may still be running there: the counts are copied on that stream (behind the
+    event `after`, if given) and the ticket's event covers both streams.  None: everything ran on `cur`."""
+    P["err_host"].copy_(err, non_blocking=True)
+    if det_stream is not None:
+        if after is not None:
+            det_stream.wait_event(after)
+        P["err_ready"].record(cur)
+        det_stream.wait_event(P["err_ready"])
+        with torch.cuda.stream(det_stream):
+            P["count_host"].copy_(P["count"], non_blocking=True)
+            P["ready"].record(det_stream)
+    else:
+        P["count_host"].copy_(P["count"], non_blocking=True)
+        P["ready"].record(cur)
+    return P
+
+
+def _instances(P: dict, err: torch.Tensor, host_profile: dict, n_cells: int, device, active=None) -> List[Optional[Instances]]:
+    """Slice a result set by its scenes' detection counts (the frame's only host wait: on the event recorded after the counts'
+    async copy) -> one `Instances` per scene, None for a scene that is not `active`.  The paste kernel writes 0/1 bytes, so the
+    masks are handed out as a bool view."""
+    t0 = _time.perf_counter()
+    P["ready"].synchronize()
+    host_profile["wait_s"] += _time.perf_counter() - t0
+    flags = int(P["err_host"][0])
+    if flags:
+        err.zero_()
+        raise _lib.EodError(
+            f"device error flags {flags:#x}: proj_indices holds cell indices outside [0, {n_cells}) "
+            "(an index image written for another map size?); they were clamped, the frame's results are not trustworthy")
+    cur = torch.cuda.current_stream(device)
+    for k in ("boxes", "scores", "classes", "masks"):
+        P[k].record_stream(cur)           # allocated on the stream that filled them; the caller reads them on this one
+    B = P["count_host"].shape[0]
+    D = P["src"].shape[0] // B
+    out = []
+    for b in range(B):
+        if active is not None and not active[b]:
+            out.append(None)
+            continue
+        n = int(P["count_host"][b])
+        inst = Instances(P["hw"])
+        inst.pred_boxes = Boxes(P["boxes"][b * D:b * D + n])
+        inst.scores = P["scores"][b * D:b * D + n]
+        inst.pred_classes = P["classes"][b * D:b * D + n].to(torch.int64)
+        inst.pred_masks = P["masks"][b, :n].view(torch.bool)       # the paste kernel writes 0/1 bytes: a view, no copy
+        out.append(inst)
+    P["boxes"] = P["scores"] = P["classes"] = P["masks"] = None
+    return out
 
 
 @META_ARCH_REGISTRY.register()
@@ -293,15 +357,7 @@ class CustomRCNNRecurrent:
         if self._posts is None or self._posts[0]["hw"] != (H, W):
             # RESULT_SETS result sets: frame t's `Instances` are sliced out of set t % 3 only after frame t+2 has been enqueued
             # (`forward`), so the host's read-back of the detection count never leaves the GPU idle
-            D = self.roi_heads.topk
-            dev = self.device
-            # boxes / scores / classes / masks of a set are allocated anew for every frame (`_postprocess_and_paste`) and handed to the
-            # caller as they are: no copy of the 0/1 byte masks ([300,H,W]: 123 MB at 640x640) when the Instances are built
-            self._posts = [dict(
-                hw=(H, W), boxes=None, scores=None, classes=None, masks=None,
-                src=torch.zeros((D,), dtype=torch.int32, device=dev), count=torch.zeros((1,), dtype=torch.int32, device=dev),
-                count_host=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_host=torch.zeros((1,), dtype=torch.int32).pin_memory(),
-                ready=torch.cuda.Event(), err_ready=torch.cuda.Event()) for _ in range(RESULT_SETS)]
+            self._posts = _result_sets(1, self.roi_heads.topk, (H, W), self.device)
             self._post_slot = 0
         self._post = self._posts[self._post_slot]
 
@@ -365,23 +421,11 @@ class CustomRCNNRecurrent:
 
     def _post_ticket(self):
         """Async read-back of the frame's detection count into pinned host memory + an event; flips the result set."""
-        P = self._post
         cur = torch.cuda.current_stream(self.device)
-        P["err_host"].copy_(self._err, non_blocking=True)
-        k = self._post_slot
         if self.overlap_branches:
-            # the detection pass of this frame may still be running on its own stream: the count is copied there, and the ticket's
-            # event covers both streams
-            ds = self._det_stream
-            ds.wait_event(self._ev_det[k])
-            P["err_ready"].record(cur)
-            ds.wait_event(P["err_ready"])
-            with torch.cuda.stream(ds):
-                P["count_host"].copy_(P["count"], non_blocking=True)
-                P["ready"].record(ds)
+            P = _ticket(self._post, self._err, cur, self._det_stream, after=self._ev_det[self._post_slot])
         else:
-            P["count_host"].copy_(P["count"], non_blocking=True)
-            P["ready"].record(cur)
+            P = _ticket(self._post, self._err, cur, None)
         self._post_slot = (self._post_slot + 1) % RESULT_SETS
         return P
 
@@ -427,11 +471,11 @@ class CustomRCNNRecurrent:
                 x4, Hp, Wp = ops.preprocess_image(self._device_image(f), self.pixel_mean, self.pixel_std)
                 xs.append(x4)
             if len(frames) == 1:
-                self.backbone.top_down(self.backbone.bottom_up.forward(xs[0], Hp, Wp), Hp, Wp, sets[0])
+                self.backbone.top_down(self.backbone.bottom_up.forward(xs[0], Hp, Wp), 1, self.backbone._plan(Hp, Wp, sets[0])[3])
             else:
                 n = len(frames)
                 c = self.backbone.bottom_up.forward(torch.cat(xs, dim=0), Hp, Wp, N=n)
-                p345 = self.backbone.top_down_batched(c, Hp, Wp, n)
+                p345 = self.backbone.top_down(c, n, planned=True)
                 for b, st in enumerate(sets):
                     views = self.backbone._plan(Hp, Wp, st)[3]
                     for l in range(3):
@@ -557,14 +601,15 @@ class CustomRCNNRecurrent:
         """`overlap_branches = False`: the rest of the frame on the current stream, one launch after the other."""
         H, W = image_hw
         prop_boxes, prop_scores, prop_count = props
-        det = self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W),
-                                         mem_rescore=(self.zs_weight, self.mem_scores))
-        det_boxes, det_scores, det_classes, det_rows, det_count = det
+        self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W), mem_rescore=(self.zs_weight, self.mem_scores))
         if self.front_event is not None:
             # the latency-bound front of the frame (memory fusion, tower, proposal decoding, cascade) ends here; what follows is
             # dense (mask passes): BatchedSequences staggers its scenes on this point
             self.front_event.record(torch.cuda.current_stream(self.device))
-        self._detection_masks(views, shapes, det_boxes, det_count)
+        rh, k = self.roi_heads, self._post_slot
+        self._check_output_size(frame, (H, W))
+        rh.detection_masks(rh.bufs, views, shapes, rh.last_selector, k, self.dedup_detection_masks, rh.det_pass_lds_reserve,
+                           ("det", self._frame_no))
         mem_sel = None
         if self.lazy_proposal_masks:
             # select the memory instances first, then run the mask head only on those proposals (same results: the other
@@ -575,7 +620,7 @@ class CustomRCNNRecurrent:
         else:
             prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, tag=("prop_all", self._frame_no))
         # detector_postprocess (custom_rcnn.py:579-580)
-        self._postprocess_and_paste(det_boxes, det_scores, det_classes, det_count, (H, W), frame, self._post)
+        rh.postprocess_and_paste(rh.bufs, rh.last_selector, self._post, (H, W), self.mask_threshold, self.dedup_detection_masks)
         # memory update (custom_rcnn.py:515)
         self.update_implicit_memory(prop_boxes, prop_scores, prop_count, prop_masks, proj, (H, W), mem_sel)
 
@@ -600,7 +645,7 @@ class CustomRCNNRecurrent:
         # stream's other ~35 small ones; they all execute beside the two mask passes.
         if not lazy:
             prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count,
-                                                            bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop_all", self._frame_no))
+                                                            bufs=self.roi_heads.bufs.proposal_pass_buffers(), tag=("prop_all", self._frame_no))
             self._ev_pm.record(main)
         mem_sel = None
         # the memory selection's suppression matrix needs the proposal boxes only: built here, on the main stream, which has nothing
@@ -624,7 +669,7 @@ class CustomRCNNRecurrent:
                 self._mark("mem_select", main)
                 prop_masks = self.roi_heads.forward_mask_memory(views, shapes, prop_boxes, prop_count, rows=self._uniq_rows,
                                                                 rows_count=self._uniq_count,
-                                                                bufs=self.roi_heads.proposal_pass_buffers(), tag=("prop", self._frame_no))
+                                                                bufs=self.roi_heads.bufs.proposal_pass_buffers(), tag=("prop", self._frame_no))
                 self._ev_pm.record(main)
                 self._mark("prop_masks", main)
 
@@ -633,16 +678,15 @@ class CustomRCNNRecurrent:
             k = self._post_slot
             if self._ev_det[k] is not None:
                 side.wait_event(self._ev_det[k])     # the detection list set k is still read by frame t-2's pass
-            det = self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W), sel=k,
-                                             mem_rescore=(self.zs_weight, self.mem_scores),
-                                             after_stage0=memory_chain if lazy else None)
+            self.roi_heads.forward_box(views, shapes, prop_boxes, prop_scores, prop_count, (H, W), sel=k,
+                                       mem_rescore=(self.zs_weight, self.mem_scores), after_stage0=memory_chain if lazy else None)
             self._ev_box.record(side)
             self._mark("cascade+det_select", side)
         det_after = self.detection_pass_after if lazy else "cascade"
         if det_after == "cascade":
-            self._enqueue_detection_pass(views, shapes, det, (H, W), frame)
+            self._enqueue_detection_pass(views, shapes, (H, W), frame)
         if det_after == "proposal_masks":
-            self._enqueue_detection_pass(views, shapes, det, (H, W), frame, after=self._ev_pm)
+            self._enqueue_detection_pass(views, shapes, (H, W), frame, after=self._ev_pm)
         # memory update (custom_rcnn.py:515): it needs the proposal masks and the selection (main stream, both before `_ev_pm`) and
         # runs on the side stream beside the detection mask pass -- behind this frame's stages 1-2 and ahead of the next frame's
         # stage 0, which overwrites `featn0` and `mem_scores`; the main stream joins below
@@ -654,7 +698,7 @@ class CustomRCNNRecurrent:
             self._ev_mem.record(side)
             self._mark("mem_write", side)
         if det_after == "memory_write":
-            self._enqueue_detection_pass(views, shapes, det, (H, W), frame, after=self._ev_mem)
+            self._enqueue_detection_pass(views, shapes, (H, W), frame, after=self._ev_mem)
         main.wait_event(self._ev_mem)
         if not trailing_detection_pass:
             main.wait_event(self._ev_det[self._post_slot])     # in-order callers see a finished frame
@@ -668,35 +712,13 @@ class CustomRCNNRecurrent:
         ev.record(stream if stream is not None else torch.cuda.current_stream(self.device))
         self.trace.append((self._frame_no, name, ev))
 
-    def _detection_masks(self, views, shapes, det_boxes, det_count):
-        """`forward_with_given_boxes` (detic_roi_heads.py:257): the mask head on the detections -- once per distinct box when
-        `dedup_detection_masks` (the groups come from the detection selection's launch)."""
-        rh = self.roi_heads
-        sel = rh.last_selector
-        if self.dedup_detection_masks:
-            return rh.forward_mask(views, shapes, det_boxes, sel.rep_count, rh.topk, rh.det_masks, rows=sel.rep_list,
-                                   lds_reserve=rh.det_pass_lds_reserve, tag=("det", self._frame_no))
-        return rh.forward_mask(views, shapes, det_boxes, det_count, rh.topk, rh.det_masks, lds_reserve=rh.det_pass_lds_reserve,
-                               tag=("det", self._frame_no))
-
-    def _postprocess_and_paste(self, det_boxes, det_scores, det_classes, det_count, image_hw, frame, P):
+    @staticmethod
+    def _check_output_size(frame: dict, image_hw):
         H, W = image_hw
-        out_h, out_w = int(frame.get("height", H)), int(frame.get("width", W))
-        if (out_h, out_w) != (H, W):
+        if (int(frame.get("height", H)), int(frame.get("width", W))) != (H, W):
             raise NotImplementedError("output size != input size is not used on this path (train_mp3d.py:487-490)")
-        D, dev = self.roi_heads.topk, self.device
-        # this frame's own result tensors, from the caching allocator on the stream that fills them; `_materialize` slices them
-        P["boxes"] = torch.empty((D, 4), dtype=torch.float32, device=dev)
-        P["scores"] = torch.empty((D,), dtype=torch.float32, device=dev)
-        P["classes"] = torch.empty((D,), dtype=torch.int32, device=dev)
-        P["masks"] = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
-        ops.detector_postprocess(det_boxes, det_scores, det_classes, det_count, self.roi_heads.topk, out_w / W, out_h / H,
-                                 float(out_w), float(out_h), P["boxes"], P["scores"], P["classes"], P["src"], P["count"],
-                                 remap=self.roi_heads.last_selector.rep_of if self.dedup_detection_masks else None)
-        ops.paste_masks(self.roi_heads.det_masks, P["boxes"], P["src"], P["count"], self.roi_heads.topk, out_h, out_w,
-                        self.mask_threshold, P["masks"])
 
-    def _enqueue_detection_pass(self, views, shapes, det, image_hw, frame, after=None):
+    def _enqueue_detection_pass(self, views, shapes, image_hw, frame, after=None):
         """`forward_with_given_boxes` (detic_roi_heads.py:257) + `detector_postprocess` + paste (custom_rcnn.py:579-580) of this
         frame on the detection stream (lowest priority: its GEMMs fill whatever the latency-bound chains of the frame -- and of
         the next frame -- leave idle)."""
@@ -704,15 +726,15 @@ class CustomRCNNRecurrent:
             self._det_stream = _det_stream(self.device)
             self._ev_det = [torch.cuda.Event() for _ in range(RESULT_SETS)]
         ds = self._det_stream
-        det_boxes, det_scores, det_classes, det_rows, det_count = det
-        k = self._post_slot
+        rh, k = self.roi_heads, self._post_slot
+        self._check_output_size(frame, image_hw)
         ds.wait_event(self._ev_box)
         if after is not None:
             ds.wait_event(after)
         with torch.cuda.stream(ds):
             self._mark("det_pass_begin", ds)
-            self._detection_masks(views, shapes, det_boxes, det_count)
-            self._postprocess_and_paste(det_boxes, det_scores, det_classes, det_count, image_hw, frame, self._post)
+            rh.detection_pass(rh.bufs, views, shapes, rh.last_selector, k, self._post, image_hw, self.mask_threshold,
+                              self.dedup_detection_masks, rh.det_pass_lds_reserve, ("det", self._frame_no))
             self._ev_det[k].record(ds)
             self._mark("det_pass", ds)
         self._pyr_reader[self._pyramid] = self._ev_det[k]
@@ -750,28 +772,8 @@ class CustomRCNNRecurrent:
                               self.observations.cpu().numpy())
 
     def _materialize(self, P) -> Instances:
-        """Slice a result set by its detection count (the frame's only host wait: on the event recorded after the count's
-        async copy).  The paste kernel writes 0/1 bytes, so the masks are handed out as a bool view's copy."""
-        t0 = _time.perf_counter()
-        P["ready"].synchronize()
-        self.host_profile["wait_s"] += _time.perf_counter() - t0
-        flags = int(P["err_host"][0])
-        if flags:
-            self._err.zero_()
-            raise _lib.EodError(
-                f"device error flags {flags:#x}: proj_indices holds cell indices outside [0, {self.implicit_memory.shape[0]}) "
-                "(an index image written for another map size?); they were clamped, the frame's results are not trustworthy")
-        n = int(P["count_host"][0])
-        inst = Instances(P["hw"])
-        cur = torch.cuda.current_stream(self.device)
-        for k in ("boxes", "scores", "classes", "masks"):
-            P[k].record_stream(cur)           # allocated on the stream that filled them; the caller reads them on this one
-        inst.pred_boxes = Boxes(P["boxes"][:n])
-        inst.scores = P["scores"][:n]
-        inst.pred_classes = P["classes"][:n].to(torch.int64)
-        inst.pred_masks = P["masks"][:n].view(torch.bool)       # the paste kernel writes 0/1 bytes: a view, no copy
-        P["boxes"] = P["scores"] = P["classes"] = P["masks"] = None
-        return inst
+        """The `Instances` of a ticket (`_instances`: the frame's only host wait)."""
+        return _instances(P, self._err, self.host_profile, self.implicit_memory.shape[0], self.device)[0]
 
     def semantic_map(self, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None, scores: bool = False):
         """a20, evaluated lazily: the explicit map `self.semmap` the reference recomputes (and syncs to the host) every

@@ -17,6 +17,100 @@ from .. import ops
 from ..registry import ROI_HEADS_REGISTRY
 
 
+RESULT_SETS = 3     # detection-list sets: frame t's detection pass may still read set t % 3 while later cascades write the others
+
+
+class RoiBuffers:
+    """The ROI half's persistent activations for B scenes of R proposals, and the batch geometry its launches are told.
+
+    One scene (`lockstep=False`, the heads' own instance): every launch is the plain single-image call -- `batch` 1, no
+    `boxes_per_image`, no `m_segments`, no `plan_rows`, ROI lists passed as they are.  Lock-step (`LockstepScenes`, any B >= 1):
+    the B scenes' rows back to back, `batch` = B, per-scene counts (`m_segments`), every layer planned like ONE scene while
+    `plan_like_single` holds, and the scenes' ROI lists concatenated into one list of global indices (`roi_list`)."""
+
+    def __init__(self, heads: "DeticCascadeROIHeads", B: int, lockstep: bool):
+        R, D, dev = heads.R, heads.topk, heads.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.device, self.B, self.R, self.D, self.rows = dev, B, R, D, B * R
+        self.lockstep = lockstep
+        self.batch, self.m_segments = (B, B) if lockstep else (1, 0)
+        # True: every layer is planned like ONE scene (same split-K slabs / wave split, same summation order): each scene's results are
+        # bitwise those of its own single-scene run.  False: layers are planned for the rows the batched launch really has (fewer
+        # slabs and reduce launches, 64x64 tiles instead of the wave-split kernel on the B x R rows of the FC layers): the same
+        # arithmetic in another summation order -- results agree with the single-scene run like two fp32 implementations do
+        # (tests/test_fullsize_gpu.py::test_lockstep_planned_for_the_batch_agrees_within_tolerance)
+        self.plan_like_single = True
+        self.pool7 = torch.empty((B * R, 7, 7, 256), **f32)
+        self.h1 = torch.empty((B * R, 1, 1, 1024), **f32)
+        self.h2 = torch.empty((B * R, 1, 1, 1024), **f32)
+        self.hb = torch.empty((B * R, 1, 1, 1024), **f32)
+        self.feat = torch.empty((B * R, 1, 1, 512), **f32)
+        self.feat0 = torch.empty((B * R, 1, 1, 512), **f32)        # stage-0 CLIP-space feature = proposals.feat
+        self.featn0 = torch.zeros((B * R, 512), **f32)            # 50 * normalize(feat0): what the memory stores
+        self.deltas = torch.empty((B * R, 1, 1, 4), **f32)
+        self.prob = torch.zeros((B * R, heads.C1), **f32)
+        self.boxes = [torch.zeros((B * R, 4), **f32) for _ in range(heads.num_stages + 1)]
+        # mask-pass activations (pool, conv ping-pong, deconv output of the two-launch tail).  One scene: one set for both passes,
+        # sized for all R proposals, and a second one once the proposal pass runs on its own stream (`proposal_pass_buffers`).
+        # Lock-step: a set per pass over the concatenated lists (<= 100 unique memory rows per scene), no deconv output.
+        self.Pcap = min(R, 128) if lockstep else R
+        if lockstep:
+            self.mask_bufs = (torch.empty((B * D, 14, 14, 256), **f32), torch.empty((B * D, 14, 14, 256), **f32), None)
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.glist_p, self.total_p = torch.zeros((B * R,), **i32), torch.zeros((1,), **i32)
+            self.glist_d = [torch.zeros((B * D,), **i32) for _ in range(RESULT_SETS)]
+            self.total_d = [torch.zeros((1,), **i32) for _ in range(RESULT_SETS)]
+            self._identity = None
+        else:
+            M = max(R, heads.Dcap)
+            self.mask_bufs = (torch.empty((M, 14, 14, 256), **f32), torch.empty((M, 14, 14, 256), **f32),
+                              torch.empty((M, 28, 28, 256), **f32))
+        self.det_masks = torch.zeros((B * heads.Dcap, 28, 28), **f32)
+        self.prop_masks = torch.zeros((B * R, 28, 28), **f32)
+        self._prop_bufs = None
+
+    TENSORS = ("pool7", "h1", "h2", "hb", "feat", "feat0", "featn0", "deltas", "prob", "boxes", "det_masks", "prop_masks")
+
+    def expose_on(self, owner) -> None:
+        """The tensors under their own names on `owner` (what tests and tools read); again after `set_width`."""
+        for name in self.TENSORS:
+            setattr(owner, name, getattr(self, name))
+
+    def set_width(self, C1: int) -> None:
+        self.prob = torch.zeros((self.rows, C1), dtype=torch.float32, device=self.device)
+
+    def plan_rows(self, rows: int) -> int:
+        """EodConvDesc.plan_rows of a layer whose launch holds `rows` rows per scene."""
+        return rows if (self.lockstep and self.plan_like_single) else 0
+
+    def per_scene(self, n: int) -> int:
+        """`boxes_per_image` / `prob_units` of a launch over buffers that hold `n` entries per scene (0: one image, not used)."""
+        return n if self.lockstep else 0
+
+    def proposal_pass_buffers(self):
+        """Own activation buffers for the proposal mask pass, so that it can run concurrently with the box cascade / the
+        detection pass."""
+        if self._prop_bufs is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            n = self.B * self.Pcap
+            self._prop_bufs = (torch.empty((n, 14, 14, 256), **f32), torch.empty((n, 14, 14, 256), **f32),
+                               None if self.lockstep else torch.empty((n, 28, 28, 256), **f32))
+        return self._prop_bufs
+
+    def roi_list(self, lists, counts, cap_in: int, slot: int = None):
+        """The ROI list a mask pass runs over -> (rows, count).  One scene: the list as it is (`lists` None: the first `counts[0]`
+        boxes).  Lock-step: the scenes' lists concatenated as global indices b * cap_in + lists[b][k], into the proposal list
+        (`slot` None) or detection-list set `slot`."""
+        if not self.lockstep:
+            return lists, counts
+        if lists is None:
+            if self._identity is None:
+                self._identity = torch.arange(cap_in, dtype=torch.int32, device=self.device).repeat(self.B)
+            lists = self._identity
+        out = (self.glist_p, self.total_p) if slot is None else (self.glist_d[slot], self.total_d[slot])
+        return ops.concat_lists(lists, counts, cap_in, cap_in, self.B, out[0], out[1])
+
+
 @ROI_HEADS_REGISTRY.register()
 class DeticCascadeROIHeads:
     def __init__(self, cfg, sd: Dict[str, torch.Tensor], device, prop_cap: int):
@@ -80,26 +174,8 @@ class DeticCascadeROIHeads:
         self.deconv = ops.Conv(sd[f"{m}.deconv.weight"], sd[f"{m}.deconv.bias"], device=device, deconv=True, name="mask_deconv")
         self.pred_w = sd[f"{m}.predictor.weight"].reshape(-1).contiguous().to(device)
         self.pred_b = float(sd[f"{m}.predictor.bias"].item())
-        # persistent buffers
-        R, D = self.R, self.Dcap
-        f32 = dict(dtype=torch.float32, device=device)
-        self.pool7 = torch.empty((R, 7, 7, 256), **f32)
-        self.h1 = torch.empty((R, 1, 1, 1024), **f32)
-        self.h2 = torch.empty((R, 1, 1, 1024), **f32)
-        self.hb = torch.empty((R, 1, 1, 1024), **f32)
-        self.feat = torch.empty((R, 1, 1, 512), **f32)
-        self.feat0 = torch.empty((R, 1, 1, 512), **f32)        # stage-0 CLIP-space feature = proposals.feat
-        self.featn0 = torch.zeros((R, 512), **f32)            # 50 * normalize(feat0): what the memory stores
-        self.deltas = torch.empty((R, 1, 1, 4), **f32)
-        self.prob = torch.zeros((R, self.C1), **f32)
-        self.boxes = [torch.zeros((R, 4), **f32) for _ in range(self.num_stages + 1)]
-        M = max(R, D)
-        self.mpool = torch.empty((M, 14, 14, 256), **f32)
-        self.mbuf = torch.empty((M, 14, 14, 256), **f32)
-        self.mup = torch.empty((M, 28, 28, 256), **f32)
-        self.det_masks = torch.zeros((D, 28, 28), **f32)
-        self.prop_masks = torch.zeros((R, 28, 28), **f32)
-        self._prop_bufs = None      # second activation set, allocated when the proposal pass runs on its own stream
+        self.bufs = RoiBuffers(self, 1, lockstep=False)        # the single scene's activations, under the heads' own names too
+        self.bufs.expose_on(self)
         # deconv + ReLU + predictor + sigmoid in ONE launch (the [rois,28,28,256] activation never goes to memory); False keeps
         # the two-launch form (used by the tests as the cross-check)
         self.fuse_mask_tail = True
@@ -117,13 +193,11 @@ class DeticCascadeROIHeads:
         # does not remove, and the host is not the limit: off.
         self.graph_cascade = False
         self._graphs = {}
-        # three detection-list sets: the detection mask pass of frame t may still read set t % 3 while the cascades of the next
-        # frames write the others (meta_arch.py, `_enqueue_detection_pass` / RESULT_SETS)
         # LDS reserve of the DETECTION mask pass's launches (the pass that trails under the frame's / the next frame's latency-bound
         # chains): see EodConvDesc.lds_reserve.  0 = the kernel's natural occupancy.
         self.det_pass_lds_reserve = int(__import__("os").environ.get("EOD_DET_LDS_RESERVE", "0"))
         self.prop_pass_lds_reserve = int(__import__("os").environ.get("EOD_PROP_LDS_RESERVE", "0"))
-        self.selectors = [ops.DetectionSelector(R, self.C1, self.topk, device, groups=True) for _ in range(3)]
+        self.selectors = [ops.DetectionSelector(self.R, self.C1, self.topk, device, groups=True) for _ in range(RESULT_SETS)]
         self.selector = self.selectors[0]
 
     def set_classifier(self, zs: torch.Tensor) -> None:
@@ -137,8 +211,9 @@ class DeticCascadeROIHeads:
         if zs.shape[1] != self.C1:
             self.C1 = int(zs.shape[1])
             self.num_classes = self.C1 - 1
-            self.prob = torch.zeros((self.R, self.C1), dtype=torch.float32, device=self.device)
-            self.selectors = [ops.DetectionSelector(self.R, self.C1, self.topk, self.device, groups=True) for _ in range(3)]
+            self.bufs.set_width(self.C1)
+            self.bufs.expose_on(self)
+            self.selectors = [ops.DetectionSelector(self.R, self.C1, self.topk, self.device, groups=True) for _ in range(RESULT_SETS)]
             self.selector = self.selectors[0]
         self._graphs = {}
 
@@ -185,87 +260,105 @@ class DeticCascadeROIHeads:
         equally wide (the narrow kernel stages one after the other in the same LDS); otherwise `ops.memory_scores` runs."""
         return self.C1 <= ops.ZS_MAX_C1 and int(zs_mem.shape[1]) == self.C1
 
-    def _cascade(self, views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore, part=None, carry=None, after_stage0=None):
-        """The cascade stages `part` (default: all three; detic_roi_heads.py:88-175) -> (the boxes buffer they end on, `pending`), which
-        is also the `carry` a later part starts from; scores land in `self.prob`.  `after_stage0`: see `forward_box`."""
+    def _cascade(self, views, shapes, prop_boxes, prop_scores, count, image_hw, mem_rescore, part=None, carry=None, after_stage0=None,
+                 g: RoiBuffers = None):
+        """The cascade stages `part` (default: all three; detic_roi_heads.py:88-175) on the buffers `g` (default: the heads' own single
+        scene) -> (the boxes buffer they end on, `pending`), which is also the `carry` a later part starts from; scores land in
+        `g.prob`.  `after_stage0`: see `forward_box`."""
+        g = g if g is not None else self.bufs
         h3, w3 = shapes[0]
         H, W = image_hw
-        R = self.R
+        R, rows, batch, segs = self.R, g.rows, g.batch, g.m_segments
+        bpi, pr = g.per_scene(R), g.plan_rows(R)
         if mem_rescore is not None and not self.fuses_mem_rescore(mem_rescore[0]):
             mem_rescore = None
         # pending (`fold_deltas`): regression weights of the deltas that the next ROIAlign applies to `boxes` on load
         boxes, pending = carry if carry is not None else (prop_boxes, None)
         for k in (part if part is not None else range(self.num_stages)):
             st = self.stages[k]
-            if pending is None:
-                ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, count, R, 7, out=self.pool7)
-            else:
-                # next-stage proposals = apply_deltas(boxes, deltas) clipped to the image (detic_roi_heads.py:314): computed by the
-                # ROIAlign launch itself (EodBoxRefine) and stored to boxes[k] -- one launch less per stage on the frame's chain
-                ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, count, R, 7, out=self.pool7,
-                              refine=(self.deltas, 4, pending, True, float(W), float(H), self.boxes[k]))
-                boxes = self.boxes[k]
-                pending = None
-            st["fc1"](self.pool7, R, 1, 1, relu=True, m_count=count, m_unit=1, out=self.h1)
-            st["fc2"](self.h1, R, 1, 1, relu=True, m_count=count, m_unit=1, out=self.h2)
-            feat = self.feat0 if k == 0 else self.feat
+            # pending: next-stage proposals = apply_deltas(boxes, deltas) clipped to the image (detic_roi_heads.py:314) are computed by
+            # the ROIAlign launch itself (EodBoxRefine) and stored to boxes[k] -- one launch less per stage on the frame's chain
+            refine = None if pending is None else (g.deltas, 4, pending, True, float(W), float(H), g.boxes[k])
+            ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, count, rows, 7, out=g.pool7, batch=batch,
+                          boxes_per_image=bpi, refine=refine)
+            if pending is not None:
+                boxes, pending = g.boxes[k], None
+            # the FC layers are ONE GEMM over the scenes' rows, with per-scene counts (EodConvDesc.m_segments)
+            st["fc1"](g.pool7, rows, 1, 1, relu=True, m_count=count, m_unit=1, out=g.h1, m_segments=segs, plan_rows=pr)
+            st["fc2"](g.h1, rows, 1, 1, relu=True, m_count=count, m_unit=1, out=g.h2, m_segments=segs, plan_rows=pr)
+            feat = g.feat0 if k == 0 else g.feat
             if self.merge_cls_bb0:
-                st["cls_bb0"](self.h2, R, 1, 1, relu=True, m_count=count, m_unit=1, out=feat, split=(512, self.hb))
+                st["cls_bb0"](g.h2, rows, 1, 1, relu=True, m_count=count, m_unit=1, out=feat, split=(512, g.hb), m_segments=segs,
+                              plan_rows=pr)
             else:
-                st["cls"](self.h2, R, 1, 1, m_count=count, m_unit=1, out=feat)
+                st["cls"](g.h2, rows, 1, 1, m_count=count, m_unit=1, out=feat, m_segments=segs, plan_rows=pr)
             last = k == self.num_stages - 1
+            # the memory update's CLIP re-score rides on stage 0's classifier launch (`fuses_mem_rescore`)
+            rescore = mem_rescore if k == 0 else None
             if self.fuse_stage_tail and self.merge_cls_bb0 and not self.fold_deltas:
                 # classifier tail + bbox_pred.2 + apply_deltas as ONE launch (two launch boundaries less per stage on the cascade's
                 # chain); the last stage's launch also fuses the cascade's scores (detic_roi_heads.py:164-173)
-                ops.cascade_stage_tail(feat, st["zs"], self.prob, k > 0, self.featn0 if k == 0 else None, count, R, self.C1, self.norm_temp,
-                                       self.hb, st["bb2"], boxes, self.boxes[k + 1], self.cascade_weights[k], not last, float(W), float(H),
-                                       zs_mem=mem_rescore[0] if (k == 0 and mem_rescore is not None) else None,
-                                       prop_scores=prop_scores if (last or (k == 0 and mem_rescore is not None)) else None,
-                                       mem_scores_out=mem_rescore[1] if (k == 0 and mem_rescore is not None) else None,
-                                       final_inv_stages=1.0 / self.num_stages if last else 0.0, deltas_out=self.deltas, wide=True)
-                boxes = self.boxes[k + 1]
+                ops.cascade_stage_tail(feat, st["zs"], g.prob, k > 0, g.featn0 if k == 0 else None, count, R, self.C1, self.norm_temp,
+                                       g.hb, st["bb2"], boxes, g.boxes[k + 1], self.cascade_weights[k], not last, float(W), float(H),
+                                       zs_mem=rescore[0] if rescore is not None else None,
+                                       prop_scores=prop_scores if (last or rescore is not None) else None,
+                                       mem_scores_out=rescore[1] if rescore is not None else None,
+                                       final_inv_stages=1.0 / self.num_stages if last else 0.0, deltas_out=g.deltas, batch=batch,
+                                       wide=True)
+                boxes = g.boxes[k + 1]
                 if k == 0 and after_stage0 is not None:
                     after_stage0()
                 continue
             # the last stage's launch also fuses the cascade's scores: sqrt(mean_k(prob) * proposal score) (detic_roi_heads.py:164-173)
-            ops.zs_classify(feat, st["zs"], self.prob, k > 0, self.featn0 if k == 0 else None, count, R, self.C1, self.norm_temp,
-                            zs_mem=mem_rescore[0] if (k == 0 and mem_rescore is not None) else None,
-                            prop_scores=prop_scores if (last or (k == 0 and mem_rescore is not None)) else None,
-                            mem_scores_out=mem_rescore[1] if (k == 0 and mem_rescore is not None) else None,
-                            final_inv_stages=1.0 / self.num_stages if last else 0.0, wide=True)
+            ops.zs_classify(feat, st["zs"], g.prob, k > 0, g.featn0 if k == 0 else None, count, R, self.C1, self.norm_temp,
+                            zs_mem=rescore[0] if rescore is not None else None,
+                            prop_scores=prop_scores if (last or rescore is not None) else None,
+                            mem_scores_out=rescore[1] if rescore is not None else None,
+                            final_inv_stages=1.0 / self.num_stages if last else 0.0, batch=batch, wide=True)
             if k == 0 and after_stage0 is not None:
                 after_stage0()      # bbox_pred.2 and apply_deltas of stage 0 feed stage 1 only
             if not self.merge_cls_bb0:
-                st["bb0"](self.h2, R, 1, 1, relu=True, m_count=count, m_unit=1, out=self.hb)
-            st["bb2"](self.hb, R, 1, 1, m_count=count, m_unit=1, out=self.deltas)
+                st["bb0"](g.h2, rows, 1, 1, relu=True, m_count=count, m_unit=1, out=g.hb, m_segments=segs, plan_rows=pr)
+            st["bb2"](g.hb, rows, 1, 1, m_count=count, m_unit=1, out=g.deltas, m_segments=segs, plan_rows=pr)
             # next-stage proposals are clipped to the image (detic_roi_heads.py:314); the final boxes are clipped by
             # fast_rcnn_inference itself
             if self.fold_deltas and not last:
                 pending = self.cascade_weights[k]
             else:
-                ops.apply_deltas(self.deltas, 4, boxes, self.boxes[k + 1], count, R, self.cascade_weights[k], not last, float(W), float(H))
-                boxes = self.boxes[k + 1]
+                ops.apply_deltas(g.deltas, 4, boxes, g.boxes[k + 1], count, R, self.cascade_weights[k], not last, float(W), float(H),
+                                 batch=batch)
+                boxes = g.boxes[k + 1]
         return boxes, pending
 
     # ---- mask head ----------------------------------------------------------------------------------
     def forward_mask(self, views, shapes, boxes: torch.Tensor, count: torch.Tensor, cap: int, out: torch.Tensor,
-                     rows: torch.Tensor = None, bufs=None, lds_reserve: int = 0, tag=None):
-        """Mask head on `count` ROIs.  With `rows` (a compact ascending list of box indices) ROI k pools `boxes[rows[k]]` and its
-        28x28 mask is written to `out[rows[k]]`: only the listed boxes are computed, the output layout stays per-box."""
+                     rows: torch.Tensor = None, bufs=None, lds_reserve: int = 0, tag=None, g: RoiBuffers = None,
+                     boxes_per_image: int = 0):
+        """Mask head on `count` ROIs, at most `cap` per scene.  With `rows` (a compact ascending list of box indices) ROI k pools
+        `boxes[rows[k]]` and its 28x28 mask is written to `out[rows[k]]`: only the listed boxes are computed, the output layout stays
+        per-box.  Lock-step buffers `g`: `rows` / `count` are the scenes' concatenated list (`RoiBuffers.roi_list`) over `boxes`,
+        which holds `boxes_per_image` boxes per scene; box j is pooled from image j // boxes_per_image."""
+        g = g if g is not None else self.bufs
         h3, w3 = shapes[0]
-        mpool, mbuf, mup = bufs if bufs is not None else (self.mpool, self.mbuf, self.mup)
-        ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, count, cap, 14, out=mpool, box_rows=rows)
+        mpool, mbuf, mup = bufs if bufs is not None else g.mask_bufs
+        if not self.fuse_mask_tail and mup is None:
+            raise NotImplementedError("fuse_mask_tail = False: the lock-step buffers hold no deconv output; run the two-launch mask tail "
+                                      "on the single-scene model")
+        cap, pr = g.B * cap, g.plan_rows(cap * 196)
+        ops.roi_align(views[0], views[1], views[2], h3, w3, 256, boxes, count, cap, 14, out=mpool, box_rows=rows, batch=g.batch,
+                      boxes_per_image=g.per_scene(boxes_per_image))
         src, dst = mpool, mbuf
         self.deconv.lds_reserve = lds_reserve
         for conv in self.mask_convs:
             conv.lds_reserve = lds_reserve          # occupancy cap of the dense launches (EodConvDesc.lds_reserve)
             conv.event_tag = tag
-            conv(src, cap, 14, 14, relu=True, m_count=count, m_unit=196, out=dst)
+            conv(src, cap, 14, 14, relu=True, m_count=count, m_unit=196, out=dst, plan_rows=pr)
             src, dst = dst, src
         if self.fuse_mask_tail:
-            self.deconv(src, cap, 14, 14, relu=True, m_count=count, m_unit=196, out=out, fuse=(self.pred_w, self.pred_b, rows))
+            self.deconv(src, cap, 14, 14, relu=True, m_count=count, m_unit=196, out=out, fuse=(self.pred_w, self.pred_b, rows),
+                        plan_rows=pr)
         else:
-            self.deconv(src, cap, 14, 14, relu=True, m_count=count, m_unit=196, out=mup)
+            self.deconv(src, cap, 14, 14, relu=True, m_count=count, m_unit=196, out=mup, plan_rows=pr)
             ops.mask_predictor_sigmoid(mup, self.pred_w, self.pred_b, cap * 784, 256, count, 784, out=out, out_units=rows)
         return out
 
@@ -276,23 +369,50 @@ class DeticCascadeROIHeads:
         self.forward_mask(views, shapes, det_boxes, det_count, self.topk, self.det_masks)      # forward_with_given_boxes
         return det
 
-    def proposal_pass_buffers(self):
-        """Own activation buffers for the proposal mask pass, so that it can run concurrently with the box cascade."""
-        if self._prop_bufs is None:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            R = self.R
-            self._prop_bufs = (torch.empty((R, 14, 14, 256), **f32), torch.empty((R, 14, 14, 256), **f32),
-                               torch.empty((R, 28, 28, 256), **f32))
-        return self._prop_bufs
-
     def forward_mask_memory(self, views, shapes, prop_boxes, prop_count, rows: torch.Tensor = None, rows_count: torch.Tensor = None,
-                            bufs=None, tag=None):
+                            bufs=None, tag=None, g: RoiBuffers = None, lds_reserve: int = None):
         """`forward_mask_memory` + `mask_rcnn_inference` on ALL proposals (custom_rcnn.py:573-574).
 
         `rows` / `rows_count`: lazy variant -- only the proposals the memory update will read (custom_rcnn.py:875-880) get a
-        mask; every other proposal's mask is dead in the reference (never read after `inference_with_proposals`)."""
+        mask; every other proposal's mask is dead in the reference (never read after `inference_with_proposals`).  With the
+        lock-step buffers `g` they are the scenes' lists (`mem_selector.uniq_rows` / `uniq_count`), concatenated here."""
+        g = g if g is not None else self.bufs
+        lds = self.prop_pass_lds_reserve if lds_reserve is None else lds_reserve
         if rows is not None:
-            return self.forward_mask(views, shapes, prop_boxes, rows_count, min(self.R, 128), self.prop_masks, rows=rows, bufs=bufs,
-                                     lds_reserve=self.prop_pass_lds_reserve, tag=tag)
-        return self.forward_mask(views, shapes, prop_boxes, prop_count, self.R, self.prop_masks, bufs=bufs,
-                                 lds_reserve=self.prop_pass_lds_reserve, tag=tag)
+            rows, rows_count = g.roi_list(rows, rows_count, self.R)
+            return self.forward_mask(views, shapes, prop_boxes, rows_count, min(self.R, 128), g.prop_masks, rows=rows, bufs=bufs,
+                                     lds_reserve=lds, tag=tag, g=g, boxes_per_image=self.R)
+        return self.forward_mask(views, shapes, prop_boxes, prop_count, self.R, g.prop_masks, bufs=bufs, lds_reserve=lds, tag=tag, g=g,
+                                 boxes_per_image=self.R)
+
+    # ---- detections: masks, post-processing, paste ----------------------------------------------------
+    def detection_masks(self, g: RoiBuffers, views, shapes, sel, slot: int, dedup: bool, lds_reserve: int, tag=None):
+        """`forward_with_given_boxes` (detic_roi_heads.py:257): the mask head on the detections `sel` (a `DetectionSelector` after its
+        call) of g.B scenes -- once per distinct box when `dedup` (the groups come from the detection selection's launch)."""
+        rows, count = g.roi_list(sel.rep_list, sel.rep_count, self.topk, slot) if dedup else g.roi_list(None, sel.count, self.topk, slot)
+        return self.forward_mask(views, shapes, sel.boxes, count, self.topk, g.det_masks, rows=rows, lds_reserve=lds_reserve, tag=tag,
+                                 g=g, boxes_per_image=self.topk)
+
+    def postprocess_and_paste(self, g: RoiBuffers, sel, post: dict, image_hw, mask_threshold: float, dedup: bool):
+        """`detector_postprocess` + paste (custom_rcnn.py:579-580) of g.B scenes' detections into result set `post`, at the input
+        size (output size != input size is not used on this path, train_mp3d.py:487-490)."""
+        H, W = image_hw
+        B, D, dev = g.B, self.topk, self.device
+        # this frame's own result tensors, from the caching allocator on the stream that fills them; `materialize` slices them
+        post["boxes"] = torch.empty((B * D, 4), dtype=torch.float32, device=dev)
+        post["scores"] = torch.empty((B * D,), dtype=torch.float32, device=dev)
+        post["classes"] = torch.empty((B * D,), dtype=torch.int32, device=dev)
+        post["masks"] = torch.empty((B, D, H, W), dtype=torch.uint8, device=dev)
+        ops.detector_postprocess(sel.boxes, sel.scores, sel.classes, sel.count, D, 1.0, 1.0, float(W), float(H), post["boxes"],
+                                 post["scores"], post["classes"], post["src"], post["count"], remap=sel.rep_of if dedup else None,
+                                 batch=g.batch)
+        ops.paste_masks(g.det_masks, post["boxes"], post["src"], post["count"], D, H, W, mask_threshold, post["masks"], batch=g.batch,
+                        prob_units=g.per_scene(D))
+
+    def detection_pass(self, g: RoiBuffers, views, shapes, sel, slot: int, post: dict, image_hw, mask_threshold: float, dedup: bool,
+                       lds_reserve: int, tag=None):
+        """Detection masks, post-processing and paste back to back (the in-order single-scene frame runs the proposal masks between
+        the two halves, so they stay callable on their own)."""
+        self.detection_masks(g, views, shapes, sel, slot, dedup, lds_reserve, tag)
+        self.postprocess_and_paste(g, sel, post, image_hw, mask_threshold, dedup)
+

@@ -201,6 +201,39 @@ def test_lockstep_of_one_and_other_memory_modes_equal_single_runs(synthetic_sd, 
         torch.cuda.empty_cache()
 
 
+def _set_knob(model, knob):
+    """`knob`: the attribute the test switches off, on the heads (`roi_heads.x`) or on the single-scene model itself."""
+    owner, _, name = knob.rpartition(".")
+    setattr(getattr(model, owner) if owner else model, name, False)
+
+
+@pytest.mark.parametrize("knob", ["roi_heads.merge_cls_bb0", "dedup_detection_masks"])
+def test_lockstep_honours_the_single_scene_knobs(synthetic_sd, knob):
+    """`roi_heads.merge_cls_bb0 = False` (the two linear layers as two launches) and `dedup_detection_masks = False` (one mask ROI per
+    detection) reach the lock-step batch through the shared stage functions: B = 2, three frames, outputs and final state bitwise
+    those of the two single-scene runs with the same knob."""
+    from embodied_object_detection_amd import build_model
+    from embodied_object_detection_amd.data.synthetic import SyntheticSequence
+    from embodied_object_detection_amd.modeling.lockstep import LockstepScenes
+    B, T = 2, 3
+    seqs = [SyntheticSequence(20 + b, H=128, W=160, n_frames=T, map_w=24, map_h=24, cell=0.5) for b in range(B)]
+    eps = [[s.frame(i) for i in range(T)] for s in seqs]
+    ls = LockstepScenes(_cfg(), B, synthetic_sd)
+    _set_knob(ls.model, knob)
+    outs = ls(eps)
+    for b in range(B):
+        single = build_model(_cfg(), synthetic_sd)
+        _set_knob(single, knob)
+        ref = single([eps[b]])
+        for t in range(T):
+            a, r = outs[b][t]["instances"], ref[t]["instances"]
+            assert torch.equal(a.pred_boxes.tensor, r.pred_boxes.tensor) and torch.equal(a.scores, r.scores), (b, t)
+            assert torch.equal(a.pred_classes, r.pred_classes) and torch.equal(a.pred_masks, r.pred_masks), (b, t)
+        assert torch.equal(ls.scenes[b].implicit_memory, single.implicit_memory) and torch.equal(ls.scenes[b].observations, single.observations)
+        del single
+        torch.cuda.empty_cache()
+
+
 def test_lockstep_schedules_are_bitwise_identical(synthetic_sd):
     """The step's streams (look-ahead trunk one step ahead, detection pass trailing under the next step) are a scheduling change only:
     with and without them, over two calls of 6 steps, every output and the final state of every scene are bitwise the same."""

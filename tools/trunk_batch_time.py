@@ -19,9 +19,9 @@ for N in (1, 2, 4):
     def run():
         c = m.backbone.bottom_up.forward(x, Hp, Wp, N=N) if N > 1 else m.backbone.bottom_up.forward(x, Hp, Wp)
         if N > 1:
-            m.backbone.top_down_batched(c, Hp, Wp, N)
+            m.backbone.top_down(c, N, planned=True)
         else:
-            m.backbone.top_down(c, Hp, Wp, 0)
+            m.backbone.top_down(c, 1, m.backbone._plan(Hp, Wp, 0)[3])
     run(); torch.cuda.synchronize()
     ts = []
     for _ in range(5):

@@ -47,7 +47,7 @@ torch.cuda.synchronize()
 print("as shipped                         ", " ".join(f"{v:6.1f}" for v in rate(model)), "frames/s")
 
 bu, bb = model.backbone.bottom_up, model.backbone
-real = (bu.forward, bb.top_down, bb.top_down_batched)
+real = (bu.forward, bb.top_down)
 kept = {}
 
 
@@ -58,22 +58,19 @@ def fake_forward(x, Hp, Wp, N=1):
     return kept[key]
 
 
-def fake_top_down(c, Hp, Wp, st):
-    return None                       # the set keeps an earlier frame's P3..P5
-
-
 tdb = {}
 
 
-def fake_top_down_batched(c, Hp, Wp, n):
-    key = (Hp, Wp, n)
-    if key not in tdb:
-        tdb[key] = real[2](c, Hp, Wp, n)
-    return tdb[key]
+def fake_top_down(c, N=1, views=None, planned=False):
+    if views is not None:
+        return views[:3]              # the set keeps an earlier frame's P3..P5
+    if N not in tdb:
+        tdb[N] = real[1](c, N, planned=planned)
+    return tdb[N]
 
 
-bu.forward, bb.top_down, bb.top_down_batched = fake_forward, fake_top_down, fake_top_down_batched
+bu.forward, bb.top_down = fake_forward, fake_top_down
 model([frames[:20]])
 torch.cuda.synchronize()
 print("look-ahead trunk + top-down removed", " ".join(f"{v:6.1f}" for v in rate(model)), "frames/s   (the three P3..P5 copies per frame remain)")
-bu.forward, bb.top_down, bb.top_down_batched = real
+bu.forward, bb.top_down = real
