@@ -1,4 +1,4 @@
-"""ctypes binding of libeod_hip.so (C ABI declared in include/eod_hip.h).
+"""ctypes binding of libeod_hip.so (C ABI declared in include/eod_hip.h; the frame-side map queries in include/eod_place.h).
 
 Fails loudly: there is no CPU fallback.  If the shared library is missing or a call returns a negative
 EOD_ERR_* code, an exception is raised.
@@ -236,6 +236,12 @@ SIGNATURES = {
     "eod_fill_i32": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/eod_place.h declares (the frame-side map queries)
+PLACE_SIGNATURES = {
+    "eod_place_masks_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "eod_place_masks": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -249,7 +255,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension is not built. Run `python -m embodied_object_detection_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -85,6 +85,21 @@ class RobotFrontEnd:
         return (float(cx * self.res + float(self.map_shift[0])), float(cy * self.res + float(self.map_shift[2])))
 
 
+    def cell_centers(self, cells) -> np.ndarray:
+        """`cell_center` for many memory indices `x * map_h + y` at once (the `cells` of `place`, the `peaks` of `locate`):
+        float64 [n, 2] in metres, NaN for the padding value -1."""
+        c = np.asarray(cells.cpu() if torch.is_tensor(cells) else cells, dtype=np.int64).reshape(-1)
+        cx, cy = np.divmod(c, self.map_h)
+        out = np.stack([cx * self.res + float(self.map_shift[0]), cy * self.res + float(self.map_shift[2])], axis=1).astype(np.float64)
+        out[c < 0] = np.nan
+        return out
+
+    def exclude_cell(self, pose_xyt: Sequence[float]) -> int:
+        """The robot's own cell as the memory's index `x * map_h + y`: the `exclude_cell` of `place`."""
+        x, y = self.robot_cell(pose_xyt)
+        return x * self.map_h + y
+
+
 def read_depth_mm(path: str) -> np.ndarray:
     """`cv2.imread(path, cv2.IMREAD_ANYDEPTH)` (robot_demo.py:498): the 16-bit depth PNG as uint16 millimetres, via Pillow."""
     from PIL import Image

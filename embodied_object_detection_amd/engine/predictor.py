@@ -82,6 +82,11 @@ class EmbodiedPredictor:
             classifier = resolve_vocabulary(vocabulary)
         return self.model.locate(classes, classifier=classifier, thresh=thresh, map_shape=map_shape, radius=radius, topk=topk)
 
+    def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
+        """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
+        returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""
+        return self.model.place(instances, data["proj_indices"], topk=topk, exclude_cell=exclude_cell, attach=attach)
+
     def _resized_hw(self, h: int, w: int):
         """`ResizeShortestEdge([480, 480], max_size).get_output_shape`."""
         scale = 480.0 / min(h, w)

@@ -41,8 +41,8 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
-from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _det_stream, _instances, _result_sets, _sched_streams, _semmap_locate,
-                        _semmap_query, _ticket)
+from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _det_stream, _instances, _place, _result_sets, _sched_streams,
+                        _semmap_locate, _semmap_query, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -207,6 +207,13 @@ class LockstepScenes:
             raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
         return _semmap_locate(self.model, self.implicit_memory[int(scene)], self.observations[int(scene)], classes, classifier,
                               num_classes, thresh, map_shape, radius, topk)
+
+    def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
+        """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""
+        if not 0 <= int(scene) < self.B:
+            raise IndexError(f"scene {scene} of a lock-step batch of {self.B}")
+        mem = None if self.implicit_memory is None else self.implicit_memory[int(scene)]
+        return _place(self.model, mem, instances, proj_indices, topk, exclude_cell, attach)
 
     def _refresh_snapshot(self):
         """a4 + fp16 cast for the B tables: they are one [B*N,512] table to the kernels."""

@@ -96,6 +96,33 @@ def _semmap_locate(model, mem, obs, classes, classifier, num_classes, thresh, ma
                              radius=radius, topk=topk)
 
 
+def place_rects(boxes: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """int32 [K, 4] half-open rects outside which the pasted masks of `boxes` (float [K, 4], x0 y0 x1 y1) are zero: the box grown
+    by (w / 14 + 1, h / 14 + 1) pixels, floor and ceil.  A pasted mask is exactly zero more than one mask pixel (box side / 28)
+    outside its box (`mw_cover_kernel`'s quick reject, csrc/memory.hip).  The values are only kept near the image here; the
+    kernel clips each rect to it."""
+    b = boxes.to(torch.float32)
+    m = (b[:, 2:] - b[:, :2]) / 14.0 + 1.0
+    r = torch.cat([torch.floor(b[:, :2] - m), torch.ceil(b[:, 2:] + m)], dim=1)
+    return r.clamp_(-1.0, float(max(H, W) + 1)).to(torch.int32)
+
+
+def _place(model, mem, instances, proj_indices, topk, exclude_cell, attach):
+    """`place` against one scene's cell count (`mem`: that scene's memory)."""
+    if mem is None:
+        raise _lib.EodError("place: no memory yet (no frame has run)")
+    proj = model._device_proj({"proj_indices": proj_indices})
+    masks = instances.pred_masks
+    if not masks.is_contiguous():
+        masks = masks.contiguous()
+    rects = place_rects(instances.pred_boxes.tensor, int(masks.shape[1]), int(masks.shape[2]))
+    out = ops.place_masks(masks, proj, int(mem.shape[0]), rects=rects, topk=topk, exclude_cell=exclude_cell)
+    if attach:
+        instances.pred_cells = out["cells"][:, 0]
+        instances.pred_cell_pixels = out["cell_pixels"][:, 0]
+    return out
+
+
 def _result_sets(B: int, D: int, hw: Tuple[int, int], dev) -> List[dict]:
     """RESULT_SETS result sets of B scenes with up to D detections each.  boxes / scores / classes / masks of a set are allocated anew
     for every frame (`roi_heads.postprocess_and_paste`) and handed to the caller as they are: no copy of the 0/1 byte masks
@@ -798,6 +825,15 @@ class CustomRCNNRecurrent:
         model."""
         return _semmap_locate(self, self.implicit_memory, self.observations, classes, classifier, num_classes, thresh, map_shape,
                               radius, topk)
+
+    def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
+        """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as
+        `ops.place_masks` returns them (`mask_pixels`, `pixels`, `invalid`, `distinct` [K]; `cells`, `cell_pixels` [K, topk], the
+        cells with the most mask pixels first, padded with -1 / 0).  `instances`: what the model returned for the frame;
+        `proj_indices`: the frame's, numpy or tensor, [H, W] or [H, W, 1].  `exclude_cell` drops one cell (the robot's own, where
+        zero-depth pixels land).  `attach=True` also sets `instances.pred_cells` (the cell with the most pixels, -1 for none) and
+        `instances.pred_cell_pixels`.  One op on the current stream; nothing of the model changes."""
+        return _place(self, self.implicit_memory, instances, proj_indices, topk, exclude_cell, attach)
 
     # ---- introspection used by tests / bench -----------------------------------------------------------
     def proposals_snapshot(self):

@@ -1451,3 +1451,69 @@ def semmap_locate(mem: torch.Tensor, obs: torch.Tensor, zs: torch.Tensor, classe
     k0 = p0 + 2 * Q * N
     return {"labels": labels, "scores": ws[4 + N:4 + 2 * N], "prob": ws[p0:p0 + Q * N].view(Q, N),
             "peaks": ws[k0:k0 + Q * K].view(torch.int32).view(Q, K), "peak_scores": ws[k0 + Q * K:k0 + 2 * Q * K].view(Q, K)}
+
+
+PLACE_TOPK_MAX, PLACE_TABLE_LOG2_MIN, PLACE_TABLE_LOG2_MAX, PLACE_TABLE_LOG2 = 8, 4, 12, 12     # EOD_PLACE_* of include/eod_place.h
+
+
+def place_masks_workspace(K_cap: int, n_cells: int) -> int:
+    """int32 words of a `place_masks` workspace (eod_place_masks_workspace_bytes / 4): the overflow list and the four dense
+    [n_cells] tables of the overflow kernel.  It does not grow with K_cap * n_cells."""
+    if K_cap < 0 or n_cells < 1:
+        raise _lib.EodError(f"place_masks_workspace: K_cap {K_cap}, n_cells {n_cells}")
+    return int(_lib.load().eod_place_masks_workspace_bytes(int(K_cap), int(n_cells))) // 4
+
+
+def place_masks(masks: torch.Tensor, proj: torch.Tensor, n_cells: int, count: Optional[torch.Tensor] = None,
+                rects: Optional[torch.Tensor] = None, topk: int = 4, exclude_cell: int = -1, table_log2: Optional[int] = None,
+                workspace: Optional[torch.Tensor] = None) -> dict:
+    """The grid cells under each instance mask (eod_place_masks; the semantics are those of include/eod_place.h).  `masks` [K_cap, H, W] uint8 or
+    bool, `proj` [H, W] int32, `count` a device int32 (rows beyond it come back as padding; None: all rows), `rects` int32
+    [K_cap, 4] half-open (x0, y0, x1, y1) outside which a mask is not read (None: the image).  Returns int32 tensors, views of
+    one buffer: `mask_pixels`, `pixels`, `invalid`, `distinct` [K_cap], `cells` and `cell_pixels` [K_cap, topk] (the cells with
+    the most pixels by count descending, cell ascending; padded with -1 / 0).  Pixels whose cell is `exclude_cell` are dropped;
+    cells outside [0, n_cells) are counted as `invalid` and never used.  `table_log2` (4..12, None: 12) sizes the kernel's hash
+    table and changes nothing in the result; `workspace`: int32, at least `place_masks_workspace(K_cap, n_cells)` words, any
+    contents."""
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool) or not masks.is_contiguous():
+        raise _lib.EodError(f"place_masks: masks {tuple(getattr(masks, 'shape', ()))} {getattr(masks, 'dtype', type(masks))}: "
+                            "expected contiguous uint8 or bool [K, H, W]")
+    if not masks.is_cuda:
+        raise _lib.EodError("place_masks: masks on the host (no CPU fallback)")
+    K_cap, H, W = (int(v) for v in masks.shape)
+    dev = masks.device
+    if (not isinstance(proj, torch.Tensor) or proj.dtype != torch.int32 or tuple(proj.shape) != (H, W) or not proj.is_contiguous()
+            or proj.device != dev):
+        raise _lib.EodError(f"place_masks: proj {tuple(getattr(proj, 'shape', ()))} {getattr(proj, 'dtype', type(proj))}: expected "
+                            f"contiguous int32 [{H}, {W}] on the masks' device")
+    n_cells, T, exclude_cell = int(n_cells), int(topk), int(exclude_cell)
+    if n_cells < 1:
+        raise _lib.EodError(f"place_masks: n_cells {n_cells}")
+    if H < 1 or W < 1 or H * W > 2 ** 31 - 5:
+        raise _lib.EodError(f"place_masks: image {H} x {W}")
+    if not 1 <= T <= PLACE_TOPK_MAX:
+        raise _lib.EodError(f"place_masks: topk {topk} outside 1..{PLACE_TOPK_MAX}")
+    if not -2 ** 31 <= exclude_cell < 2 ** 31:
+        raise _lib.EodError(f"place_masks: exclude_cell {exclude_cell}")
+    log2 = PLACE_TABLE_LOG2 if table_log2 is None else int(table_log2)
+    if not PLACE_TABLE_LOG2_MIN <= log2 <= PLACE_TABLE_LOG2_MAX:
+        raise _lib.EodError(f"place_masks: table_log2 {table_log2} outside {PLACE_TABLE_LOG2_MIN}..{PLACE_TABLE_LOG2_MAX}")
+    if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != 1 or count.device != dev):
+        raise _lib.EodError("place_masks: count: expected one int32 on the masks' device")
+    if rects is not None and (not isinstance(rects, torch.Tensor) or rects.dtype != torch.int32 or tuple(rects.shape) != (K_cap, 4)
+                              or not rects.is_contiguous() or rects.device != dev):
+        raise _lib.EodError(f"place_masks: rects: expected contiguous int32 [{K_cap}, 4] on the masks' device")
+    need = place_masks_workspace(K_cap, n_cells)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev):
+        raise _lib.EodError(f"place_masks: workspace: expected {need} contiguous int32 on the masks' device")
+    out = torch.empty(((4 + 2 * T) * K_cap,), dtype=torch.int32, device=dev)
+    if K_cap > 0:
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+        check(_lib.load().eod_place_masks(masks.data_ptr(), proj.data_ptr(), _ptr(count), _ptr(rects), K_cap, H, W, n_cells, T,
+                                          exclude_cell, log2, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 4, _stream()),
+              "eod_place_masks")
+    stats = out[:4 * K_cap].view(4, K_cap)
+    return {"mask_pixels": stats[0], "pixels": stats[1], "invalid": stats[2], "distinct": stats[3],
+            "cells": out[4 * K_cap:(4 + T) * K_cap].view(K_cap, T), "cell_pixels": out[(4 + T) * K_cap:].view(K_cap, T)}
