@@ -67,6 +67,28 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
   return v;
 }
 
+// 64-bit keys ((value << 32) | ~index) of the selection rounds of place.hip and regions.hip
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)(v >> 32), off, 64);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// maximum over the workgroup, in every thread; red_s: one word per wave
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red_s) {
+  v = wave_max_u64(v);
+  if ((threadIdx.x & 63) == 0) red_s[threadIdx.x >> 6] = v;
+  __syncthreads();
+  unsigned long long b = red_s[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) b = red_s[w] > b ? red_s[w] : b;
+  __syncthreads();
+  return b;
+}
+
 // Bijective XCD-aware remap of a linear workgroup id: workgroups that share an XCD (id % 8 equal under
 // round-robin dispatch) get a contiguous range of tile ids, so neighbouring tiles hit the same L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

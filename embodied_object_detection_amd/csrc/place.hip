@@ -103,27 +103,6 @@ __device__ __forceinline__ void place_word(unsigned word, int p, const int* __re
 
 __device__ __forceinline__ u64 place_key(int count, int cell) { return ((u64)(unsigned)count << 32) | (unsigned)~cell; }
 
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)(v >> 32), off, 64);
-    const u64 o = ((u64)hi << 32) | lo;
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-// maximum over the workgroup, in every thread; red_s: one word per wave
-__device__ __forceinline__ u64 block_max_u64(u64 v, u64* red_s) {
-  v = wave_max_u64(v);
-  if ((threadIdx.x & 63) == 0) red_s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  u64 b = red_s[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) b = red_s[w] > b ? red_s[w] : b;
-  __syncthreads();
-  return b;
-}
-
 // sums over the workgroup, in every thread; sum_s: N words
 template <int N>
 __device__ __forceinline__ void block_sum(int (&v)[N], int* sum_s) {

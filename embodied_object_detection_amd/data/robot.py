@@ -94,6 +94,18 @@ class RobotFrontEnd:
         out[c < 0] = np.nan
         return out
 
+    def region_centroids(self, sum_rc, area) -> np.ndarray:
+        """The centroids of the regions of `regions(..., map_shape=(map_w, map_h))` in metres: `sum_rc` [..., 2] over `area` [...],
+        with the index convention of `cell_center` (cell = x * map_h + y, so the row is x and the column is y).  float64 [..., 2];
+        NaN for the padding (area 0)."""
+        s = np.asarray(sum_rc.cpu() if torch.is_tensor(sum_rc) else sum_rc, dtype=np.float64)
+        a = np.asarray(area.cpu() if torch.is_tensor(area) else area, dtype=np.float64)
+        if s.shape != a.shape + (2,):
+            raise ValueError(f"region_centroids: sum_rc {s.shape} against area {a.shape}")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = np.where(a[..., None] > 0, s / a[..., None], np.nan)
+        return np.stack([mean[..., 0] * self.res + float(self.map_shift[0]), mean[..., 1] * self.res + float(self.map_shift[2])], axis=-1)
+
     def exclude_cell(self, pose_xyt: Sequence[float]) -> int:
         """The robot's own cell as the memory's index `x * map_h + y`: the `exclude_cell` of `place`."""
         x, y = self.robot_cell(pose_xyt)

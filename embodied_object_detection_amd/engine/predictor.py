@@ -82,6 +82,15 @@ class EmbodiedPredictor:
             classifier = resolve_vocabulary(vocabulary)
         return self.model.locate(classes, classifier=classifier, thresh=thresh, map_shape=map_shape, radius=radius, topk=topk)
 
+    def regions(self, classes, vocabulary: Optional[str] = None, classifier=None, thresh: Optional[float] = None, map_shape=None,
+                level: float = 0.5, connectivity: int = 8, min_cells: int = 1, topk: int = 16, radius: int = 1, peaks: int = 8) -> Dict:
+        """The map objects of the queried classes: the dict of `CustomRCNNRecurrent.regions`; `classes`, `vocabulary` and
+        `classifier` as in `locate`.  The model, its heads and the memory are left as they are."""
+        if vocabulary is not None and classifier is None:
+            classifier = resolve_vocabulary(vocabulary)
+        return self.model.regions(classes, classifier=classifier, thresh=thresh, map_shape=map_shape, level=level,
+                                  connectivity=connectivity, min_cells=min_cells, topk=topk, radius=radius, peaks=peaks)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

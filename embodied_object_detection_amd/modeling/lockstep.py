@@ -41,7 +41,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
-from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _det_stream, _instances, _place, _result_sets, _sched_streams,
+from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _det_stream, _instances, _map_regions, _place, _result_sets, _sched_streams,
                         _semmap_locate, _semmap_query, _ticket)
 from .roi_heads import RoiBuffers
 
@@ -207,6 +207,17 @@ class LockstepScenes:
             raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
         return _semmap_locate(self.model, self.implicit_memory[int(scene)], self.observations[int(scene)], classes, classifier,
                               num_classes, thresh, map_shape, radius, topk)
+
+    def regions(self, scene: int, classes, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None,
+                map_shape=None, level: float = 0.5, connectivity: int = 8, min_cells: int = 1, topk: int = 16, radius: int = 1,
+                peaks: int = 8):
+        """`CustomRCNNRecurrent.regions` on scene `scene`'s state.  Nothing of the batch model changes."""
+        if not 0 <= int(scene) < self.B:
+            raise IndexError(f"scene {scene} of a lock-step batch of {self.B}")
+        if self.implicit_memory is None:
+            raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
+        return _map_regions(self.model, self.implicit_memory[int(scene)], self.observations[int(scene)], classes, classifier,
+                            num_classes, thresh, map_shape, level, connectivity, min_cells, topk, radius, peaks)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

@@ -96,6 +96,20 @@ def _semmap_locate(model, mem, obs, classes, classifier, num_classes, thresh, ma
                              radius=radius, topk=topk)
 
 
+def _map_regions(model, mem, obs, classes, classifier, num_classes, thresh, map_shape, level, connectivity, min_cells, topk, radius,
+                 peaks):
+    """`regions` on one scene's state: `locate`, then `ops.map_regions` on its `prob`."""
+    if map_shape is None:
+        raise _lib.EodError("regions: map_shape (rows, cols) is required: the regions live on the grid")
+    out = dict(_semmap_locate(model, mem, obs, classes, classifier, num_classes, thresh, map_shape, radius, peaks))
+    reg = ops.map_regions(out["prob"], int(map_shape[1]), level, connectivity=connectivity, min_cells=min_cells, topk=topk)
+    status = int(reg["status"])                                      # the results are handed over here
+    if status != 0:
+        raise _lib.EodError(f"regions: a bounded loop of eod_map_regions reached its bound (status {status}); the result is void")
+    out.update(reg)
+    return out
+
+
 def place_rects(boxes: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """int32 [K, 4] half-open rects outside which the pasted masks of `boxes` (float [K, 4], x0 y0 x1 y1) are zero: the box grown
     by (w / 14 + 1, h / 14 + 1) pixels, floor and ceil.  A pasted mask is exactly zero more than one mask pixel (box side / 28)
@@ -825,6 +839,17 @@ class CustomRCNNRecurrent:
         model."""
         return _semmap_locate(self, self.implicit_memory, self.observations, classes, classifier, num_classes, thresh, map_shape,
                               radius, topk)
+
+    def regions(self, classes, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None, map_shape=None,
+                level: float = 0.5, connectivity: int = 8, min_cells: int = 1, topk: int = 16, radius: int = 1, peaks: int = 8) -> dict:
+        """The map objects of the queried classes: `locate(classes, ..., map_shape, radius, topk=peaks)` and, on its `prob`, the
+        connected regions of the cells with `prob >= level` as `ops.map_regions` returns them (`region_labels` [Q, N], `count`,
+        `foreground` [Q], and for the `topk` largest regions of at least `min_cells` cells `region`, `area`, `bbox`, `sum_rc`, `peak`,
+        `peak_prob`, `mass_q24`, `status`), in one dict with locate's keys.  `map_shape` = (rows, cols) is required.
+        `region_labels[q, cell]` names the map object a cell belongs to (a `pred_cells` of `place`, for one).  Raises `EodError`
+        if the op's status is nonzero.  Changes nothing in the model."""
+        return _map_regions(self, self.implicit_memory, self.observations, classes, classifier, num_classes, thresh, map_shape, level,
+                            connectivity, min_cells, topk, radius, peaks)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

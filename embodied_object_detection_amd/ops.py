@@ -1517,3 +1517,68 @@ def place_masks(masks: torch.Tensor, proj: torch.Tensor, n_cells: int, count: Op
     stats = out[:4 * K_cap].view(4, K_cap)
     return {"mask_pixels": stats[0], "pixels": stats[1], "invalid": stats[2], "distinct": stats[3],
             "cells": out[4 * K_cap:(4 + T) * K_cap].view(K_cap, T), "cell_pixels": out[(4 + T) * K_cap:].view(K_cap, T)}
+
+
+# EOD_REGIONS_* of include/eod_regions.h
+REGIONS_Q_MAX, REGIONS_TOPK_MAX, REGIONS_N_MAX, REGIONS_TILE_ROWS, REGIONS_TILE_COLS = 32, 64, 1 << 22, 32, 32
+
+
+def map_regions_workspace(Q: int, N: int, topk: int) -> int:
+    """int32 words of a `map_regions` workspace (eod_map_regions_workspace_bytes / 4): three [Q, N] arrays and Q * topk peak keys."""
+    need = int(_lib.load().eod_map_regions_workspace_bytes(int(Q), int(N), int(topk)))
+    if need == 0:
+        raise _lib.EodError(f"map_regions_workspace: Q {Q}, N {N}, topk {topk}")
+    return need // 4
+
+
+def map_regions(prob: torch.Tensor, cols: int, level: float, connectivity: int = 8, min_cells: int = 1, topk: int = 16,
+                workspace: Optional[torch.Tensor] = None) -> dict:
+    """The connected regions of each class of a map, ranked by size (eod_map_regions; the semantics are those of
+    include/eod_regions.h).  `prob` [Q, N] float32 (the `prob` of `semmap_locate`, or any map), cell i = r * cols + c; the foreground
+    of a class is `prob >= level`, two cells are neighbours under `connectivity` 4 or 8 on the grid, a component's label is its
+    smallest cell.  Returns `region_labels` int32 [Q, N] (-1: background), `count` and `foreground` int32 [Q], `status` int32 [1]
+    (nonzero: a kernel's bounded loop reached its bound; not read here, so nothing synchronises) and, per class for the `topk`
+    components of at least `min_cells` cells by (area descending, label ascending), padded with region -1 and zeros: `region`, `area`,
+    `peak` int32 [Q, K], `peak_prob` float32 [Q, K], `bbox` int32 [Q, K, 4] (r0, c0, r1, c1 inclusive), `sum_rc` int64 [Q, K, 2],
+    `mass_q24` int64 [Q, K].  All but `region_labels` are views of one buffer.  `workspace`: int32, 8-byte aligned, at least
+    `map_regions_workspace(Q, N, topk)` words, any contents."""
+    if (not isinstance(prob, torch.Tensor) or prob.dim() != 2 or prob.dtype != torch.float32 or not prob.is_contiguous()):
+        raise _lib.EodError(f"map_regions: prob {tuple(getattr(prob, 'shape', ()))} {getattr(prob, 'dtype', type(prob))}: expected "
+                            "contiguous float32 [Q, N]")
+    Q, N = (int(v) for v in prob.shape)
+    dev = prob.device
+    if not 1 <= Q <= REGIONS_Q_MAX:
+        raise _lib.EodError(f"map_regions: prob: Q {Q} outside 1..{REGIONS_Q_MAX}")
+    if not 1 <= N <= REGIONS_N_MAX:
+        raise _lib.EodError(f"map_regions: prob: N {N} outside 1..{REGIONS_N_MAX}")
+    if isinstance(cols, bool) or int(cols) != cols or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_regions: cols {cols} does not divide the {N} cells")
+    level32 = float(torch.tensor(float(level), dtype=torch.float32))            # what the kernel compares against
+    if not 0.0 < level32 <= 1.0:                                                 # a NaN and the infinities fail it
+        raise _lib.EodError(f"map_regions: level {level} outside (0, 1]")
+    if connectivity not in (4, 8):
+        raise _lib.EodError(f"map_regions: connectivity {connectivity}: 4 or 8")
+    if int(min_cells) != min_cells or int(min_cells) < 1 or int(min_cells) >= 2 ** 31:
+        raise _lib.EodError(f"map_regions: min_cells {min_cells} below 1")
+    if int(topk) != topk or not 1 <= int(topk) <= REGIONS_TOPK_MAX:
+        raise _lib.EodError(f"map_regions: topk {topk} outside 1..{REGIONS_TOPK_MAX}")
+    if not prob.is_cuda:
+        raise _lib.EodError("map_regions: prob on the host (no CPU fallback)")
+    K = int(topk)
+    need = map_regions_workspace(Q, N, K)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev
+                                  or workspace.data_ptr() % 8 != 0):
+        raise _lib.EodError(f"map_regions: workspace: expected {need} contiguous, 8-byte aligned int32 on the map's device")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+    labels = torch.empty((Q, N), dtype=torch.int32, device=dev)
+    out = torch.empty((2 + 2 * Q + 14 * Q * K,), dtype=torch.int32, device=dev)
+    check(_lib.load().eod_map_regions(prob.data_ptr(), Q, N, int(cols), level32, int(connectivity), int(min_cells), K, labels.data_ptr(),
+                                      out.data_ptr(), workspace.data_ptr(), workspace.numel() * 4, _stream()), "eod_map_regions")
+    b, QK = 2 + 2 * Q, Q * K
+    return {"region_labels": labels, "status": out[:1], "count": out[2:2 + Q], "foreground": out[2 + Q:b],
+            "region": out[b:b + QK].view(Q, K), "area": out[b + QK:b + 2 * QK].view(Q, K), "peak": out[b + 2 * QK:b + 3 * QK].view(Q, K),
+            "peak_prob": out[b + 3 * QK:b + 4 * QK].view(torch.float32).view(Q, K), "bbox": out[b + 4 * QK:b + 8 * QK].view(Q, K, 4),
+            "sum_rc": out[b + 8 * QK:b + 12 * QK].view(torch.int64).view(Q, K, 2),
+            "mass_q24": out[b + 12 * QK:b + 14 * QK].view(torch.int64).view(Q, K)}
