@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libeod_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_fp32.hip", "conv_pointwise.hip", "conv_bf16x3.hip", "conv_f16.hip", "elementwise.hip", "roi_align.hip", "select.hip", "heads.hip", "memory.hip", "semmap.hip", "place.hip", "regions.hip", "memory_read.hip", "memory_backward.hip", "conv_wgrad.hip", "train_losses.hip"]
+SOURCES = ["conv_igemm.hip", "conv_fp32.hip", "conv_pointwise.hip", "conv_bf16x3.hip", "conv_f16.hip", "elementwise.hip", "roi_align.hip", "select.hip", "heads.hip", "memory.hip", "semmap.hip", "place.hip", "regions.hip", "inventory.hip", "memory_read.hip", "memory_backward.hip", "conv_wgrad.hip", "train_losses.hip"]
 ARCH = "gfx950"
 
 
@@ -19,7 +19,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("eod_hip.h", "eod_place.h", "eod_regions.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("eod_hip.h", "eod_place.h", "eod_regions.h", "eod_inventory.h")]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
@@ -76,10 +76,16 @@ def build(force: bool = False, verbose: bool = True) -> str:
     failed = [s for s, p in procs if p.wait() != 0]
     for src in SOURCES:                       # the compiler's other diagnostics (warnings, errors) still reach the terminal
         skip = 0
+        held = []                                     # "In file included from" lines: they belong to the diagnostic after them
         for line in open(_usage_file(src)):
-            if "kernel-resource-usage" in line:
+            if line.startswith("In file included from"):
+                held.append(line)
+                continue
+            trace, held = held, []
+            if "kernel-resource-usage" in line:       # a remark on a kernel of a shared header comes with its include trace
                 skip = 2 if "Function Name" in line else 0      # the remark that names a kernel is followed by its source line + caret
                 continue
+            sys.stderr.writelines(trace)
             if skip and (line.lstrip()[:1].isdigit() or line.strip().startswith("|")):
                 skip -= 1
                 continue

@@ -97,7 +97,8 @@ class RobotFrontEnd:
     def region_centroids(self, sum_rc, area) -> np.ndarray:
         """The centroids of the regions of `regions(..., map_shape=(map_w, map_h))` in metres: `sum_rc` [..., 2] over `area` [...],
         with the index convention of `cell_center` (cell = x * map_h + y, so the row is x and the column is y).  float64 [..., 2];
-        NaN for the padding (area 0)."""
+        NaN for the padding (area 0).  The `sum_rc` and `area` of `inventory(..., map_shape=(map_w, map_h))` are served alike: its
+        objects are summed the same way, [K, 2] over [K] (or [B, K, 2] over [B, K])."""
         s = np.asarray(sum_rc.cpu() if torch.is_tensor(sum_rc) else sum_rc, dtype=np.float64)
         a = np.asarray(area.cpu() if torch.is_tensor(area) else area, dtype=np.float64)
         if s.shape != a.shape + (2,):

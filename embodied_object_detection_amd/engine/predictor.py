@@ -91,6 +91,15 @@ class EmbodiedPredictor:
         return self.model.regions(classes, classifier=classifier, thresh=thresh, map_shape=map_shape, level=level,
                                   connectivity=connectivity, min_cells=min_cells, topk=topk, radius=radius, peaks=peaks)
 
+    def inventory(self, vocabulary: Optional[str] = None, classifier=None, thresh: Optional[float] = None, map_shape=None,
+                  level: float = 0.5, connectivity: int = 8, min_cells: int = 1, topk: int = 16, exclude=None) -> Dict:
+        """What the map holds, all classes at once: the dict of `CustomRCNNRecurrent.inventory`; `vocabulary` and `classifier` as in
+        `semantic_map`.  The model, its heads and the memory are left as they are."""
+        if vocabulary is not None and classifier is None:
+            classifier = resolve_vocabulary(vocabulary)
+        return self.model.inventory(classifier=classifier, thresh=thresh, map_shape=map_shape, level=level, connectivity=connectivity,
+                                    min_cells=min_cells, topk=topk, exclude=exclude)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

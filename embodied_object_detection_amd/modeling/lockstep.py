@@ -41,8 +41,8 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
-from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _det_stream, _instances, _map_regions, _place, _result_sets, _sched_streams,
-                        _semmap_locate, _semmap_query, _ticket)
+from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _det_stream, _instances, _map_inventory, _map_regions, _place, _result_sets,
+                        _sched_streams, _semmap_locate, _semmap_query, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -218,6 +218,19 @@ class LockstepScenes:
             raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
         return _map_regions(self.model, self.implicit_memory[int(scene)], self.observations[int(scene)], classes, classifier,
                             num_classes, thresh, map_shape, level, connectivity, min_cells, topk, radius, peaks)
+
+    def inventory(self, scene: Optional[int] = None, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None,
+                  map_shape=None, level: float = 0.5, connectivity: int = 8, min_cells: int = 1, topk: int = 16, exclude=None):
+        """`CustomRCNNRecurrent.inventory` on scene `scene`'s state; `scene=None`: all B scenes, queried one after the other and
+        handed to the op as one [B, N] call (every entry of the dict but `status` gains a leading [B]).  Nothing of the batch model changes."""
+        if scene is not None and not 0 <= int(scene) < self.B:
+            raise IndexError(f"scene {scene} of a lock-step batch of {self.B}")
+        if self.implicit_memory is None:
+            raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
+        scenes = range(self.B) if scene is None else [int(scene)]
+        states = [(self.implicit_memory[b], self.observations[b]) for b in scenes]
+        return _map_inventory(self.model, states if scene is None else states[0], classifier, num_classes, thresh, map_shape, level,
+                              connectivity, min_cells, topk, exclude)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

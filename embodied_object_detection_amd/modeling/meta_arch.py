@@ -110,6 +110,42 @@ def _map_regions(model, mem, obs, classes, classifier, num_classes, thresh, map_
     return out
 
 
+def _map_inventory(model, states, classifier, num_classes, thresh, map_shape, level, connectivity, min_cells, topk, exclude):
+    """`inventory` on the states [(mem, obs), ...] of one scene or of several: `semantic_map(scores=True)` in query form on each,
+    then one `ops.map_inventory` call on all of them ([N] maps for one state, [B, N] for a list of B)."""
+    if map_shape is None:
+        raise _lib.EodError("inventory: map_shape (rows, cols) is required: the objects live on the grid")
+    single = not isinstance(states, list)
+    states = [states] if single else states
+    zs = _query_matrix(model, states[0][0], classifier, num_classes)
+    rows, cols = int(map_shape[0]), int(map_shape[1])
+    if rows * cols != states[0][0].shape[0]:
+        raise _lib.EodError(f"inventory: map_shape {tuple(map_shape)} does not hold the memory's {states[0][0].shape[0]} cells")
+    C = int(zs.shape[1]) - 1                                        # the last column is the background
+    keep = None
+    if exclude is not None:
+        exclude = [int(c) for c in (exclude.tolist() if isinstance(exclude, torch.Tensor) else exclude)]
+        bad = [c for c in exclude if not 0 <= c < C]
+        if bad:
+            raise _lib.EodError(f"inventory: exclude: class indices {bad} outside [0, {C - 1}]")
+        table = torch.ones((C,), dtype=torch.uint8)
+        table[exclude] = 0
+        keep = table.to(model.device)
+    th = model.obs_score_thresh if thresh is None else float(thresh)
+    maps = [ops.semmap_query(mem, obs, zs, th) for mem, obs in states]
+    if single:
+        labels, scores = maps[0]
+    else:
+        labels, scores = torch.stack([m[0] for m in maps]), torch.stack([m[1] for m in maps])
+    inv = ops.map_inventory(labels, scores, cols, C, level=level, connectivity=connectivity, min_cells=min_cells, topk=topk, keep=keep)
+    status = int(inv["status"])                                      # the results are handed over here
+    if status != 0:
+        raise _lib.EodError(f"inventory: a bounded loop of eod_map_inventory reached its bound (status {status}); the result is void")
+    out = {"labels": labels, "scores": scores}
+    out.update(inv)
+    return out
+
+
 def place_rects(boxes: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """int32 [K, 4] half-open rects outside which the pasted masks of `boxes` (float [K, 4], x0 y0 x1 y1) are zero: the box grown
     by (w / 14 + 1, h / 14 + 1) pixels, floor and ceil.  A pasted mask is exactly zero more than one mask pixel (box side / 28)
@@ -850,6 +886,18 @@ class CustomRCNNRecurrent:
         if the op's status is nonzero.  Changes nothing in the model."""
         return _map_regions(self, self.implicit_memory, self.observations, classes, classifier, num_classes, thresh, map_shape, level,
                             connectivity, min_cells, topk, radius, peaks)
+
+    def inventory(self, classifier=None, num_classes: Optional[int] = None, thresh: Optional[float] = None, map_shape=None,
+                  level: float = 0.5, connectivity: int = 8, min_cells: int = 1, topk: int = 16, exclude=None) -> dict:
+        """What the map holds, all classes at once: `semantic_map(classifier, num_classes, thresh, scores=True)` as `labels` and
+        `scores` [N] and, on them, every object as `ops.map_inventory` returns it: a connected area of cells that carry one label
+        with `scores >= level` (`object_labels` [N], `count`, `foreground`; for the `topk` largest objects of at least `min_cells`
+        cells over all classes `object`, `cls`, `area`, `bbox`, `sum_rc`, `peak`, `peak_score`, `mass_q24`; per class
+        `class_objects`, `class_cells`, `class_largest`, `class_largest_area` [C]; `status`).  `map_shape` = (rows, cols) is required.
+        `exclude`: class indices to leave out (walls and floors would otherwise be the largest objects).  `level = 2 ** -11` keeps
+        every labelled cell of any vocabulary.  Raises `EodError` if the op's status is nonzero.  Changes nothing in the model."""
+        return _map_inventory(self, (self.implicit_memory, self.observations), classifier, num_classes, thresh, map_shape, level,
+                              connectivity, min_cells, topk, exclude)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

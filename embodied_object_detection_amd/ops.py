@@ -1582,3 +1582,98 @@ def map_regions(prob: torch.Tensor, cols: int, level: float, connectivity: int =
             "peak_prob": out[b + 3 * QK:b + 4 * QK].view(torch.float32).view(Q, K), "bbox": out[b + 4 * QK:b + 8 * QK].view(Q, K, 4),
             "sum_rc": out[b + 8 * QK:b + 12 * QK].view(torch.int64).view(Q, K, 2),
             "mass_q24": out[b + 12 * QK:b + 14 * QK].view(torch.int64).view(Q, K)}
+
+
+# EOD_INVENTORY_* of include/eod_inventory.h
+INVENTORY_B_MAX, INVENTORY_C_MAX, INVENTORY_TOPK_MAX, INVENTORY_N_MAX = 32, 2047, 64, 1 << 22
+
+
+def map_inventory_workspace(B: int, N: int, C: int, topk: int) -> int:
+    """int32 words of a `map_inventory` workspace (eod_map_inventory_workspace_bytes / 4): three [B, N] arrays, B * topk peak keys and
+    B * C class keys."""
+    need = int(_lib.load().eod_map_inventory_workspace_bytes(int(B), int(N), int(C), int(topk)))
+    if need == 0:
+        raise _lib.EodError(f"map_inventory_workspace: B {B}, N {N}, C {C}, topk {topk}")
+    return need // 4
+
+
+def map_inventory(labels: torch.Tensor, scores: torch.Tensor, cols: int, num_classes: int, level: float = 0.5, connectivity: int = 8,
+                  min_cells: int = 1, topk: int = 16, keep: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> dict:
+    """Every object of a label map, all classes in one call (eod_map_inventory; the semantics are those of
+    include/eod_inventory.h).  `labels` int32 and `scores` float32, [N] or [B, N] (what `semmap_query` returns, or any label map),
+    cell i = r * cols + c.  A cell is foreground when 0 <= label < `num_classes`, `keep` (uint8 or bool [num_classes], None: every
+    class) holds a nonzero for its label and its score is >= `level`; two foreground cells are neighbours under `connectivity` 4 or 8
+    on the grid when they carry the same label; an object's label is its smallest cell.  `level = 2 ** -11` lies below any argmax
+    probability of a vocabulary of up to 2047 classes (the largest of at most 2048 softmax terms is at least 1 / 2048), so it keeps
+    every labelled cell.  Returns `object_labels` int32 (-1: background) in the shape of `labels`, `status` int32 [1] (nonzero: a
+    kernel's bounded loop reached its bound; not read here, so nothing synchronises) and, with the leading [B] only for [B, N] maps:
+    `count`, `foreground` int32 [B]; for the `topk` objects of at least `min_cells` cells by (area descending, label ascending) over
+    all classes, padded with object -1, cls -1 and zeros: `object`, `cls`, `area`, `peak` int32 [B, K], `peak_score` float32 [B, K],
+    `bbox` int32 [B, K, 4] (r0, c0, r1, c1 inclusive), `sum_rc` int64 [B, K, 2], `mass_q24` int64 [B, K]; and per class, int32
+    [B, num_classes]: `class_objects` (objects of at least `min_cells` cells), `class_cells` (foreground cells, all of them),
+    `class_largest` (the label of the class's first object in the same order, -1 for none), `class_largest_area`.  All but
+    `object_labels` are views of one buffer.  `workspace`: int32, 8-byte aligned, at least
+    `map_inventory_workspace(B, N, num_classes, topk)` words, any contents."""
+    def is_map(t, dtype):
+        return isinstance(t, torch.Tensor) and t.dim() in (1, 2) and t.dtype == dtype and t.is_contiguous()
+    if not is_map(labels, torch.int32):
+        raise _lib.EodError(f"map_inventory: labels {tuple(getattr(labels, 'shape', ()))} {getattr(labels, 'dtype', type(labels))}: expected "
+                            "contiguous int32 [N] or [B, N]")
+    if not is_map(scores, torch.float32) or scores.shape != labels.shape or scores.device != labels.device:
+        raise _lib.EodError(f"map_inventory: scores {tuple(getattr(scores, 'shape', ()))} {getattr(scores, 'dtype', type(scores))}: expected "
+                            f"contiguous float32 {tuple(labels.shape)} on the labels' device")
+    single = labels.dim() == 1
+    B, N = (1, int(labels.shape[0])) if single else (int(v) for v in labels.shape)
+    dev = labels.device
+    if not 1 <= B <= INVENTORY_B_MAX:
+        raise _lib.EodError(f"map_inventory: labels: B {B} outside 1..{INVENTORY_B_MAX}")
+    if not 1 <= N <= INVENTORY_N_MAX:
+        raise _lib.EodError(f"map_inventory: labels: N {N} outside 1..{INVENTORY_N_MAX}")
+    if isinstance(cols, bool) or int(cols) != cols or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_inventory: cols {cols} does not divide the {N} cells")
+    if isinstance(num_classes, bool) or int(num_classes) != num_classes or not 1 <= int(num_classes) <= INVENTORY_C_MAX:
+        raise _lib.EodError(f"map_inventory: num_classes {num_classes} outside 1..{INVENTORY_C_MAX}")
+    C = int(num_classes)
+    level32 = float(torch.tensor(float(level), dtype=torch.float32))            # what the kernel compares against
+    if not 0.0 < level32 <= 1.0:                                                 # a NaN and the infinities fail it
+        raise _lib.EodError(f"map_inventory: level {level} outside (0, 1]")
+    if connectivity not in (4, 8):
+        raise _lib.EodError(f"map_inventory: connectivity {connectivity}: 4 or 8")
+    if int(min_cells) != min_cells or int(min_cells) < 1 or int(min_cells) >= 2 ** 31:
+        raise _lib.EodError(f"map_inventory: min_cells {min_cells} below 1")
+    if int(topk) != topk or not 1 <= int(topk) <= INVENTORY_TOPK_MAX:
+        raise _lib.EodError(f"map_inventory: topk {topk} outside 1..{INVENTORY_TOPK_MAX}")
+    if keep is not None and (not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.uint8, torch.bool) or tuple(keep.shape) != (C,)
+                             or not keep.is_contiguous() or keep.device != dev):
+        raise _lib.EodError(f"map_inventory: keep {tuple(getattr(keep, 'shape', ()))} {getattr(keep, 'dtype', type(keep))}: expected "
+                            f"contiguous uint8 or bool [{C}] on the labels' device")
+    K = int(topk)
+    need = map_inventory_workspace(B, N, C, K)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev
+                                  or workspace.data_ptr() % 8 != 0):
+        raise _lib.EodError(f"map_inventory: workspace: expected {need} contiguous, 8-byte aligned int32 on the maps' device")
+    if not labels.is_cuda:
+        raise _lib.EodError("map_inventory: labels on the host (no CPU fallback)")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+    object_labels = torch.empty_like(labels)
+    out = torch.empty((2 + 2 * B + 15 * B * K + 4 * B * C,), dtype=torch.int32, device=dev)
+    check(_lib.load().eod_map_inventory(labels.data_ptr(), scores.data_ptr(), _ptr(keep), B, N, int(cols), C, level32, int(connectivity),
+                                        int(min_cells), K, object_labels.data_ptr(), out.data_ptr(), workspace.data_ptr(),
+                                        workspace.numel() * 4, _stream()), "eod_map_inventory")
+    s, BK, BC = 2 + 2 * B, B * K, B * C
+    t = s + 15 * BK
+    res = {"count": out[2:2 + B], "foreground": out[2 + B:s],
+           "object": out[s:s + BK].view(B, K), "area": out[s + BK:s + 2 * BK].view(B, K), "peak": out[s + 2 * BK:s + 3 * BK].view(B, K),
+           "peak_score": out[s + 3 * BK:s + 4 * BK].view(torch.float32).view(B, K), "bbox": out[s + 4 * BK:s + 8 * BK].view(B, K, 4),
+           "sum_rc": out[s + 8 * BK:s + 12 * BK].view(torch.int64).view(B, K, 2),
+           "mass_q24": out[s + 12 * BK:s + 14 * BK].view(torch.int64).view(B, K), "cls": out[s + 14 * BK:t].view(B, K),
+           "class_objects": out[t:t + BC].view(B, C), "class_cells": out[t + BC:t + 2 * BC].view(B, C),
+           "class_largest": out[t + 2 * BC:t + 3 * BC].view(B, C), "class_largest_area": out[t + 3 * BC:t + 4 * BC].view(B, C)}
+    if single:
+        res = {k: v[0] for k, v in res.items()}
+    res["object_labels"] = object_labels
+    res["status"] = out[:1]
+    return res
