@@ -1,5 +1,6 @@
 """ctypes binding of libeod_hip.so (C ABI declared in include/eod_hip.h; the frame-side map queries in include/eod_place.h, the
-map regions in include/eod_regions.h, the map inventory in include/eod_inventory.h).
+map regions in include/eod_regions.h, the map inventory in include/eod_inventory.h, the object descriptions in
+include/eod_describe.h).
 
 Fails loudly: there is no CPU fallback.  If the shared library is missing or a call returns a negative
 EOD_ERR_* code, an exception is raised.
@@ -255,6 +256,12 @@ INVENTORY_SIGNATURES = {
     "eod_map_inventory": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/eod_describe.h declares (pooled embedding and classes per map object)
+DESCRIBE_SIGNATURES = {
+    "eod_describe_pool": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 5),
+    "eod_describe_classify": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p] * 4),
+}
+
 _lib = None
 
 
@@ -268,7 +275,8 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension is not built. Run `python -m embodied_object_detection_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES, **REGIONS_SIGNATURES, **INVENTORY_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES, **REGIONS_SIGNATURES, **INVENTORY_SIGNATURES,
+                              **DESCRIBE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -100,6 +100,14 @@ class EmbodiedPredictor:
         return self.model.inventory(classifier=classifier, thresh=thresh, map_shape=map_shape, level=level, connectivity=connectivity,
                                     min_cells=min_cells, topk=topk, exclude=exclude)
 
+    def describe(self, objects, object_labels, vocabulary: Optional[str] = None, classifier=None, topn: int = 5, embedding=None) -> Dict:
+        """What the map objects are, each as a whole: the dict of `CustomRCNNRecurrent.describe` (`embedding`, `coherence`, `prob`,
+        `top_cls`, `top_prob`, ...) for the objects of an `inventory`; `vocabulary` and `classifier` as in `semantic_map`.  The model,
+        its heads and the memory are left as they are."""
+        if vocabulary is not None and classifier is None:
+            classifier = resolve_vocabulary(vocabulary)
+        return self.model.describe(objects, object_labels, classifier=classifier, topn=topn, embedding=embedding)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

@@ -41,8 +41,8 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
-from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _det_stream, _instances, _map_inventory, _map_regions, _place, _result_sets,
-                        _sched_streams, _semmap_locate, _semmap_query, _ticket)
+from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _describe, _det_stream, _instances, _map_inventory, _map_regions, _place,
+                        _result_sets, _sched_streams, _semmap_locate, _semmap_query, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -231,6 +231,15 @@ class LockstepScenes:
         states = [(self.implicit_memory[b], self.observations[b]) for b in scenes]
         return _map_inventory(self.model, states if scene is None else states[0], classifier, num_classes, thresh, map_shape, level,
                               connectivity, min_cells, topk, exclude)
+
+    def describe(self, scene: int, objects, object_labels, classifier=None, num_classes: Optional[int] = None, topn: int = 5,
+                 embedding=None):
+        """`CustomRCNNRecurrent.describe` on scene `scene`'s memory.  Nothing of the batch model changes."""
+        if not 0 <= int(scene) < self.B:
+            raise IndexError(f"scene {scene} of a lock-step batch of {self.B}")
+        if self.implicit_memory is None:
+            raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
+        return _describe(self.model, self.implicit_memory[int(scene)], objects, object_labels, classifier, num_classes, topn, embedding)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

@@ -146,6 +146,20 @@ def _map_inventory(model, states, classifier, num_classes, thresh, map_shape, le
     return out
 
 
+def _describe(model, mem, objects, object_labels, classifier, num_classes, topn, embedding):
+    """`describe` on one scene's memory: `ops.describe_pool` (skipped with `embedding`), then `ops.describe_classify` with the
+    class matrix of `_query_matrix`."""
+    zs = _query_matrix(model, mem, classifier, num_classes)
+    out = {}
+    if embedding is None:
+        if not isinstance(objects, torch.Tensor):
+            objects = torch.as_tensor(objects, dtype=torch.int32, device=mem.device)
+        out.update(ops.describe_pool(mem, object_labels, objects))
+        embedding = out["embedding"]
+    out.update(ops.describe_classify(embedding, zs, topn=topn))
+    return out
+
+
 def place_rects(boxes: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """int32 [K, 4] half-open rects outside which the pasted masks of `boxes` (float [K, 4], x0 y0 x1 y1) are zero: the box grown
     by (w / 14 + 1, h / 14 + 1) pixels, floor and ceil.  A pasted mask is exactly zero more than one mask pixel (box side / 28)
@@ -898,6 +912,17 @@ class CustomRCNNRecurrent:
         every labelled cell of any vocabulary.  Raises `EodError` if the op's status is nonzero.  Changes nothing in the model."""
         return _map_inventory(self, (self.implicit_memory, self.observations), classifier, num_classes, thresh, map_shape, level,
                               connectivity, min_cells, topk, exclude)
+
+    def describe(self, objects, object_labels, classifier=None, num_classes: Optional[int] = None, topn: int = 5, embedding=None) -> dict:
+        """What the map objects are, each as a whole: the memory rows of an object's cells pooled into one CLIP-space direction
+        (`ops.describe_pool`: `sum_q`, `cells`, `embedding` [K, 512], `coherence` [K]) and that direction classified
+        (`ops.describe_classify`: `prob` [K, C], `top_cls`, `top_prob` [K, topn]) in the model's own vocabulary or in `classifier`
+        (as in `semantic_map`), in one dict.  `objects` int32 [K] (a sequence will do) and `object_labels` int32 [N]: `inv["object"]`
+        and `inv["object_labels"]` of `inventory`, or a row of `region_labels` of `regions` with its `region` row.  With
+        `embedding=` (an earlier call's, or a snapshot's) the pooling is skipped: the same objects asked in another vocabulary, no
+        pass over the cells; `objects` and `object_labels` are then not read.  Embeddings of two maps compare as
+        `a["embedding"] @ b["embedding"].T`.  Changes nothing in the model."""
+        return _describe(self, self.implicit_memory, objects, object_labels, classifier, num_classes, topn, embedding)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

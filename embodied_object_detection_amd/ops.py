@@ -1677,3 +1677,83 @@ def map_inventory(labels: torch.Tensor, scores: torch.Tensor, cols: int, num_cla
     res["object_labels"] = object_labels
     res["status"] = out[:1]
     return res
+
+
+DESCRIBE_D, DESCRIBE_K_MAX, DESCRIBE_N_MAX, DESCRIBE_C_MAX, DESCRIBE_TOPN_MAX = 512, 64, 1 << 22, 2047, 8
+
+
+def _describe_what(t) -> str:
+    return f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}"
+
+
+def describe_pool(mem: torch.Tensor, object_labels: torch.Tensor, objects: torch.Tensor) -> dict:
+    """One CLIP-space direction per map object (eod_describe_pool; the semantics are those of include/eod_describe.h).  `mem`
+    float32 [N, 512], the memory's sum rows; `object_labels` int32 [N], the `object_labels` of `map_inventory`, a row of the
+    `region_labels` of `map_regions` or any other label map; `objects` int32 [K], 1 <= K <= 64, the labels to describe as
+    `inv["object"]` holds them (-1 in unused slots).  A cell belongs to the lowest slot that names its label; cells in no slot are
+    skipped and their rows are not read.  Returns `sum_q` int64 [K, 512] (the sum over the slot's cells of the normalised row in
+    fixed point, truncated at 2^-30), `cells` int32 [K], `embedding` float32 [K, 512] (the unit mean direction; zeros for a slot
+    without cells) and `coherence` float32 [K] (the length of the mean of the unit rows: 1 when all cells point the same way).
+    Integer atomics only: the same bits on every call, whatever the order of the cells."""
+    if not isinstance(mem, torch.Tensor) or mem.dim() != 2 or mem.shape[1] != DESCRIBE_D or mem.dtype != torch.float32 or not mem.is_contiguous():
+        raise _lib.EodError(f"describe_pool: mem {_describe_what(mem)}: expected contiguous float32 [N, {DESCRIBE_D}]")
+    N = int(mem.shape[0])
+    if not 1 <= N <= DESCRIBE_N_MAX:
+        raise _lib.EodError(f"describe_pool: mem: N {N} outside 1..{DESCRIBE_N_MAX}")
+    if (not isinstance(object_labels, torch.Tensor) or tuple(object_labels.shape) != (N,) or object_labels.dtype != torch.int32
+            or not object_labels.is_contiguous() or object_labels.device != mem.device):
+        raise _lib.EodError(f"describe_pool: object_labels {_describe_what(object_labels)}: expected contiguous int32 [{N}] on the "
+                            "memory's device")
+    if (not isinstance(objects, torch.Tensor) or objects.dim() != 1 or objects.dtype != torch.int32 or not objects.is_contiguous()
+            or objects.device != mem.device):
+        raise _lib.EodError(f"describe_pool: objects {_describe_what(objects)}: expected contiguous int32 [K] on the memory's device")
+    K = int(objects.shape[0])
+    if not 1 <= K <= DESCRIBE_K_MAX:
+        raise _lib.EodError(f"describe_pool: objects: K {K} outside 1..{DESCRIBE_K_MAX}")
+    if mem.data_ptr() % 16 != 0:
+        raise _lib.EodError("describe_pool: mem is not 16-byte aligned")
+    if not mem.is_cuda:
+        raise _lib.EodError("describe_pool: mem on the host (no CPU fallback)")
+    dev = mem.device
+    sum_q = torch.empty((K, DESCRIBE_D), dtype=torch.int64, device=dev)
+    cells = torch.empty((K,), dtype=torch.int32, device=dev)
+    embedding = torch.empty((K, DESCRIBE_D), dtype=torch.float32, device=dev)
+    coherence = torch.empty((K,), dtype=torch.float32, device=dev)
+    check(_lib.load().eod_describe_pool(mem.data_ptr(), object_labels.data_ptr(), objects.data_ptr(), N, K, sum_q.data_ptr(),
+                                        cells.data_ptr(), embedding.data_ptr(), coherence.data_ptr(), _stream()), "eod_describe_pool")
+    return {"sum_q": sum_q, "cells": cells, "embedding": embedding, "coherence": coherence}
+
+
+def describe_classify(embedding: torch.Tensor, zs: torch.Tensor, topn: int = 5) -> dict:
+    """The classes of described objects in any vocabulary (eod_describe_classify): K x C work, no pass over the cells.  `embedding`
+    float32 [K, 512], 1 <= K <= 64: what `describe_pool` returned, now or earlier; `zs` float32 [512, C1] as the heads and
+    `semmap_query` take it (the last column is the background and never enters; 1 <= C1 - 1 <= 2047); 1 <= `topn` <= min(8, C1 - 1).
+    Returns `prob` float32 [K, C1 - 1] (the softmax of 50 * embedding @ zs over the classes), `top_cls` int32 and `top_prob` float32
+    [K, topn]: the row's entries by (prob descending, class ascending).  An all-zero embedding row is an empty slot: a prob row of
+    zeros, top_cls -1, top_prob 0.  The same bits on every call."""
+    if (not isinstance(embedding, torch.Tensor) or embedding.dim() != 2 or embedding.shape[1] != DESCRIBE_D
+            or embedding.dtype != torch.float32 or not embedding.is_contiguous()):
+        raise _lib.EodError(f"describe_classify: embedding {_describe_what(embedding)}: expected contiguous float32 [K, {DESCRIBE_D}]")
+    K = int(embedding.shape[0])
+    if not 1 <= K <= DESCRIBE_K_MAX:
+        raise _lib.EodError(f"describe_classify: embedding: K {K} outside 1..{DESCRIBE_K_MAX}")
+    if (not isinstance(zs, torch.Tensor) or zs.dim() != 2 or zs.shape[0] != DESCRIBE_D or zs.dtype != torch.float32
+            or not zs.is_contiguous() or zs.device != embedding.device):
+        raise _lib.EodError(f"describe_classify: zs {_describe_what(zs)}: expected contiguous float32 [{DESCRIBE_D}, C1] on the "
+                            "embedding's device")
+    C = int(zs.shape[1]) - 1
+    if not 1 <= C <= DESCRIBE_C_MAX:
+        raise _lib.EodError(f"describe_classify: zs: {C} classes beside the background column, outside 1..{DESCRIBE_C_MAX}")
+    if isinstance(topn, bool) or int(topn) != topn or not 1 <= int(topn) <= min(DESCRIBE_TOPN_MAX, C):
+        raise _lib.EodError(f"describe_classify: topn {topn} outside 1..{min(DESCRIBE_TOPN_MAX, C)}")
+    if embedding.data_ptr() % 16 != 0:
+        raise _lib.EodError("describe_classify: embedding is not 16-byte aligned")
+    if not embedding.is_cuda:
+        raise _lib.EodError("describe_classify: embedding on the host (no CPU fallback)")
+    dev, T = embedding.device, int(topn)
+    prob = torch.empty((K, C), dtype=torch.float32, device=dev)
+    top_cls = torch.empty((K, T), dtype=torch.int32, device=dev)
+    top_prob = torch.empty((K, T), dtype=torch.float32, device=dev)
+    check(_lib.load().eod_describe_classify(embedding.data_ptr(), zs.data_ptr(), K, C + 1, T, prob.data_ptr(), top_cls.data_ptr(),
+                                            top_prob.data_ptr(), _stream()), "eod_describe_classify")
+    return {"prob": prob, "top_cls": top_cls, "top_prob": top_prob}
