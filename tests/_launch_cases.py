@@ -1,5 +1,6 @@
 """CPU side of test_training_launches_gpu.py: the recorder of the non-convolution entry points and the references of ROIAlign written
 out in torch at a chosen precision (float64 = reference, float32 = yardstick).  Nothing here touches a GPU by itself."""
+import math
 from typing import Dict, List, Sequence, Tuple
 
 import torch
@@ -409,6 +410,26 @@ class RoiRef:
                 l, y0, y1, x0, x1, Ay, Ax, _ = roi
                 n[l][y0:y1, x0:x1] += torch.outer((Ay != 0).sum(0).double(), (Ax != 0).sum(0).double())
         return n
+
+
+ROI_HEAD = 2.0          # head-room over the first-order bounds of the ROIAlign comparisons
+
+
+def roi_forward_reference(boxes: torch.Tensor, S: int, shapes: Sequence[Tuple[int, int]], feats: Sequence[torch.Tensor]):
+    """ROIAlign of `boxes` over one image's pyramid in float64 -> (RoiRef, pooled [R,S,S,C], element-wise bound on an fp32 kernel's
+    error).  The bound is test_training_launches_gpu.py's `_roi_bound` per ROI: 8 U 2^ceil(log2 E) for the roundings of the sample
+    coordinates on a level of extent E plus n U for adding the n cells a bin touches, times the sum T of the magnitudes those cells
+    hold, times ROI_HEAD."""
+    rr = RoiRef(boxes, S, shapes, torch.float64)
+    ref, T = rr.forward(feats), rr.forward([f.abs() for f in feats], indicator=True)
+    R = boxes.shape[0]
+    n = torch.zeros((R, S, S, 1), dtype=torch.float64)
+    ext = torch.ones((R, 1, 1, 1), dtype=torch.float64)
+    for r, roi in enumerate(rr.rois):
+        if roi is not None:
+            n[r, :, :, 0] = torch.outer((roi[5] != 0).sum(1).double(), (roi[6] != 0).sum(1).double())
+            ext[r] = 2.0 ** math.ceil(math.log2(max(shapes[roi[0]])))
+    return rr, ref, ROI_HEAD * U * (8.0 * ext + n) * T
 
 
 def hostile_boxes(H: int, W: int, rows: int, seed: int) -> torch.Tensor:

@@ -36,13 +36,20 @@ its fused `zs_mem` re-score and `final_inv_stages` fusion (test_narrow_classifie
 (test_narrow_memory_scores, test_wide_memory_scores), `mask_predictor_sigmoid` (test_mask_predictor), `detector_postprocess`
 (test_detector_postprocess).
 
-NOT replayed here and not covered there either (recorded and printed only; the tests named hold them at TOY shapes, not at these --
-that gap stays open): `groupnorm_relu` inference form (test_kernels_gpu.py::test_groupnorm_statistics_ride_on_the_conv_slab_reduce),
-`roi_align` with `box_rows` / `refine` / `batch` (test_batch_abi_gpu.py::test_roi_align_over_the_images_of_a_batch,
-test_kernels_gpu.py::test_box_head_glue), `MemoryWriter` (test_memory_write_matches_oracle, _write_parity.py at full size on the
-frame's own masks), `unproject_grid_index` (test_unproject_grid_index_bit_exact), `semmap_labels`
-(test_semmap_labels_match_oracle).  Lock-step is recorded in its `launches` kind (modeling/lockstep.py); the `streams` kind
-(modeling/batched.py) is recorded once and asserted to make no call the single-scene episode has not made.
+NOT replayed here either (recorded and printed only), each held alone in a module of its own, against float64 with derived bounds or
+bit for bit, at the sizes where its loops and tiles end rather than at the recorded shapes:
+  * `roi_align` with `box_rows` / `refine` / `batch`: test_roi_forms_gpu.py (float64 `RoiRef`; the grid-stride loop's second trip
+    at S = 14, both channel trips, NaN / inf / clamped deltas, per-image counts, global index lists over a batch).
+  * `MemoryWriter`: test_memory_write_edges_gpu.py (a float64 restatement of the write on scenes without a threshold band: up to
+    128 unique instances, the LDS table's overflow, partial and empty blocks, batches, the 4-wave commit); _write_parity.py holds it
+    at full size on the frame's own masks.
+  * `unproject_grid_index`: test_kernels_gpu.py::test_unproject_grid_index_sizes_and_hostile_depth (bitwise oracle/projector.c past
+    the launch's 1 048 576-pixel cap, with non-finite and negative depth) beside test_unproject_grid_index_bit_exact.
+  * `semmap_labels`: test_semmap_query_gpu.py (float64, derived bounds).
+  * `groupnorm_relu` with `partial_ready=True` (the inference form): at 640 x 640 by the fused-statistics way of
+    test_training_launches_gpu.py::test_groupnorm_forward_and_backward_at_the_recorded_pyramids.
+Lock-step is recorded in its `launches` kind (modeling/lockstep.py); the `streams` kind (modeling/batched.py) is recorded once and
+asserted to make no call the single-scene episode has not made.
 """
 import os
 import sys

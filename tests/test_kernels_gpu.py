@@ -760,6 +760,76 @@ def test_unproject_grid_index_bit_exact(dev):
         assert np.array_equal(idx.cpu().numpy(), idx_ref), "grid-cell indices must be bit-exact"
 
 
+def _unproject_into(depth, T, intr, proj_shift, map_shift, cell, map_w, map_h, order, xyz, idx):
+    """`ops.unproject_grid_index` into the caller's buffers (the test's sentinel-filled ones with their guard rows)."""
+    import ctypes as C
+    from embodied_object_detection_amd import _lib, ops
+    H, W = depth.shape
+    T16 = (C.c_float * 16)(*np.asarray(T, dtype=np.float32).reshape(-1).tolist())
+    ps = (C.c_float * 3)(*np.asarray(proj_shift, dtype=np.float32).tolist())
+    ms = (C.c_float * 3)(*np.asarray(map_shift, dtype=np.float32).tolist())
+    fx, fy, cx, cy = [float(np.float32(v)) for v in intr]
+    _lib.check(_lib.load().eod_unproject_grid_index(depth.data_ptr(), H, W, T16, fx, fy, cx, cy, ps, ms, float(np.float32(cell)), map_w, map_h,
+                                                    order, None if xyz is None else xyz.data_ptr(), idx.data_ptr(), ops._stream()),
+               "eod_unproject_grid_index")
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (3, 85), (1032, 1024)])
+def test_unproject_grid_index_sizes_and_hostile_depth(dev, H, W):
+    """Bitwise against oracle/projector.c at the sizes where the launch changes shape -- one pixel, 255 pixels (one partial workgroup),
+    1 056 768 pixels (8192 more than the launch's 4096 workgroups x 256 threads: the kernel loop's second trip) -- with depth 0,
+    negative, 1e-30, 1e30, +inf and NaN among ordinary values (the last pixels of the image among them), a translation of 1e6, cells
+    of 0.05 and 1e-3, maps of 1 x 1, 250 x 250 and 512 x 512 in both orders.  World coordinates compare with NaN equal to NaN
+    (payloads differ between hosts), indices exactly; sentinel-filled outputs with guard rows, every launch twice, and
+    `want_xyz=False` gives the same index image."""
+    from embodied_object_detection_amd import ops
+    P = H * W
+    assert P <= 4096 * 256 or P - 4096 * 256 == 8192
+    rng = np.random.RandomState(11 + H)
+    depth = np.clip(3 + rng.randn(H, W) * 1.5, 0.1, 10).astype(np.float32)
+    specials = [0.0, -2.5, 1e-30, 1e30, np.inf, np.nan]
+    flat = depth.reshape(-1)
+    if P == 1:
+        depths = [np.full((1, 1), v, dtype=np.float32) for v in [2.0] + specials]
+    else:
+        for i, v in enumerate(specials):
+            flat[rng.choice(P, max(2, P // 64), replace=False)] = v
+            flat[P - 1 - 2 * i] = v                                       # the image's last pixels: the second trip at the large size
+        depths = [depth]
+    intr = OP.intrinsics_from_vfov(W, H, 67.5 * math.pi / 180) if H > 1 else (np.float32(1.3), np.float32(1.3), np.float32(0.5), np.float32(0.5))
+    far = OP.transform3d([1.0e6, 1.5, 1.0e6, 0.7, math.pi])
+    near = OP.transform3d([2.0, 1.5, 2.5, -0.4, 0.1])
+    # (transform, proj_shift, map_shift, cell, map_w, map_h, order)
+    setups = [(far, (0.1, 0.0, -0.2), (1.0e6 - 6.0, 0.0, 1.0e6 - 6.0), 0.05, 250, 250, 0),
+              (near, (0.1, 0.0, -0.2), (1.9, 0.0, 2.3), 1e-3, 512, 512, 1),
+              (near, (0.0, 0.0, 0.0), (-5.0, 0.0, -5.0), 0.05, 250, 250, 1),
+              (near, (0.1, 0.0, -0.2), (-5.0, 0.0, -5.0), 0.05, 1, 1, 0)]
+    if P > 4096 * 256:
+        setups = setups[:2]
+    for depth in depths:
+        d = torch.from_numpy(depth).to(dev)
+        for T, ps, ms, cell, mw, mh, order in setups:
+            tag = f"{H}x{W} depth[0,0] {depth[0, 0]} cell {cell} map {mw}x{mh} order {order}"
+            xyz_ref = OP.unproject_world(depth, T, *intr, proj_shift=ps)
+            idx_ref = OP.grid_index(xyz_ref, ms, cell, mw, mh, order)
+            assert idx_ref.min() >= 0 and idx_ref.max() < mw * mh
+            if P > 1 and mw > 1:
+                assert len(np.unique(idx_ref)) > 3, "the set-up spreads the image over the map"
+            runs = []
+            for rep in range(2):
+                xyz = torch.full((P + 1, 3), -777.0, dtype=torch.float32, device=dev)
+                idx = torch.full((P + 1,), -777, dtype=torch.int32, device=dev)
+                _unproject_into(d, T, intr, ps, ms, cell, mw, mh, order, xyz, idx)
+                runs.append((xyz.cpu(), idx.cpu()))
+            (xyz, idx), (xyz2, idx2) = runs
+            assert torch.equal(xyz.view(torch.int32), xyz2.view(torch.int32)) and torch.equal(idx, idx2), f"{tag}: the second launch gave other bits"
+            assert bool((xyz[P] == -777.0).all()) and int(idx[P]) == -777, f"{tag}: a guard row was written"
+            assert np.array_equal(xyz[:P].numpy().reshape(H, W, 3), xyz_ref, equal_nan=True), f"{tag}: world xyz differs from oracle/projector.c"
+            assert np.array_equal(idx[:P].numpy().reshape(H, W), idx_ref), f"{tag}: grid-cell indices differ from oracle/projector.c"
+            only = ops.unproject_grid_index(d, T, intr, ps, ms, cell, mw, mh, order)
+            assert torch.equal(only.cpu(), idx[:P].reshape(H, W)), f"{tag}: want_xyz=False gives another index image"
+
+
 def _pooled_rows(pooled_ref):
     """oracle's three [1,512,h,w] fp16 tensors -> one [h8*w8 + h16*w16 + h32*w32, 512] row list"""
     return torch.cat([nhwc(r.float()).reshape(-1, 512) for r in pooled_ref])

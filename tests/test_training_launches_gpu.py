@@ -43,7 +43,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if __name__ == "__main__":
     sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
 
-from _launch_cases import SENTINEL, U, Recorder, RoiRef, fragments_to_rows, hostile_boxes, roi_geometry    # noqa: E402
+from _launch_cases import (ROI_HEAD, SENTINEL, U, Recorder, RoiRef, fragments_to_rows, hostile_boxes, roi_forward_reference,    # noqa: E402
+                           roi_geometry)
 
 pytestmark = pytest.mark.gpu
 
@@ -247,9 +248,6 @@ def test_recording_holds_every_family(recorded, config):
 # ------------------------------------------------------------------------------------------------
 # 2. ROIAlign
 # ------------------------------------------------------------------------------------------------
-ROI_HEAD = 2.0          # head-room over the first-order bound below
-
-
 def _roi_bound(T: torch.Tensor, reach: torch.Tensor, extent: int) -> torch.Tensor:
     """First-order bound on the fp32 error of one ROIAlign sum, element-wise.  A sample coordinate is built from a few fp32 roundings
     at the magnitude of the level's extent E (ulp/2 <= U * 2^ceil(log2 E)), so every tap weight is off by at most ~4 of those, an
@@ -334,17 +332,8 @@ def _roi_forward_check(tag: str, dev, shapes, C: int, boxes: torch.Tensor, S: in
     fd = [f.to(dev) for f in feats]
     ops.roi_align(fd[0], fd[1], fd[2], shapes[0][0], shapes[0][1], C, boxes.to(dev), cnt, R_cap, S, out=out[:R_cap])
     torch.cuda.synchronize()
-    rr = RoiRef(boxes[:R], S, shapes, torch.float64)
-    ref, T = rr.forward(feats), rr.forward([f.abs() for f in feats], indicator=True)
+    rr, ref, bound = roi_forward_reference(boxes[:R], S, shapes, feats)      # ROI_HEAD * U * (8 extent + cells a bin touches) * T
     y32 = RoiRef(boxes[:R], S, shapes, torch.float32).forward(feats)
-    # per ROI: the cells a bin touches (at most (2 g + 1)^2 of its level), the level's extent
-    n = torch.zeros((R, S, S, 1), dtype=torch.float64)
-    ext = torch.ones((R, 1, 1, 1), dtype=torch.float64)
-    for r, roi in enumerate(rr.rois):
-        if roi is not None:
-            n[r, :, :, 0] = torch.outer((roi[5] != 0).sum(1).double(), (roi[6] != 0).sum(1).double())
-            ext[r] = 2.0 ** math.ceil(math.log2(max(shapes[roi[0]])))
-    bound = ROI_HEAD * U * (8.0 * ext + n) * T
     got = out[:R].cpu()
     err, e32 = (got.double() - ref).abs(), (y32.double() - ref).abs()
     ratio = err / bound.clamp(min=1e-300)
