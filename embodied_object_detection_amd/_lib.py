@@ -1,6 +1,6 @@
 """ctypes binding of libeod_hip.so (C ABI declared in include/eod_hip.h; the frame-side map queries in include/eod_place.h, the
 map regions in include/eod_regions.h, the map inventory in include/eod_inventory.h, the object descriptions in
-include/eod_describe.h).
+include/eod_describe.h, the object relations in include/eod_relations.h).
 
 Fails loudly: there is no CPU fallback.  If the shared library is missing or a call returns a negative
 EOD_ERR_* code, an exception is raised.
@@ -262,6 +262,11 @@ DESCRIBE_SIGNATURES = {
     "eod_describe_classify": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p] * 4),
 }
 
+# name -> (restype, argtypes); every symbol include/eod_relations.h declares (pairwise relations of map objects within a radius)
+RELATIONS_SIGNATURES = {
+    "eod_map_relations": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 6 + [C.c_void_p] * 12),
+}
+
 _lib = None
 
 
@@ -276,7 +281,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES, **REGIONS_SIGNATURES, **INVENTORY_SIGNATURES,
-                              **DESCRIBE_SIGNATURES}.items():
+                              **DESCRIBE_SIGNATURES, **RELATIONS_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

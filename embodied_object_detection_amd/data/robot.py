@@ -107,6 +107,13 @@ class RobotFrontEnd:
             mean = np.where(a[..., None] > 0, s / a[..., None], np.nan)
         return np.stack([mean[..., 0] * self.res + float(self.map_shift[0]), mean[..., 1] * self.res + float(self.map_shift[2])], axis=-1)
 
+    def relation_metres(self, d2) -> np.ndarray:
+        """The squared cell distances of `relations` (`min_d2`, `nearest_d2`, `from_d2`) in metres: sqrt(d2) * res as float64 in the
+        shape of `d2`; inf for INT_MAX (no pair within reach, an empty slot, no `from_cell`).  The point to drive to is
+        `cell_centers(rel["from_closest"])`."""
+        d = np.asarray(d2.cpu() if torch.is_tensor(d2) else d2, dtype=np.int64)
+        return np.where(d == 2 ** 31 - 1, np.inf, np.sqrt(d.astype(np.float64)) * self.res)
+
     def exclude_cell(self, pose_xyt: Sequence[float]) -> int:
         """The robot's own cell as the memory's index `x * map_h + y`: the `exclude_cell` of `place`."""
         x, y = self.robot_cell(pose_xyt)

@@ -108,6 +108,12 @@ class EmbodiedPredictor:
             classifier = resolve_vocabulary(vocabulary)
         return self.model.describe(objects, object_labels, classifier=classifier, topn=topn, embedding=embedding)
 
+    def relations(self, objects, object_labels, map_shape=None, radius: int = 2, from_cell: Optional[int] = None, topn: int = 4) -> Dict:
+        """How the map objects stand to each other and to one cell: the dict of `CustomRCNNRecurrent.relations` (`min_d2`, `closest`,
+        `near_cells`, `edges`, `cells`, `nearest`, `from_d2`, `from_closest`, ...) for the objects of an `inventory` on the grid
+        `map_shape` = (rows, cols).  The model, its heads and the memory are neither read nor changed."""
+        return self.model.relations(objects, object_labels, map_shape=map_shape, radius=radius, from_cell=from_cell, topn=topn)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

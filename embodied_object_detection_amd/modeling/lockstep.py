@@ -42,7 +42,7 @@ import torch
 
 from .. import _lib, ops
 from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _describe, _det_stream, _instances, _map_inventory, _map_regions, _place,
-                        _result_sets, _sched_streams, _semmap_locate, _semmap_query, _ticket)
+                        _relations, _result_sets, _sched_streams, _semmap_locate, _semmap_query, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -240,6 +240,19 @@ class LockstepScenes:
         if self.implicit_memory is None:
             raise _lib.EodError("semantic_map: no memory yet (no frame has run)")
         return _describe(self.model, self.implicit_memory[int(scene)], objects, object_labels, classifier, num_classes, topn, embedding)
+
+    def relations(self, objects, object_labels, map_shape=None, radius: int = 2, from_cell: Optional[int] = None, topn: int = 4):
+        """`CustomRCNNRecurrent.relations`; with the `[B, K]` objects and `[B, N]` object_labels of `inventory(None, ...)` the op
+        runs once per scene and every entry of the dict gains a leading [B].  Nothing of the batch model changes."""
+        if isinstance(object_labels, torch.Tensor) and object_labels.dim() == 2:
+            objects = torch.as_tensor(objects, dtype=torch.int32, device=object_labels.device)
+            if objects.dim() != 2 or objects.shape[0] != object_labels.shape[0]:
+                raise _lib.EodError(f"relations: objects {tuple(objects.shape)}: expected [B, K] beside object_labels "
+                                    f"{tuple(object_labels.shape)}")
+            per = [_relations(objects[b].contiguous(), object_labels[b].contiguous(), map_shape, radius, from_cell, topn)
+                   for b in range(int(object_labels.shape[0]))]
+            return {k: torch.stack([p[k] for p in per]) for k in per[0]}
+        return _relations(objects, object_labels, map_shape, radius, from_cell, topn)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

@@ -160,6 +160,19 @@ def _describe(model, mem, objects, object_labels, classifier, num_classes, topn,
     return out
 
 
+def _relations(objects, object_labels, map_shape, radius, from_cell, topn):
+    """`relations` on one label map: `ops.map_relations` on the grid `map_shape`.  Reads no model and no memory."""
+    if map_shape is None:
+        raise _lib.EodError("relations: map_shape (rows, cols) is required: the distances are those of the grid")
+    rows, cols = int(map_shape[0]), int(map_shape[1])
+    if not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or rows < 1 or cols < 1 or rows * cols != object_labels.shape[0]:
+        raise _lib.EodError(f"relations: map_shape {tuple(map_shape)} does not hold the {tuple(getattr(object_labels, 'shape', ()))} "
+                            "cells of object_labels")
+    if not isinstance(objects, torch.Tensor):
+        objects = torch.as_tensor(objects, dtype=torch.int32, device=object_labels.device)
+    return ops.map_relations(object_labels, objects, cols, radius=radius, from_cell=-1 if from_cell is None else from_cell, topn=topn)
+
+
 def place_rects(boxes: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """int32 [K, 4] half-open rects outside which the pasted masks of `boxes` (float [K, 4], x0 y0 x1 y1) are zero: the box grown
     by (w / 14 + 1, h / 14 + 1) pixels, floor and ceil.  A pasted mask is exactly zero more than one mask pixel (box side / 28)
@@ -923,6 +936,17 @@ class CustomRCNNRecurrent:
         pass over the cells; `objects` and `object_labels` are then not read.  Embeddings of two maps compare as
         `a["embedding"] @ b["embedding"].T`.  Changes nothing in the model."""
         return _describe(self, self.implicit_memory, objects, object_labels, classifier, num_classes, topn, embedding)
+
+    def relations(self, objects, object_labels, map_shape=None, radius: int = 2, from_cell: Optional[int] = None, topn: int = 4) -> dict:
+        """How the map objects stand to each other and to one cell: the dict of `ops.map_relations` for `objects` int32 [K] (a
+        sequence will do) and `object_labels` int32 [N] (`inv["object"]` and `inv["object_labels"]` of `inventory`, or a row of
+        `region_labels` of `regions` with its `region` row) on the grid `map_shape` = (rows, cols), which is required.  For every
+        ordered pair of objects with cells within `radius` of each other (a disc on the grid): `min_d2`, `closest` (the cell of a
+        nearest to b), `near_cells` (`near_cells[a, b] == cells[a]`: a lies on / inside the reach of b), `edges` (the shared
+        border), `pair_key`; per object `cells`, its `topn` `nearest` objects with `nearest_d2`, and from `from_cell` (the robot's
+        cell, `RobotFrontEnd.exclude_cell(pose)`; None: not asked) `from_d2`, `from_closest` (the cell to drive to) and `from_key`,
+        whatever the radius.  Distances in metres: `RobotFrontEnd.relation_metres`.  Reads neither the model nor the memory."""
+        return _relations(objects, object_labels, map_shape, radius, from_cell, topn)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

@@ -1757,3 +1757,68 @@ def describe_classify(embedding: torch.Tensor, zs: torch.Tensor, topn: int = 5) 
     check(_lib.load().eod_describe_classify(embedding.data_ptr(), zs.data_ptr(), K, C + 1, T, prob.data_ptr(), top_cls.data_ptr(),
                                             top_prob.data_ptr(), _stream()), "eod_describe_classify")
     return {"prob": prob, "top_cls": top_cls, "top_prob": top_prob}
+
+
+RELATIONS_K_MAX, RELATIONS_N_MAX, RELATIONS_DIM_MAX, RELATIONS_RADIUS_MAX, RELATIONS_TOPN_MAX = 64, 1 << 22, 32767, 16, 8
+RELATIONS_TILE_ROWS, RELATIONS_TILE_COLS = 32, 32        # the cells one workgroup owns (RL_TR, RL_TC of csrc/relations.hip)
+
+
+def map_relations(object_labels: torch.Tensor, objects: torch.Tensor, cols: int, radius: int = 2, from_cell: int = -1,
+                  topn: int = 4) -> dict:
+    """How the objects of a label map stand to each other and to one cell (eod_map_relations; the semantics are those of
+    include/eod_relations.h).  `object_labels` int32 [N], cell i = r * cols + c: the `object_labels` of `map_inventory`, a row of the
+    `region_labels` of `map_regions` or any other label map; `objects` int32 [K], 1 <= K <= 64, as `inv["object"]` holds them (-1
+    in unused slots; a cell belongs to the lowest slot that names its label).  Two cells are within reach when the squared
+    distance of their rows and columns is at most `radius` ** 2 (1 <= `radius` <= 16).  Returns, for every ordered pair of slots
+    a != b over the cell pairs within reach: `pair_key` int64 [K, K] (the bits of the unsigned minimum of (d2 << 32) | cell of a;
+    -1 where no pair is within reach), `min_d2` int32 [K, K] (INT_MAX where none), `closest` int32 [K, K] (the cell of a nearest to
+    b, the lowest on ties; -1), `near_cells` int32 [K, K] (cells of a with a cell of b within reach), `edges` int32 [K, K] (cell
+    pairs one step apart: the shared border); per slot `cells` int32 [K], `nearest` and `nearest_d2` int32 [K, topn] (the slots
+    within reach by (min_d2, slot) ascending, padded with -1 and INT_MAX; 1 <= `topn` <= 8), and for `from_cell` in 0..N-1, over
+    all cells of a slot whatever the radius, `from_key` int64 [K], `from_d2` and `from_closest` int32 [K] (INT_MAX and -1 for an
+    empty slot and for `from_cell` -1).  Integer atomics only: the same bits on every call."""
+    if (not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or object_labels.dtype != torch.int32
+            or not object_labels.is_contiguous()):
+        raise _lib.EodError(f"map_relations: object_labels {_describe_what(object_labels)}: expected contiguous int32 [N]")
+    N = int(object_labels.shape[0])
+    if not 1 <= N <= RELATIONS_N_MAX:
+        raise _lib.EodError(f"map_relations: object_labels: N {N} outside 1..{RELATIONS_N_MAX}")
+    if (not isinstance(objects, torch.Tensor) or objects.dim() != 1 or objects.dtype != torch.int32 or not objects.is_contiguous()
+            or objects.device != object_labels.device):
+        raise _lib.EodError(f"map_relations: objects {_describe_what(objects)}: expected contiguous int32 [K] on the labels' device")
+    K = int(objects.shape[0])
+    if not 1 <= K <= RELATIONS_K_MAX:
+        raise _lib.EodError(f"map_relations: objects: K {K} outside 1..{RELATIONS_K_MAX}")
+
+    def whole(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if not whole(cols) or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_relations: cols {cols} does not divide the {N} cells")
+    if int(cols) > RELATIONS_DIM_MAX or N // int(cols) > RELATIONS_DIM_MAX:
+        raise _lib.EodError(f"map_relations: cols {cols}: {N // int(cols)} rows x {cols} columns, more than {RELATIONS_DIM_MAX} one way")
+    if not whole(radius) or not 1 <= int(radius) <= RELATIONS_RADIUS_MAX:
+        raise _lib.EodError(f"map_relations: radius {radius} outside 1..{RELATIONS_RADIUS_MAX}")
+    if not whole(from_cell) or not -1 <= int(from_cell) < N:
+        raise _lib.EodError(f"map_relations: from_cell {from_cell} outside -1..{N - 1}")
+    if not whole(topn) or not 1 <= int(topn) <= RELATIONS_TOPN_MAX:
+        raise _lib.EodError(f"map_relations: topn {topn} outside 1..{RELATIONS_TOPN_MAX}")
+    if not object_labels.is_cuda:
+        raise _lib.EodError("map_relations: object_labels on the host (no CPU fallback)")
+    dev, T = object_labels.device, int(topn)
+    keys = torch.empty((K * K + K,), dtype=torch.int64, device=dev)               # pair_key, from_key
+    out = torch.empty((4 * K * K + 2 * K * T + 3 * K,), dtype=torch.int32, device=dev)
+    KK, KT = K * K, K * T
+    part = {}
+    at = 0
+    for name, n, shape in (("min_d2", KK, (K, K)), ("closest", KK, (K, K)), ("near_cells", KK, (K, K)), ("edges", KK, (K, K)),
+                           ("cells", K, (K,)), ("nearest", KT, (K, T)), ("nearest_d2", KT, (K, T)), ("from_d2", K, (K,)),
+                           ("from_closest", K, (K,))):
+        part[name] = out[at:at + n].view(shape)
+        at += n
+    pair_key, from_key = keys[:KK].view(K, K), keys[KK:]
+    check(_lib.load().eod_map_relations(object_labels.data_ptr(), objects.data_ptr(), N, K, int(cols), int(radius), int(from_cell), T,
+                                        pair_key.data_ptr(), part["min_d2"].data_ptr(), part["closest"].data_ptr(),
+                                        part["near_cells"].data_ptr(), part["edges"].data_ptr(), part["cells"].data_ptr(),
+                                        part["nearest"].data_ptr(), part["nearest_d2"].data_ptr(), from_key.data_ptr(),
+                                        part["from_d2"].data_ptr(), part["from_closest"].data_ptr(), _stream()), "eod_map_relations")
+    return {"pair_key": pair_key, **part, "from_key": from_key}
