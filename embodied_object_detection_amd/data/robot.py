@@ -114,6 +114,13 @@ class RobotFrontEnd:
         d = np.asarray(d2.cpu() if torch.is_tensor(d2) else d2, dtype=np.int64)
         return np.where(d == 2 ** 31 - 1, np.inf, np.sqrt(d.astype(np.float64)) * self.res)
 
+    def route_metres(self, cost) -> np.ndarray:
+        """The costs of `route` (`dist`, `goal_cost`) in metres: cost / 5 * res as float64 in the shape of `cost` (a move along a
+        row or column costs 5, a diagonal one 7); inf for INT_MAX (blocked, unreached, no way to the object).  The waypoints are
+        `cell_centers(route["path"][k])`, NaN behind the path's end."""
+        d = np.asarray(cost.cpu() if torch.is_tensor(cost) else cost, dtype=np.int64)
+        return np.where(d == 2 ** 31 - 1, np.inf, d.astype(np.float64) / 5.0 * self.res)
+
     def exclude_cell(self, pose_xyt: Sequence[float]) -> int:
         """The robot's own cell as the memory's index `x * map_h + y`: the `exclude_cell` of `place`."""
         x, y = self.robot_cell(pose_xyt)

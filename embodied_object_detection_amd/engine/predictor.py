@@ -114,6 +114,14 @@ class EmbodiedPredictor:
         `map_shape` = (rows, cols).  The model, its heads and the memory are neither read nor changed."""
         return self.model.relations(objects, object_labels, map_shape=map_shape, radius=radius, from_cell=from_cell, topn=topn)
 
+    def route(self, objects, object_labels, map_shape=None, from_cell: Optional[int] = None, passable=None, path_max: int = 256,
+              sweeps: Optional[int] = None) -> Dict:
+        """How to reach the map objects: the dict of `CustomRCNNRecurrent.route` (`dist`, `parent`, `goal_cost`, `goal_cell`, `path`,
+        `path_cells`, `cells`, `counts`, ...) for the objects of an `inventory` on the grid `map_shape` = (rows, cols), from
+        `from_cell`.  The model, its heads and the memory are neither read nor changed."""
+        return self.model.route(objects, object_labels, map_shape=map_shape, from_cell=from_cell, passable=passable, path_max=path_max,
+                                sweeps=sweeps)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

@@ -42,7 +42,7 @@ import torch
 
 from .. import _lib, ops
 from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _describe, _det_stream, _instances, _map_inventory, _map_regions, _place,
-                        _relations, _result_sets, _sched_streams, _semmap_locate, _semmap_query, _ticket)
+                        _relations, _result_sets, _route, _sched_streams, _semmap_locate, _semmap_query, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -253,6 +253,27 @@ class LockstepScenes:
                    for b in range(int(object_labels.shape[0]))]
             return {k: torch.stack([p[k] for p in per]) for k in per[0]}
         return _relations(objects, object_labels, map_shape, radius, from_cell, topn)
+
+    def route(self, objects, object_labels, map_shape=None, from_cell=None, passable=None, path_max: int = 256,
+              sweeps: Optional[int] = None):
+        """`CustomRCNNRecurrent.route`; with the `[B, K]` objects and `[B, N]` object_labels of `inventory(None, ...)` the op runs
+        once per scene, `from_cell` is one int or a sequence of B, and every entry of the dict gains a leading [B].  Nothing of
+        the batch model changes."""
+        if isinstance(object_labels, torch.Tensor) and object_labels.dim() == 2:
+            B = int(object_labels.shape[0])
+            objects = torch.as_tensor(objects, dtype=torch.int32, device=object_labels.device)
+            if objects.dim() != 2 or objects.shape[0] != B:
+                raise _lib.EodError(f"route: objects {tuple(objects.shape)}: expected [B, K] beside object_labels "
+                                    f"{tuple(object_labels.shape)}")
+            if isinstance(from_cell, torch.Tensor):
+                from_cell = from_cell.tolist()
+            cells = list(from_cell) if hasattr(from_cell, "__len__") else [from_cell] * B
+            if len(cells) != B:
+                raise _lib.EodError(f"route: from_cell: {len(cells)} cells for {B} scenes")
+            per = [_route(objects[b].contiguous(), object_labels[b].contiguous(), map_shape, None if cells[b] is None else int(cells[b]),
+                          passable, path_max, sweeps) for b in range(B)]
+            return {k: torch.stack([p[k] for p in per]) for k in per[0]}
+        return _route(objects, object_labels, map_shape, from_cell, passable, path_max, sweeps)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

@@ -173,6 +173,40 @@ def _relations(objects, object_labels, map_shape, radius, from_cell, topn):
     return ops.map_relations(object_labels, objects, cols, radius=radius, from_cell=-1 if from_cell is None else from_cell, topn=topn)
 
 
+def _route(objects, object_labels, map_shape, from_cell, passable=None, path_max=256, sweeps=None):
+    """`route` on one label map: `ops.map_route` on the grid `map_shape`, resumed while the sweeps run out (each resumed call with
+    twice the sweeps of the last, `ops.ROUTE_RESUMES` of them at the most).  Reads no model and no memory."""
+    if map_shape is None:
+        raise _lib.EodError("route: map_shape (rows, cols) is required: the moves are those of the grid")
+    rows, cols = int(map_shape[0]), int(map_shape[1])
+    if not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or rows < 1 or cols < 1 or rows * cols != object_labels.shape[0]:
+        raise _lib.EodError(f"route: map_shape {tuple(map_shape)} does not hold the {tuple(getattr(object_labels, 'shape', ()))} "
+                            "cells of object_labels")
+    if from_cell is None:
+        raise _lib.EodError("route: from_cell is required: the cell the paths start from (RobotFrontEnd.exclude_cell(pose))")
+    if not isinstance(objects, torch.Tensor):
+        objects = torch.as_tensor(objects, dtype=torch.int32, device=object_labels.device)
+    if passable is not None and not isinstance(passable, torch.Tensor):
+        passable = torch.as_tensor(passable, dtype=torch.int32, device=object_labels.device).reshape(-1)
+    res = ops.map_route(object_labels, objects, cols, from_cell, passable=passable, path_max=path_max, sweeps=sweeps)
+    n = ops.map_route_sweeps(rows, cols) if sweeps is None else int(sweeps)
+    total = n
+    for _ in range(ops.ROUTE_RESUMES):
+        status = int(res["status"][0])                               # the results are handed over here
+        if status != 1:
+            break
+        n = min(2 * n, ops.ROUTE_SWEEPS_MAX)
+        total += n
+        res = ops.map_route(object_labels, objects, cols, from_cell, passable=passable, path_max=path_max, sweeps=n, resume=res)
+    status = int(res["status"][0])
+    if status & 2:
+        raise _lib.EodError(f"route: a bounded loop of eod_map_route reached its bound (status {status}); the result is void")
+    if status != 0:
+        raise _lib.EodError(f"route: the distances had not settled after {total} sweeps in {ops.ROUTE_RESUMES + 1} calls (status "
+                            f"{status}); the result is void")
+    return res
+
+
 def place_rects(boxes: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """int32 [K, 4] half-open rects outside which the pasted masks of `boxes` (float [K, 4], x0 y0 x1 y1) are zero: the box grown
     by (w / 14 + 1, h / 14 + 1) pixels, floor and ceil.  A pasted mask is exactly zero more than one mask pixel (box side / 28)
@@ -947,6 +981,22 @@ class CustomRCNNRecurrent:
         cell, `RobotFrontEnd.exclude_cell(pose)`; None: not asked) `from_d2`, `from_closest` (the cell to drive to) and `from_key`,
         whatever the radius.  Distances in metres: `RobotFrontEnd.relation_metres`.  Reads neither the model nor the memory."""
         return _relations(objects, object_labels, map_shape, radius, from_cell, topn)
+
+    def route(self, objects, object_labels, map_shape=None, from_cell: Optional[int] = None, passable=None, path_max: int = 256,
+              sweeps: Optional[int] = None) -> dict:
+        """How to reach the map objects: the dict of `ops.map_route` for `objects` int32 [K] (a sequence will do) and
+        `object_labels` int32 [N] (`inv["object"]` and `inv["object_labels"]` of `inventory`) on the grid `map_shape` =
+        (rows, cols), from `from_cell` (the robot's cell, `RobotFrontEnd.exclude_cell(pose)`); both are required.  Every labelled
+        cell blocks unless its label is one of `passable`; unlabelled cells are free, also where the memory knows nothing: the
+        optimistic planner's assumption.  Moves go to the 8 neighbours and never between two blocked cells that touch at a corner;
+        they cost 5 along a row or column and 7 diagonally.  `dist` and `parent` [N] are the cost from `from_cell` and the cell a
+        cheapest path enters from; per object `goal_cell` is the free cell beside it to stop on, `goal_cost` the cost to it
+        (INT_MAX: no way there), `path` [K, path_max] the cells from `goal_cell` back to `from_cell` (-1 behind them), `path_cells`
+        their number, `cells` the object's cells; `counts` the free and the reached cells.  Metres: `RobotFrontEnd.route_metres`
+        and `cell_centers(route["path"][k])`.  `sweeps` (None: `ops.map_route_sweeps`) is the number of sweep launches of one call;
+        the status is read here, a call whose sweeps ran out is resumed up to `ops.ROUTE_RESUMES` times, and `EodError` is raised
+        if the distances have not settled by then.  Reads neither the model nor the memory."""
+        return _route(objects, object_labels, map_shape, from_cell, passable, path_max, sweeps)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

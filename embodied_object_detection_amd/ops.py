@@ -1822,3 +1822,118 @@ def map_relations(object_labels: torch.Tensor, objects: torch.Tensor, cols: int,
                                         part["nearest"].data_ptr(), part["nearest_d2"].data_ptr(), from_key.data_ptr(),
                                         part["from_d2"].data_ptr(), part["from_closest"].data_ptr(), _stream()), "eod_map_relations")
     return {"pair_key": pair_key, **part, "from_key": from_key}
+
+
+ROUTE_K_MAX, ROUTE_P_MAX, ROUTE_N_MAX, ROUTE_DIM_MAX, ROUTE_PATH_MAX, ROUTE_SWEEPS_MAX = 64, 64, 1 << 22, 32767, 1024, 1024
+ROUTE_COST_ORTH, ROUTE_COST_DIAG = 5, 7                  # a move along a row or column, a diagonal move (sqrt(2) taken as 7 / 5)
+ROUTE_TILE_ROWS, ROUTE_TILE_COLS = 32, 32                # the cells one workgroup of a sweep owns (RT_TR, RT_TC of csrc/route.hip)
+ROUTE_RESUMES = 8                                        # resumed calls of the model-level `route`, each with twice the sweeps of the last
+
+
+def map_route_sweeps(rows: int, cols: int) -> int:
+    """The default `sweeps` of `map_route`: four times the tile count of the longer side plus four, at most 1024.  A map that is
+    reached without detours settles in about one sweep per tile across plus one, so this leaves room for a path that
+    winds across the map about four times; a sweep launch in which no tile runs costs about as much as an empty launch."""
+    ty, tx = -(-int(rows) // ROUTE_TILE_ROWS), -(-int(cols) // ROUTE_TILE_COLS)
+    return min(ROUTE_SWEEPS_MAX, 4 * max(ty, tx) + 4)
+
+
+def map_route_workspace(N: int, cols: int) -> int:
+    """int32 words of a `map_route` workspace (eod_map_route_workspace_bytes / 4): three flags per tile and one byte per cell."""
+    need = int(_lib.load().eod_map_route_workspace_bytes(int(N), int(cols)))
+    if need == 0:
+        raise _lib.EodError(f"map_route_workspace: N {N}, cols {cols}")
+    return need // 4
+
+
+def map_route(object_labels: torch.Tensor, objects: torch.Tensor, cols: int, from_cell: int, passable=None, path_max: int = 256,
+              sweeps: Optional[int] = None, resume=None, workspace: Optional[torch.Tensor] = None) -> dict:
+    """Shortest paths round the objects of a label map, from `from_cell` to every cell and to each of up to 64 objects
+    (eod_map_route; the semantics are those of include/eod_route.h).  `object_labels` int32 [N], cell i = r * cols + c: the
+    `object_labels` of `map_inventory` or any other label map; `objects` int32 [K], 1 <= K <= 64, as `inv["object"]` holds them (-1
+    in unused slots; a cell belongs to the lowest slot that names its label).  A cell is free when its label is negative, when its
+    label is one of `passable` (None, or int32 [P], P <= 64, or a sequence) or when it is `from_cell`; unlabelled cells count as
+    free, the optimistic planner's assumption about space the memory does not know.  A move goes to one of the 8 neighbours on the
+    grid, the target free and, for a diagonal move, both cells it passes between free too; it costs 5 along a row or column and 7
+    diagonally.  Returns `dist` int32 [N] (INT_MAX: blocked or unreached), `parent` int32 [N] (the lowest cell a cheapest path
+    enters from; -1), per slot `goal_key` int64 [K] (the bits of the unsigned minimum of (dist << 32) | cell over the reached free
+    cells at most one row and one column from a cell of the slot; -1 where none), `goal_cost` (INT_MAX), `goal_cell` (-1), `cells`
+    int32 [K], `path` int32 [K, path_max] (from `goal_cell` along `parent` to `from_cell`, then -1), `path_cells` int32 [K],
+    `counts` int32 [2] (free cells, reached free cells) and `status` int32 [2]: status[0] bit 0: the `sweeps` (1..1024; None:
+    `map_route_sweeps`) ran out before the distances had settled, bit 1: a bounded loop reached its bound; with a nonzero status
+    every output but `dist` is void.  `status` is not read here, so nothing synchronises.  `resume`: the dict of an earlier call on
+    the same `object_labels`, `passable` and `from_cell`, or its `dist`: the sweeps continue from that `dist`, which is updated in
+    place and returned.  `workspace`: int32, 8-byte aligned, at least `map_route_workspace(N, cols)` words, any contents.  Integer
+    min and add only: at status 0 the same bits on every call, whatever the sweeps and resumed calls that led there."""
+    if (not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or object_labels.dtype != torch.int32
+            or not object_labels.is_contiguous()):
+        raise _lib.EodError(f"map_route: object_labels {_describe_what(object_labels)}: expected contiguous int32 [N]")
+    N = int(object_labels.shape[0])
+    if not 1 <= N <= ROUTE_N_MAX:
+        raise _lib.EodError(f"map_route: object_labels: N {N} outside 1..{ROUTE_N_MAX}")
+    dev = object_labels.device
+    if (not isinstance(objects, torch.Tensor) or objects.dim() != 1 or objects.dtype != torch.int32 or not objects.is_contiguous()
+            or objects.device != dev):
+        raise _lib.EodError(f"map_route: objects {_describe_what(objects)}: expected contiguous int32 [K] on the labels' device")
+    K = int(objects.shape[0])
+    if not 1 <= K <= ROUTE_K_MAX:
+        raise _lib.EodError(f"map_route: objects: K {K} outside 1..{ROUTE_K_MAX}")
+
+    def whole(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if not whole(cols) or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_route: cols {cols} does not divide the {N} cells")
+    if int(cols) > ROUTE_DIM_MAX or N // int(cols) > ROUTE_DIM_MAX:
+        raise _lib.EodError(f"map_route: cols {cols}: {N // int(cols)} rows x {cols} columns, more than {ROUTE_DIM_MAX} one way")
+    if not whole(from_cell) or not 0 <= int(from_cell) < N:
+        raise _lib.EodError(f"map_route: from_cell {from_cell} outside 0..{N - 1}")
+    if passable is not None and not isinstance(passable, torch.Tensor):
+        try:
+            passable = torch.as_tensor(np.asarray(list(passable), dtype=np.int64).astype(np.int32).reshape(-1), device=dev)
+        except (TypeError, ValueError, OverflowError):
+            raise _lib.EodError(f"map_route: passable {type(passable).__name__}: expected None, int32 [P] or a sequence of labels") from None
+    if passable is not None and (passable.dim() != 1 or passable.dtype != torch.int32 or not passable.is_contiguous()
+                                 or passable.device != dev or passable.shape[0] > ROUTE_P_MAX):
+        raise _lib.EodError(f"map_route: passable {_describe_what(passable)}: expected contiguous int32 [P], P <= {ROUTE_P_MAX}, on the "
+                            "labels' device")
+    P = 0 if passable is None else int(passable.shape[0])
+    if not whole(path_max) or not 1 <= int(path_max) <= ROUTE_PATH_MAX:
+        raise _lib.EodError(f"map_route: path_max {path_max} outside 1..{ROUTE_PATH_MAX}")
+    if sweeps is None:
+        sweeps = map_route_sweeps(N // int(cols), int(cols))
+    if not whole(sweeps) or not 1 <= int(sweeps) <= ROUTE_SWEEPS_MAX:
+        raise _lib.EodError(f"map_route: sweeps {sweeps} outside 1..{ROUTE_SWEEPS_MAX}")
+    dist = resume["dist"] if isinstance(resume, dict) and "dist" in resume else resume
+    if dist is not None and (not isinstance(dist, torch.Tensor) or dist.dtype != torch.int32 or tuple(dist.shape) != (N,)
+                             or not dist.is_contiguous() or dist.device != dev):
+        raise _lib.EodError(f"map_route: resume {_describe_what(dist)}: expected the dict of an earlier call or its dist, contiguous "
+                            f"int32 [{N}] on the labels' device")
+    if not object_labels.is_cuda:
+        raise _lib.EodError("map_route: object_labels on the host (no CPU fallback)")
+    need = map_route_workspace(N, int(cols))
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev
+                                  or workspace.data_ptr() % 8 != 0):
+        raise _lib.EodError(f"map_route: workspace: expected {need} contiguous, 8-byte aligned int32 on the labels' device")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+    T = int(path_max)
+    cont = dist is not None
+    if not cont:
+        dist = torch.empty((N,), dtype=torch.int32, device=dev)
+    parent = torch.empty((N,), dtype=torch.int32, device=dev)
+    goal_key = torch.empty((K,), dtype=torch.int64, device=dev)
+    out = torch.empty((4 * K + K * T + 4,), dtype=torch.int32, device=dev)
+    part = {}
+    at = 0
+    for name, n, shape in (("goal_cost", K, (K,)), ("goal_cell", K, (K,)), ("cells", K, (K,)), ("path", K * T, (K, T)),
+                           ("path_cells", K, (K,)), ("counts", 2, (2,)), ("status", 2, (2,))):
+        part[name] = out[at:at + n].view(shape)
+        at += n
+    check(_lib.load().eod_map_route(object_labels.data_ptr(), objects.data_ptr(), _ptr(passable) if P else None, N, K, P, int(cols),
+                                    int(from_cell), T, int(sweeps), 1 if cont else 0, dist.data_ptr(), parent.data_ptr(),
+                                    goal_key.data_ptr(), part["goal_cost"].data_ptr(), part["goal_cell"].data_ptr(),
+                                    part["cells"].data_ptr(), part["path"].data_ptr(), part["path_cells"].data_ptr(),
+                                    part["counts"].data_ptr(), part["status"].data_ptr(), workspace.data_ptr(), workspace.numel() * 4,
+                                    _stream()), "eod_map_route")
+    return {"dist": dist, "parent": parent, "goal_key": goal_key, **part}
