@@ -1,6 +1,7 @@
 """ctypes binding of libeod_hip.so (C ABI declared in include/eod_hip.h; the frame-side map queries in include/eod_place.h, the
 map regions in include/eod_regions.h, the map inventory in include/eod_inventory.h, the object descriptions in
-include/eod_describe.h, the object relations in include/eod_relations.h, the routes in include/eod_route.h).
+include/eod_describe.h, the object relations in include/eod_relations.h, the routes in include/eod_route.h, the clearance map in
+include/eod_clearance.h).
 
 Fails loudly: there is no CPU fallback.  If the shared library is missing or a call returns a negative
 EOD_ERR_* code, an exception is raised.
@@ -273,6 +274,12 @@ ROUTE_SIGNATURES = {
     "eod_map_route": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/eod_clearance.h declares (exact distance to the nearest object, inflated map)
+CLEARANCE_SIGNATURES = {
+    "eod_map_clearance_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    "eod_map_clearance": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -287,7 +294,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES, **REGIONS_SIGNATURES, **INVENTORY_SIGNATURES,
-                              **DESCRIBE_SIGNATURES, **RELATIONS_SIGNATURES, **ROUTE_SIGNATURES}.items():
+                              **DESCRIBE_SIGNATURES, **RELATIONS_SIGNATURES, **ROUTE_SIGNATURES, **CLEARANCE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

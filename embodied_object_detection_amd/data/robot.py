@@ -121,6 +121,17 @@ class RobotFrontEnd:
         d = np.asarray(cost.cpu() if torch.is_tensor(cost) else cost, dtype=np.int64)
         return np.where(d == 2 ** 31 - 1, np.inf, d.astype(np.float64) / 5.0 * self.res)
 
+    def clearance_metres(self, d2) -> np.ndarray:
+        """The squared cell distances of `clearance` (`d2`, `widest_d2`) in metres: sqrt(d2) * res as float64 in the shape of `d2`;
+        inf for INT_MAX (the map has no blocked cell).  The place to stand is `cell_centers(clr["widest_cell"])`."""
+        d = np.asarray(d2.cpu() if torch.is_tensor(d2) else d2, dtype=np.int64)
+        return np.where(d == 2 ** 31 - 1, np.inf, np.sqrt(d.astype(np.float64)) * self.res)
+
+    def body_radius2(self, metres: float) -> int:
+        """The `radius2` of `clearance` and the `body_radius2` of `route` for a body of radius `metres`: the radius in cells,
+        squared and rounded down (1e-9 keeps a radius that is a whole number of cells from falling short by rounding)."""
+        return int(np.floor((float(metres) / self.res) ** 2 + 1e-9))
+
     def exclude_cell(self, pose_xyt: Sequence[float]) -> int:
         """The robot's own cell as the memory's index `x * map_h + y`: the `exclude_cell` of `place`."""
         x, y = self.robot_cell(pose_xyt)

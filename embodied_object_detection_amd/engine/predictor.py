@@ -115,12 +115,19 @@ class EmbodiedPredictor:
         return self.model.relations(objects, object_labels, map_shape=map_shape, radius=radius, from_cell=from_cell, topn=topn)
 
     def route(self, objects, object_labels, map_shape=None, from_cell: Optional[int] = None, passable=None, path_max: int = 256,
-              sweeps: Optional[int] = None) -> Dict:
+              sweeps: Optional[int] = None, body_radius2: Optional[int] = None) -> Dict:
         """How to reach the map objects: the dict of `CustomRCNNRecurrent.route` (`dist`, `parent`, `goal_cost`, `goal_cell`, `path`,
         `path_cells`, `cells`, `counts`, ...) for the objects of an `inventory` on the grid `map_shape` = (rows, cols), from
-        `from_cell`.  The model, its heads and the memory are neither read nor changed."""
+        `from_cell`; with `body_radius2` for a body of that squared radius in cells, on the inflated map (`clearance_d2` and
+        `inflated_labels` are added).  The model, its heads and the memory are neither read nor changed."""
         return self.model.route(objects, object_labels, map_shape=map_shape, from_cell=from_cell, passable=passable, path_max=path_max,
-                                sweeps=sweeps)
+                                sweeps=sweeps, body_radius2=body_radius2)
+
+    def clearance(self, objects, object_labels, map_shape=None, radius2: int = 0, keep_cell: Optional[int] = None, passable=None) -> Dict:
+        """How much room there is round the map objects: the dict of `CustomRCNNRecurrent.clearance` (`d2`, `nearest`, `owner`,
+        `inflated`, `cells`, `territory`, `widest_d2`, `widest_cell`, `open_key`, `counts`, ...) for the objects of an `inventory` on
+        the grid `map_shape` = (rows, cols).  The model, its heads and the memory are neither read nor changed."""
+        return self.model.clearance(objects, object_labels, map_shape=map_shape, radius2=radius2, keep_cell=keep_cell, passable=passable)
 
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`

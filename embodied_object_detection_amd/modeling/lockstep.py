@@ -41,8 +41,8 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
-from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _describe, _det_stream, _instances, _map_inventory, _map_regions, _place,
-                        _relations, _result_sets, _route, _sched_streams, _semmap_locate, _semmap_query, _ticket)
+from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _clearance, _describe, _det_stream, _instances, _map_inventory, _map_regions,
+                        _place, _relations, _result_sets, _route, _sched_streams, _semmap_locate, _semmap_query, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -255,7 +255,7 @@ class LockstepScenes:
         return _relations(objects, object_labels, map_shape, radius, from_cell, topn)
 
     def route(self, objects, object_labels, map_shape=None, from_cell=None, passable=None, path_max: int = 256,
-              sweeps: Optional[int] = None):
+              sweeps: Optional[int] = None, body_radius2: Optional[int] = None):
         """`CustomRCNNRecurrent.route`; with the `[B, K]` objects and `[B, N]` object_labels of `inventory(None, ...)` the op runs
         once per scene, `from_cell` is one int or a sequence of B, and every entry of the dict gains a leading [B].  Nothing of
         the batch model changes."""
@@ -271,9 +271,29 @@ class LockstepScenes:
             if len(cells) != B:
                 raise _lib.EodError(f"route: from_cell: {len(cells)} cells for {B} scenes")
             per = [_route(objects[b].contiguous(), object_labels[b].contiguous(), map_shape, None if cells[b] is None else int(cells[b]),
-                          passable, path_max, sweeps) for b in range(B)]
+                          passable, path_max, sweeps, body_radius2) for b in range(B)]
             return {k: torch.stack([p[k] for p in per]) for k in per[0]}
-        return _route(objects, object_labels, map_shape, from_cell, passable, path_max, sweeps)
+        return _route(objects, object_labels, map_shape, from_cell, passable, path_max, sweeps, body_radius2)
+
+    def clearance(self, objects, object_labels, map_shape=None, radius2: int = 0, keep_cell=None, passable=None):
+        """`CustomRCNNRecurrent.clearance`; with the `[B, K]` objects and `[B, N]` object_labels of `inventory(None, ...)` the op
+        runs once per scene, `keep_cell` is None, one int or a sequence of B, and every entry of the dict gains a leading [B].
+        Nothing of the batch model changes."""
+        if isinstance(object_labels, torch.Tensor) and object_labels.dim() == 2:
+            B = int(object_labels.shape[0])
+            objects = torch.as_tensor(objects, dtype=torch.int32, device=object_labels.device)
+            if objects.dim() != 2 or objects.shape[0] != B:
+                raise _lib.EodError(f"clearance: objects {tuple(objects.shape)}: expected [B, K] beside object_labels "
+                                    f"{tuple(object_labels.shape)}")
+            if isinstance(keep_cell, torch.Tensor):
+                keep_cell = keep_cell.tolist()
+            cells = list(keep_cell) if hasattr(keep_cell, "__len__") else [keep_cell] * B
+            if len(cells) != B:
+                raise _lib.EodError(f"clearance: keep_cell: {len(cells)} cells for {B} scenes")
+            per = [_clearance(objects[b].contiguous(), object_labels[b].contiguous(), map_shape, radius2,
+                              None if cells[b] is None else int(cells[b]), passable) for b in range(B)]
+            return {k: torch.stack([p[k] for p in per]) for k in per[0]}
+        return _clearance(objects, object_labels, map_shape, radius2, keep_cell, passable)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

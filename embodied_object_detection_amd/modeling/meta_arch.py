@@ -173,9 +173,38 @@ def _relations(objects, object_labels, map_shape, radius, from_cell, topn):
     return ops.map_relations(object_labels, objects, cols, radius=radius, from_cell=-1 if from_cell is None else from_cell, topn=topn)
 
 
-def _route(objects, object_labels, map_shape, from_cell, passable=None, path_max=256, sweeps=None):
+def _clearance(objects, object_labels, map_shape, radius2=0, keep_cell=None, passable=None):
+    """`clearance` on one label map: `ops.map_clearance` on the grid `map_shape`.  Reads no model and no memory."""
+    if map_shape is None:
+        raise _lib.EodError("clearance: map_shape (rows, cols) is required: the distances are those of the grid")
+    rows, cols = int(map_shape[0]), int(map_shape[1])
+    if not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or rows < 1 or cols < 1 or rows * cols != object_labels.shape[0]:
+        raise _lib.EodError(f"clearance: map_shape {tuple(map_shape)} does not hold the {tuple(getattr(object_labels, 'shape', ()))} "
+                            "cells of object_labels")
+    if not isinstance(objects, torch.Tensor):
+        objects = torch.as_tensor(objects, dtype=torch.int32, device=object_labels.device)
+    if passable is not None and not isinstance(passable, torch.Tensor):
+        passable = torch.as_tensor(passable, dtype=torch.int32, device=object_labels.device).reshape(-1)
+    res = ops.map_clearance(object_labels, objects, cols, radius2=radius2, keep_cell=-1 if keep_cell is None else keep_cell,
+                            passable=passable)
+    status = int(res["status"][0])                                   # the results are handed over here
+    if status & 2:
+        raise _lib.EodError(f"clearance: a bounded loop of eod_map_clearance reached its bound (status {status}); the result is void")
+    return res
+
+
+def _route(objects, object_labels, map_shape, from_cell, passable=None, path_max=256, sweeps=None, body_radius2=None):
     """`route` on one label map: `ops.map_route` on the grid `map_shape`, resumed while the sweeps run out (each resumed call with
-    twice the sweeps of the last, `ops.ROUTE_RESUMES` of them at the most).  Reads no model and no memory."""
+    twice the sweeps of the last, `ops.ROUTE_RESUMES` of them at the most).  With `body_radius2` the route runs on the `inflated`
+    labels of `_clearance(radius2=body_radius2, keep_cell=from_cell)`.  Reads no model and no memory."""
+    if body_radius2 is not None:
+        if from_cell is None:
+            raise _lib.EodError("route: from_cell is required: the cell the paths start from (RobotFrontEnd.exclude_cell(pose))")
+        clr = _clearance(objects, object_labels, map_shape, body_radius2, from_cell, passable)
+        res = dict(_route(objects, clr["inflated"], map_shape, from_cell, passable, path_max, sweeps))
+        res["clearance_d2"] = clr["d2"]
+        res["inflated_labels"] = clr["inflated"]
+        return res
     if map_shape is None:
         raise _lib.EodError("route: map_shape (rows, cols) is required: the moves are those of the grid")
     rows, cols = int(map_shape[0]), int(map_shape[1])
@@ -983,7 +1012,7 @@ class CustomRCNNRecurrent:
         return _relations(objects, object_labels, map_shape, radius, from_cell, topn)
 
     def route(self, objects, object_labels, map_shape=None, from_cell: Optional[int] = None, passable=None, path_max: int = 256,
-              sweeps: Optional[int] = None) -> dict:
+              sweeps: Optional[int] = None, body_radius2: Optional[int] = None) -> dict:
         """How to reach the map objects: the dict of `ops.map_route` for `objects` int32 [K] (a sequence will do) and
         `object_labels` int32 [N] (`inv["object"]` and `inv["object_labels"]` of `inventory`) on the grid `map_shape` =
         (rows, cols), from `from_cell` (the robot's cell, `RobotFrontEnd.exclude_cell(pose)`); both are required.  Every labelled
@@ -995,8 +1024,26 @@ class CustomRCNNRecurrent:
         their number, `cells` the object's cells; `counts` the free and the reached cells.  Metres: `RobotFrontEnd.route_metres`
         and `cell_centers(route["path"][k])`.  `sweeps` (None: `ops.map_route_sweeps`) is the number of sweep launches of one call;
         the status is read here, a call whose sweeps ran out is resumed up to `ops.ROUTE_RESUMES` times, and `EodError` is raised
-        if the distances have not settled by then.  Reads neither the model nor the memory."""
-        return _route(objects, object_labels, map_shape, from_cell, passable, path_max, sweeps)
+        if the distances have not settled by then.  `body_radius2` (None: a point, nothing else runs): the squared radius of the
+        robot's body in cells (`RobotFrontEnd.body_radius2`); the call then runs `clearance(radius2=body_radius2,
+        keep_cell=from_cell, passable=passable)` first and routes on its `inflated` labels, and the dict gains `clearance_d2` and
+        `inflated_labels` [N].  Every object is then grown by the radius: `goal_cell` lies on the rim of the inflated object, where
+        the body's centre may stand, and `cells` counts the inflated cells.  Reads neither the model nor the memory."""
+        return _route(objects, object_labels, map_shape, from_cell, passable, path_max, sweeps, body_radius2)
+
+    def clearance(self, objects, object_labels, map_shape=None, radius2: int = 0, keep_cell: Optional[int] = None, passable=None) -> dict:
+        """How much room there is round the map objects: the dict of `ops.map_clearance` for `objects` int32 [K] (a sequence will
+        do) and `object_labels` int32 [N] (`inv["object"]` and `inv["object_labels"]` of `inventory`) on the grid `map_shape` =
+        (rows, cols), which is required.  Every labelled cell blocks unless its label is one of `passable`.  Per cell `d2` is the
+        exact squared distance in cells to the nearest blocked cell (0 on one; INT_MAX on a map without any), `nearest` that cell
+        (the lowest on a tie) and `owner` its label: the partition of the free space by nearest object.  `inflated` is the label map
+        for a body of squared radius `radius2` (`RobotFrontEnd.body_radius2`): free cells at most that far from an object take its
+        label, except those at most that far from `keep_cell` (the robot's cell; None: no exception); hand it to `route`, or
+        pass `body_radius2` there.  Per object `cells`, `territory` (the free cells nearest to it), and `widest_cell` / `widest_d2`:
+        the most open cell of its territory, the place to stand and look at it; `open_key`: the most open cell of the map;
+        `counts`: blocked, free and inflated cells.  Metres: `RobotFrontEnd.clearance_metres`.  The status is read here.  Reads
+        neither the model nor the memory."""
+        return _clearance(objects, object_labels, map_shape, radius2, keep_cell, passable)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

@@ -1937,3 +1937,98 @@ def map_route(object_labels: torch.Tensor, objects: torch.Tensor, cols: int, fro
                                     part["counts"].data_ptr(), part["status"].data_ptr(), workspace.data_ptr(), workspace.numel() * 4,
                                     _stream()), "eod_map_route")
     return {"dist": dist, "parent": parent, "goal_key": goal_key, **part}
+
+
+CLEARANCE_K_MAX, CLEARANCE_P_MAX, CLEARANCE_N_MAX, CLEARANCE_DIM_MAX = 64, 64, 1 << 22, 32767
+# the rows and columns one workgroup of the row pass owns and the columns it stages either side (CL_TR, CL_CC, CL_HALO of
+# csrc/clearance.hip)
+CLEARANCE_TILE_ROWS, CLEARANCE_CHUNK_COLS, CLEARANCE_HALO_COLS = 4, 64, 64
+CLEARANCE_NONE = 2 ** 31 - 1                             # d2 of a map without a blocked cell
+
+
+def map_clearance_workspace(N: int, cols: int) -> int:
+    """int32 words of a `map_clearance` workspace (eod_map_clearance_workspace_bytes / 4): one byte and one int32 per cell."""
+    need = int(_lib.load().eod_map_clearance_workspace_bytes(int(N), int(cols)))
+    if need == 0:
+        raise _lib.EodError(f"map_clearance_workspace: N {N}, cols {cols}")
+    return need // 4
+
+
+def map_clearance(object_labels: torch.Tensor, objects: torch.Tensor, cols: int, radius2: int = 0, keep_cell: int = -1, passable=None,
+                  workspace: Optional[torch.Tensor] = None) -> dict:
+    """The exact squared distance from every cell of a label map to the nearest blocked cell, that cell, and the map inflated by a
+    body of squared radius `radius2` (eod_map_clearance; the semantics are those of include/eod_clearance.h).  `object_labels`
+    int32 [N], cell i = r * cols + c; `objects` int32 [K], 1 <= K <= 64, as `inv["object"]` holds them (-1 in unused slots; a cell
+    belongs to the lowest slot that names its label).  A cell is blocked when its label is >= 0 and not one of `passable` (None, or
+    int32 [P], P <= 64, or a sequence); `keep_cell` does not change that.  Returns per cell `d2` int32 [N] (0 on a blocked cell,
+    INT_MAX when the map has none), `nearest` (the lowest blocked cell at that distance; the cell itself; -1), `owner` (its label;
+    -1) and `inflated` (the label map for `map_route` with a body: a free cell with d2 <= radius2 takes its owner's label, unless
+    `keep_cell` >= 0 is at most radius2 away from it); per slot `cells`, `territory` (the free cells nearest to the slot),
+    `widest_key` int64 [K] (the bits of the unsigned maximum of (d2 << 32) | ~cell over them; 0), `widest_d2` (0) and `widest_cell`
+    (-1); `open_key` int64 [1] (the same maximum over all free cells), `counts` int32 [3] (blocked, free, free cells that
+    `inflated` changed) and `status` int32 [2] (bit 1 of status[0]: a bounded loop reached its bound), which is not read here, so
+    nothing synchronises.  `workspace`: int32, 8-byte aligned, at least `map_clearance_workspace(N, cols)` words, any contents.
+    Integer min, max, multiply and add only: the same bits on every call."""
+    if (not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or object_labels.dtype != torch.int32
+            or not object_labels.is_contiguous()):
+        raise _lib.EodError(f"map_clearance: object_labels {_describe_what(object_labels)}: expected contiguous int32 [N]")
+    N = int(object_labels.shape[0])
+    if not 1 <= N <= CLEARANCE_N_MAX:
+        raise _lib.EodError(f"map_clearance: object_labels: N {N} outside 1..{CLEARANCE_N_MAX}")
+    dev = object_labels.device
+    if (not isinstance(objects, torch.Tensor) or objects.dim() != 1 or objects.dtype != torch.int32 or not objects.is_contiguous()
+            or objects.device != dev):
+        raise _lib.EodError(f"map_clearance: objects {_describe_what(objects)}: expected contiguous int32 [K] on the labels' device")
+    K = int(objects.shape[0])
+    if not 1 <= K <= CLEARANCE_K_MAX:
+        raise _lib.EodError(f"map_clearance: objects: K {K} outside 1..{CLEARANCE_K_MAX}")
+
+    def whole(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if not whole(cols) or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_clearance: cols {cols} does not divide the {N} cells")
+    if int(cols) > CLEARANCE_DIM_MAX or N // int(cols) > CLEARANCE_DIM_MAX:
+        raise _lib.EodError(f"map_clearance: cols {cols}: {N // int(cols)} rows x {cols} columns, more than {CLEARANCE_DIM_MAX} one way")
+    if not whole(radius2) or not 0 <= int(radius2) < CLEARANCE_NONE:
+        raise _lib.EodError(f"map_clearance: radius2 {radius2} outside 0..{CLEARANCE_NONE - 1}")
+    if not whole(keep_cell) or not -1 <= int(keep_cell) < N:
+        raise _lib.EodError(f"map_clearance: keep_cell {keep_cell} outside -1..{N - 1}")
+    if passable is not None and not isinstance(passable, torch.Tensor):
+        try:
+            passable = torch.as_tensor(np.asarray(list(passable), dtype=np.int64).astype(np.int32).reshape(-1), device=dev)
+        except (TypeError, ValueError, OverflowError):
+            raise _lib.EodError(f"map_clearance: passable {type(passable).__name__}: expected None, int32 [P] or a sequence of "
+                                "labels") from None
+    if passable is not None and (passable.dim() != 1 or passable.dtype != torch.int32 or not passable.is_contiguous()
+                                 or passable.device != dev or passable.shape[0] > CLEARANCE_P_MAX):
+        raise _lib.EodError(f"map_clearance: passable {_describe_what(passable)}: expected contiguous int32 [P], P <= "
+                            f"{CLEARANCE_P_MAX}, on the labels' device")
+    P = 0 if passable is None else int(passable.shape[0])
+    if not object_labels.is_cuda:
+        raise _lib.EodError("map_clearance: object_labels on the host (no CPU fallback)")
+    need = map_clearance_workspace(N, int(cols))
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev
+                                  or workspace.data_ptr() % 8 != 0):
+        raise _lib.EodError(f"map_clearance: workspace: expected {need} contiguous, 8-byte aligned int32 on the labels' device")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+    per_cell = torch.empty((4, N), dtype=torch.int32, device=dev)
+    keys = torch.empty((K + 1,), dtype=torch.int64, device=dev)      # widest_key, open_key
+    out = torch.empty((4 * K + 5,), dtype=torch.int32, device=dev)
+    part = {}
+    at = 0
+    for name, n in (("cells", K), ("territory", K), ("widest_d2", K), ("widest_cell", K), ("counts", 3), ("status", 2)):
+        part[name] = out[at:at + n]
+        at += n
+    d2, nearest, owner, inflated = per_cell[0], per_cell[1], per_cell[2], per_cell[3]
+    widest_key, open_key = keys[:K], keys[K:]
+    check(_lib.load().eod_map_clearance(object_labels.data_ptr(), objects.data_ptr(), _ptr(passable) if P else None, N, K, P, int(cols),
+                                        int(radius2), int(keep_cell), d2.data_ptr(), nearest.data_ptr(), owner.data_ptr(),
+                                        inflated.data_ptr(), part["cells"].data_ptr(), part["territory"].data_ptr(),
+                                        widest_key.data_ptr(), part["widest_d2"].data_ptr(), part["widest_cell"].data_ptr(),
+                                        open_key.data_ptr(), part["counts"].data_ptr(), part["status"].data_ptr(),
+                                        workspace.data_ptr(), workspace.numel() * 4, _stream()), "eod_map_clearance")
+    return {"d2": d2, "nearest": nearest, "owner": owner, "inflated": inflated, "cells": part["cells"],
+            "territory": part["territory"], "widest_key": widest_key, "widest_d2": part["widest_d2"],
+            "widest_cell": part["widest_cell"], "open_key": open_key, "counts": part["counts"], "status": part["status"]}
