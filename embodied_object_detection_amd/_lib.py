@@ -1,7 +1,7 @@
 """ctypes binding of libeod_hip.so (C ABI declared in include/eod_hip.h; the frame-side map queries in include/eod_place.h, the
 map regions in include/eod_regions.h, the map inventory in include/eod_inventory.h, the object descriptions in
 include/eod_describe.h, the object relations in include/eod_relations.h, the routes in include/eod_route.h, the clearance map in
-include/eod_clearance.h).
+include/eod_clearance.h, the line of sight in include/eod_sight.h).
 
 Fails loudly: there is no CPU fallback.  If the shared library is missing or a call returns a negative
 EOD_ERR_* code, an exception is raised.
@@ -280,6 +280,12 @@ CLEARANCE_SIGNATURES = {
     "eod_map_clearance": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_size_t, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/eod_sight.h declares (which cells each of up to 64 cells sees, per object)
+SIGHT_SIGNATURES = {
+    "eod_map_sight_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    "eod_map_sight": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -294,7 +300,8 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES, **REGIONS_SIGNATURES, **INVENTORY_SIGNATURES,
-                              **DESCRIBE_SIGNATURES, **RELATIONS_SIGNATURES, **ROUTE_SIGNATURES, **CLEARANCE_SIGNATURES}.items():
+                              **DESCRIBE_SIGNATURES, **RELATIONS_SIGNATURES, **ROUTE_SIGNATURES, **CLEARANCE_SIGNATURES,
+                              **SIGHT_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -123,7 +123,8 @@ class RobotFrontEnd:
 
     def clearance_metres(self, d2) -> np.ndarray:
         """The squared cell distances of `clearance` (`d2`, `widest_d2`) in metres: sqrt(d2) * res as float64 in the shape of `d2`;
-        inf for INT_MAX (the map has no blocked cell).  The place to stand is `cell_centers(clr["widest_cell"])`."""
+        inf for INT_MAX (the map has no blocked cell).  The most open place is `cell_centers(clr["widest_cell"])`; whether the
+        object is in view from it is `sight`'s to say."""
         d = np.asarray(d2.cpu() if torch.is_tensor(d2) else d2, dtype=np.int64)
         return np.where(d == 2 ** 31 - 1, np.inf, np.sqrt(d.astype(np.float64)) * self.res)
 
@@ -131,6 +132,12 @@ class RobotFrontEnd:
         """The `radius2` of `clearance` and the `body_radius2` of `route` for a body of radius `metres`: the radius in cells,
         squared and rounded down (1e-9 keeps a radius that is a whole number of cells from falling short by rounding)."""
         return int(np.floor((float(metres) / self.res) ** 2 + 1e-9))
+
+    def sight_range2(self, metres: float) -> int:
+        """The `range2` of `sight` for a sensor that reaches `metres`: the range in cells, squared and rounded down, as
+        `body_radius2` rounds, and INT_MAX (unbounded) from there on.  The `near_d2` of `sight` in metres is
+        `relation_metres(near_d2)`."""
+        return int(min(np.floor((float(metres) / self.res) ** 2 + 1e-9), 2 ** 31 - 1))
 
     def exclude_cell(self, pose_xyt: Sequence[float]) -> int:
         """The robot's own cell as the memory's index `x * map_h + y`: the `exclude_cell` of `place`."""

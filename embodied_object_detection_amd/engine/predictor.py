@@ -129,6 +129,13 @@ class EmbodiedPredictor:
         the grid `map_shape` = (rows, cols).  The model, its heads and the memory are neither read nor changed."""
         return self.model.clearance(objects, object_labels, map_shape=map_shape, radius2=radius2, keep_cell=keep_cell, passable=passable)
 
+    def sight(self, objects, object_labels, map_shape=None, from_cells=None, range2: Optional[int] = None, passable=None) -> Dict:
+        """What can be seen from where: the dict of `CustomRCNNRecurrent.sight` (`seen_mask`, `seen_cells`, `near_d2`, `near_cell`,
+        `best_seen`, `best_source`, `source_counts`, `counts`, ...) for the objects of an `inventory` on the grid `map_shape` =
+        (rows, cols), from up to 64 candidate cells `from_cells` within the squared range `range2` (None: unbounded).  The model,
+        its heads and the memory are neither read nor changed."""
+        return self.model.sight(objects, object_labels, map_shape=map_shape, from_cells=from_cells, range2=range2, passable=passable)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

@@ -42,7 +42,7 @@ import torch
 
 from .. import _lib, ops
 from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _clearance, _describe, _det_stream, _instances, _map_inventory, _map_regions,
-                        _place, _relations, _result_sets, _route, _sched_streams, _semmap_locate, _semmap_query, _ticket)
+                        _place, _relations, _result_sets, _route, _sched_streams, _semmap_locate, _semmap_query, _sight, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -294,6 +294,26 @@ class LockstepScenes:
                               None if cells[b] is None else int(cells[b]), passable) for b in range(B)]
             return {k: torch.stack([p[k] for p in per]) for k in per[0]}
         return _clearance(objects, object_labels, map_shape, radius2, keep_cell, passable)
+
+    def sight(self, objects, object_labels, map_shape=None, from_cells=None, range2: Optional[int] = None, passable=None):
+        """`CustomRCNNRecurrent.sight`; with the `[B, K]` objects and `[B, N]` object_labels of `inventory(None, ...)` the op runs
+        once per scene, `from_cells` is [B, S] (a tensor or a sequence of B sequences), and every entry of the dict gains a leading
+        [B].  Nothing of the batch model changes."""
+        if isinstance(object_labels, torch.Tensor) and object_labels.dim() == 2:
+            B = int(object_labels.shape[0])
+            objects = torch.as_tensor(objects, dtype=torch.int32, device=object_labels.device)
+            if objects.dim() != 2 or objects.shape[0] != B:
+                raise _lib.EodError(f"sight: objects {tuple(objects.shape)}: expected [B, K] beside object_labels "
+                                    f"{tuple(object_labels.shape)}")
+            if isinstance(from_cells, torch.Tensor):
+                from_cells = from_cells.tolist()
+            rows = list(from_cells) if hasattr(from_cells, "__len__") else None
+            if rows is None or len(rows) != B or any(not hasattr(r, "__len__") or len(r) != len(rows[0]) for r in rows):
+                raise _lib.EodError(f"sight: from_cells: expected [B, S] cells for the {B} scenes")
+            per = [_sight(objects[b].contiguous(), object_labels[b].contiguous(), map_shape, [int(v) for v in rows[b]], range2, passable)
+                   for b in range(B)]
+            return {k: torch.stack([p[k] for p in per]) for k in per[0]}
+        return _sight(objects, object_labels, map_shape, from_cells, range2, passable)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

@@ -193,6 +193,28 @@ def _clearance(objects, object_labels, map_shape, radius2=0, keep_cell=None, pas
     return res
 
 
+def _sight(objects, object_labels, map_shape, from_cells, range2=None, passable=None):
+    """`sight` on one label map: `ops.map_sight` on the grid `map_shape`.  Reads no model and no memory."""
+    if map_shape is None:
+        raise _lib.EodError("sight: map_shape (rows, cols) is required: the lines are those of the grid")
+    rows, cols = int(map_shape[0]), int(map_shape[1])
+    if not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or rows < 1 or cols < 1 or rows * cols != object_labels.shape[0]:
+        raise _lib.EodError(f"sight: map_shape {tuple(map_shape)} does not hold the {tuple(getattr(object_labels, 'shape', ()))} "
+                            "cells of object_labels")
+    if from_cells is None:
+        raise _lib.EodError("sight: from_cells is required: the cells to look from (RobotFrontEnd.exclude_cell(pose), "
+                            "clearance's widest_cell, route's goal_cell)")
+    if not isinstance(objects, torch.Tensor):
+        objects = torch.as_tensor(objects, dtype=torch.int32, device=object_labels.device)
+    if passable is not None and not isinstance(passable, torch.Tensor):
+        passable = torch.as_tensor(passable, dtype=torch.int32, device=object_labels.device).reshape(-1)
+    res = ops.map_sight(object_labels, objects, cols, from_cells, range2=range2, passable=passable)
+    status = int(res["status"][0])                                   # the results are handed over here
+    if status & 2:
+        raise _lib.EodError(f"sight: a bounded loop of eod_map_sight reached its bound (status {status}); the result is void")
+    return res
+
+
 def _route(objects, object_labels, map_shape, from_cell, passable=None, path_max=256, sweeps=None, body_radius2=None):
     """`route` on one label map: `ops.map_route` on the grid `map_shape`, resumed while the sweeps run out (each resumed call with
     twice the sweeps of the last, `ops.ROUTE_RESUMES` of them at the most).  With `body_radius2` the route runs on the `inflated`
@@ -1040,10 +1062,34 @@ class CustomRCNNRecurrent:
         for a body of squared radius `radius2` (`RobotFrontEnd.body_radius2`): free cells at most that far from an object take its
         label, except those at most that far from `keep_cell` (the robot's cell; None: no exception); hand it to `route`, or
         pass `body_radius2` there.  Per object `cells`, `territory` (the free cells nearest to it), and `widest_cell` / `widest_d2`:
-        the most open cell of its territory, the place to stand and look at it; `open_key`: the most open cell of the map;
+        the most open cell of its territory (`sight` says whether the object is in view from it); `open_key`: the most open cell of the map;
         `counts`: blocked, free and inflated cells.  Metres: `RobotFrontEnd.clearance_metres`.  The status is read here.  Reads
         neither the model nor the memory."""
         return _clearance(objects, object_labels, map_shape, radius2, keep_cell, passable)
+
+    def sight(self, objects, object_labels, map_shape=None, from_cells=None, range2: Optional[int] = None, passable=None) -> dict:
+        """What can be seen from where: the dict of `ops.map_sight` for `objects` int32 [K] (a sequence will do) and
+        `object_labels` int32 [N] (`inv["object"]` and `inv["object_labels"]` of `inventory`) on the grid `map_shape` =
+        (rows, cols), from the cells `from_cells` (one int, or a sequence or tensor of up to 64; negative: unused); both are
+        required.  Every labelled cell is opaque unless its label is one of `passable`; a source's own cell never blocks its own
+        view.  `range2` is the sensor's range in cells, squared (`RobotFrontEnd.sight_range2`; None: unbounded).  Source s sees a
+        cell when it is in range and the rounded straight line to it meets no opaque cell before it and passes between no two
+        opaque cells that touch at a corner; the cell itself may be opaque: one sees the face of an object.  `seen_mask` int64 [N]
+        holds bit s of cell i for source s; per (source, object) `seen_cells` is how many of the object's cells the source sees and
+        `near_cell` / `near_d2` the nearest of them (-1 / INT_MAX: none; metres: `RobotFrontEnd.relation_metres(near_d2)`); per
+        object `best_source` is the candidate that sees most of it (-1: none does) and `best_seen` how many cells that is;
+        `source_counts` the transparent and opaque cells each source sees; `counts` the opaque, the transparent and the seen cells.
+
+            clr = model.clearance(objs, labels, shape)
+            rt = model.route(objs, labels, shape, from_cell=here)
+            s = model.sight(objs, labels, shape, from_cells=torch.cat([torch.tensor([here], device=labels.device),
+                            clr["widest_cell"], rt["goal_cell"]]), range2=front.sight_range2(4.0))
+            s["best_source"][k]          # which of the candidates to drive to for a look at object k
+
+        `from_cells` is the one argument the entry point reads on the host (a cell outside the map is refused before any launch):
+        a device tensor, as in the lines above, is copied there first, one synchronisation; a sequence of ints costs none.  Never
+        hand `eod_map_sight` itself a device pointer for it.  The status is read here.  Reads neither the model nor the memory."""
+        return _sight(objects, object_labels, map_shape, from_cells, range2, passable)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

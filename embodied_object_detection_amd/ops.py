@@ -2032,3 +2032,124 @@ def map_clearance(object_labels: torch.Tensor, objects: torch.Tensor, cols: int,
     return {"d2": d2, "nearest": nearest, "owner": owner, "inflated": inflated, "cells": part["cells"],
             "territory": part["territory"], "widest_key": widest_key, "widest_d2": part["widest_d2"],
             "widest_cell": part["widest_cell"], "open_key": open_key, "counts": part["counts"], "status": part["status"]}
+
+
+SIGHT_K_MAX, SIGHT_P_MAX, SIGHT_S_MAX, SIGHT_N_MAX, SIGHT_DIM_MAX = 64, 64, 64, 1 << 22, 32767
+# up to SIGHT_LDS_CELLS cells the walk reads the opacity bit plane from LDS, above it from the workspace; a workgroup of the walk
+# owns SIGHT_WORKGROUP consecutive cells and looks from one group of SIGHT_SOURCE_GROUP sources (csrc/sight.hip)
+SIGHT_LDS_CELLS, SIGHT_SOURCE_GROUP, SIGHT_WORKGROUP = 131072, 16, 256
+SIGHT_UNBOUNDED = 2 ** 31 - 1                            # range2 of a sensor without a range; near_d2 where nothing is seen
+
+
+def map_sight_workspace(N: int, cols: int) -> int:
+    """int32 words of a `map_sight` workspace (eod_map_sight_workspace_bytes / 4): one byte and one bit per cell."""
+    need = int(_lib.load().eod_map_sight_workspace_bytes(int(N), int(cols)))
+    if need == 0:
+        raise _lib.EodError(f"map_sight_workspace: N {N}, cols {cols}")
+    return need // 4
+
+
+def map_sight(object_labels: torch.Tensor, objects: torch.Tensor, cols: int, from_cells, range2: Optional[int] = None, passable=None,
+              workspace: Optional[torch.Tensor] = None) -> dict:
+    """Which cells of a label map each of up to 64 cells sees, and how much of every object (eod_map_sight; the semantics are those
+    of include/eod_sight.h).  `object_labels` int32 [N], cell i = r * cols + c; `objects` int32 [K], 1 <= K <= 64, as
+    `inv["object"]` holds them (-1 in unused slots; a cell belongs to the lowest slot that names its label).  A cell is opaque when
+    its label is >= 0 and not one of `passable` (None, or int32 [P], P <= 64, or a sequence).  `from_cells`: one int, or a sequence
+    or an int32/int64 tensor of 1 <= S <= 64 cells 0..N-1 to look from, negative for an unused source, duplicates allowed; the entry
+    point reads them on the host, so a tensor on the device is copied there first (the one synchronisation of this call; a sequence
+    or a host tensor costs none).  `range2`: the sensor's range in cells, squared; None is unbounded.  Source s sees cell t when t is
+    within the range, no cell of the rounded line from s to t strictly between them is opaque, and no diagonal step of the line
+    passes between two opaque cells; the source's own cell is transparent on its own lines, and the line is not symmetric in s and t.
+    Returns `seen_mask` int64 [N]: bit s of cell i (`(seen_mask[i] >> s) & 1`; bit 63, source 63, is the sign bit) is set exactly
+    when source s is used and sees cell i; per slot `cells`; per (source, slot) `seen_cells` int32 [S, K], `near_key` int64 [S, K]
+    (the bits of the unsigned minimum of (d2 << 32) | cell over the seen cells of the slot; all ones), `near_d2` (INT_MAX) and
+    `near_cell` (-1), the nearest visible cell of the object; per slot `best_key` int64 [K] (the maximum of (seen_cells << 32) | ~s;
+    0), `best_seen` (0) and `best_source` (-1), the source that sees most of the object, the lowest on a tie; `source_counts` int32
+    [S, 2] (transparent and opaque cells seen), `counts` int32 [3] (opaque cells, transparent cells, cells anyone sees) and `status`
+    int32 [2] (bit 1 of status[0]: a bounded loop reached its bound), which is not read here.  `workspace`: int32, 8-byte aligned,
+    at least `map_sight_workspace(N, cols)` words, any contents.  Integer comparisons, additions and atomics only: the same bits on
+    every call."""
+    if (not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or object_labels.dtype != torch.int32
+            or not object_labels.is_contiguous()):
+        raise _lib.EodError(f"map_sight: object_labels {_describe_what(object_labels)}: expected contiguous int32 [N]")
+    N = int(object_labels.shape[0])
+    if not 1 <= N <= SIGHT_N_MAX:
+        raise _lib.EodError(f"map_sight: object_labels: N {N} outside 1..{SIGHT_N_MAX}")
+    dev = object_labels.device
+    if (not isinstance(objects, torch.Tensor) or objects.dim() != 1 or objects.dtype != torch.int32 or not objects.is_contiguous()
+            or objects.device != dev):
+        raise _lib.EodError(f"map_sight: objects {_describe_what(objects)}: expected contiguous int32 [K] on the labels' device")
+    K = int(objects.shape[0])
+    if not 1 <= K <= SIGHT_K_MAX:
+        raise _lib.EodError(f"map_sight: objects: K {K} outside 1..{SIGHT_K_MAX}")
+
+    def whole(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if not whole(cols) or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_sight: cols {cols} does not divide the {N} cells")
+    if int(cols) > SIGHT_DIM_MAX or N // int(cols) > SIGHT_DIM_MAX:
+        raise _lib.EodError(f"map_sight: cols {cols}: {N // int(cols)} rows x {cols} columns, more than {SIGHT_DIM_MAX} one way")
+    if isinstance(from_cells, torch.Tensor):
+        if from_cells.dtype not in (torch.int32, torch.int64) or from_cells.dim() > 1 or from_cells.is_meta:
+            raise _lib.EodError(f"map_sight: from_cells {_describe_what(from_cells)}: expected int32 or int64 [S] or one cell")
+        src = from_cells.detach().cpu().numpy().astype(np.int64).reshape(-1)
+    else:
+        try:
+            seq = [from_cells] if whole(from_cells) else list(from_cells)
+            if not all(whole(v) for v in seq):
+                raise TypeError
+            src = np.asarray(seq, dtype=np.int64).reshape(-1)
+        except (TypeError, ValueError, OverflowError):
+            raise _lib.EodError(f"map_sight: from_cells {type(from_cells).__name__}: expected one cell, or a sequence or tensor of "
+                                "cells") from None
+    if not 1 <= src.size <= SIGHT_S_MAX:
+        raise _lib.EodError(f"map_sight: from_cells: S {src.size} outside 1..{SIGHT_S_MAX}")
+    if src.max() >= N or src.min() < -2 ** 31:
+        raise _lib.EodError(f"map_sight: from_cells: {int(src.max() if src.max() >= N else src.min())} is no cell of the {N} (negative: unused)")
+    src = np.ascontiguousarray(src.astype(np.int32))
+    S = int(src.size)
+    if range2 is None:
+        range2 = SIGHT_UNBOUNDED
+    if not whole(range2) or not 0 <= int(range2) <= SIGHT_UNBOUNDED:
+        raise _lib.EodError(f"map_sight: range2 {range2} outside 0..{SIGHT_UNBOUNDED} (None: unbounded)")
+    if passable is not None and not isinstance(passable, torch.Tensor):
+        try:
+            passable = torch.as_tensor(np.asarray(list(passable), dtype=np.int64).astype(np.int32).reshape(-1), device=dev)
+        except (TypeError, ValueError, OverflowError):
+            raise _lib.EodError(f"map_sight: passable {type(passable).__name__}: expected None, int32 [P] or a sequence of "
+                                "labels") from None
+    if passable is not None and (passable.dim() != 1 or passable.dtype != torch.int32 or not passable.is_contiguous()
+                                 or passable.device != dev or passable.shape[0] > SIGHT_P_MAX):
+        raise _lib.EodError(f"map_sight: passable {_describe_what(passable)}: expected contiguous int32 [P], P <= "
+                            f"{SIGHT_P_MAX}, on the labels' device")
+    P = 0 if passable is None else int(passable.shape[0])
+    if not object_labels.is_cuda:
+        raise _lib.EodError("map_sight: object_labels on the host (no CPU fallback)")
+    need = map_sight_workspace(N, int(cols))
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev
+                                  or workspace.data_ptr() % 8 != 0):
+        raise _lib.EodError(f"map_sight: workspace: expected {need} contiguous, 8-byte aligned int32 on the labels' device")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+    seen_mask = torch.empty((N,), dtype=torch.int64, device=dev)
+    keys = torch.empty((S * K + K,), dtype=torch.int64, device=dev)  # near_key, best_key
+    out = torch.empty((3 * S * K + 3 * K + 2 * S + 5,), dtype=torch.int32, device=dev)
+    part = {}
+    at = 0
+    for name, n, shape in (("cells", K, (K,)), ("seen_cells", S * K, (S, K)), ("near_d2", S * K, (S, K)), ("near_cell", S * K, (S, K)),
+                           ("best_seen", K, (K,)), ("best_source", K, (K,)), ("source_counts", 2 * S, (S, 2)), ("counts", 3, (3,)),
+                           ("status", 2, (2,))):
+        part[name] = out[at:at + n].view(shape)
+        at += n
+    near_key, best_key = keys[:S * K].view(S, K), keys[S * K:]
+    check(_lib.load().eod_map_sight(object_labels.data_ptr(), objects.data_ptr(), _ptr(passable) if P else None, src.ctypes.data, N, K,
+                                    P, S, int(cols), int(range2), seen_mask.data_ptr(), part["cells"].data_ptr(),
+                                    part["seen_cells"].data_ptr(), near_key.data_ptr(), part["near_d2"].data_ptr(),
+                                    part["near_cell"].data_ptr(), best_key.data_ptr(), part["best_seen"].data_ptr(),
+                                    part["best_source"].data_ptr(), part["source_counts"].data_ptr(), part["counts"].data_ptr(),
+                                    part["status"].data_ptr(), workspace.data_ptr(), workspace.numel() * 4, _stream()), "eod_map_sight")
+    return {"seen_mask": seen_mask, "cells": part["cells"], "seen_cells": part["seen_cells"], "near_key": near_key,
+            "near_d2": part["near_d2"], "near_cell": part["near_cell"], "best_key": best_key, "best_seen": part["best_seen"],
+            "best_source": part["best_source"], "source_counts": part["source_counts"], "counts": part["counts"],
+            "status": part["status"]}
