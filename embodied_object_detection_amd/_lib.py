@@ -1,7 +1,7 @@
 """ctypes binding of libeod_hip.so (C ABI declared in include/eod_hip.h; the frame-side map queries in include/eod_place.h, the
 map regions in include/eod_regions.h, the map inventory in include/eod_inventory.h, the object descriptions in
 include/eod_describe.h, the object relations in include/eod_relations.h, the routes in include/eod_route.h, the clearance map in
-include/eod_clearance.h, the line of sight in include/eod_sight.h).
+include/eod_clearance.h, the line of sight in include/eod_sight.h, the frontiers in include/eod_frontier.h).
 
 Fails loudly: there is no CPU fallback.  If the shared library is missing or a call returns a negative
 EOD_ERR_* code, an exception is raised.
@@ -286,6 +286,13 @@ SIGHT_SIGNATURES = {
     "eod_map_sight": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_size_t, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/eod_frontier.h declares (the record of the covered cells, the frontiers of a map)
+FRONTIER_SIGNATURES = {
+    "eod_map_cover": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2),
+    "eod_map_frontier_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    "eod_map_frontier": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p] * 18 + [C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -301,7 +308,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES, **REGIONS_SIGNATURES, **INVENTORY_SIGNATURES,
                               **DESCRIBE_SIGNATURES, **RELATIONS_SIGNATURES, **ROUTE_SIGNATURES, **CLEARANCE_SIGNATURES,
-                              **SIGHT_SIGNATURES}.items():
+                              **SIGHT_SIGNATURES, **FRONTIER_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

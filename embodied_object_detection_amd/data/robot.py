@@ -86,8 +86,9 @@ class RobotFrontEnd:
 
 
     def cell_centers(self, cells) -> np.ndarray:
-        """`cell_center` for many memory indices `x * map_h + y` at once (the `cells` of `place`, the `peaks` of `locate`):
-        float64 [n, 2] in metres, NaN for the padding value -1."""
+        """`cell_center` for many memory indices `x * map_h + y` at once (the `cells` of `place`, the `peaks` of `locate`, the
+        `reach_cell` of `frontiers`: the known free cell to drive to for a look beyond a frontier): float64 [n, 2] in metres, NaN for
+        the padding value -1."""
         c = np.asarray(cells.cpu() if torch.is_tensor(cells) else cells, dtype=np.int64).reshape(-1)
         cx, cy = np.divmod(c, self.map_h)
         out = np.stack([cx * self.res + float(self.map_shift[0]), cy * self.res + float(self.map_shift[2])], axis=1).astype(np.float64)
@@ -110,14 +111,16 @@ class RobotFrontEnd:
     def relation_metres(self, d2) -> np.ndarray:
         """The squared cell distances of `relations` (`min_d2`, `nearest_d2`, `from_d2`) in metres: sqrt(d2) * res as float64 in the
         shape of `d2`; inf for INT_MAX (no pair within reach, an empty slot, no `from_cell`).  The point to drive to is
-        `cell_centers(rel["from_closest"])`."""
+        `cell_centers(rel["from_closest"])`.  The `reach_cost` of `frontiers` goes through here when it is a squared distance
+        (`from_cell` given, no `route`)."""
         d = np.asarray(d2.cpu() if torch.is_tensor(d2) else d2, dtype=np.int64)
         return np.where(d == 2 ** 31 - 1, np.inf, np.sqrt(d.astype(np.float64)) * self.res)
 
     def route_metres(self, cost) -> np.ndarray:
         """The costs of `route` (`dist`, `goal_cost`) in metres: cost / 5 * res as float64 in the shape of `cost` (a move along a
         row or column costs 5, a diagonal one 7); inf for INT_MAX (blocked, unreached, no way to the object).  The waypoints are
-        `cell_centers(route["path"][k])`, NaN behind the path's end."""
+        `cell_centers(route["path"][k])`, NaN behind the path's end.  The `reach_cost` of `frontiers(..., route=rt)` is such a
+        cost, taken from `rt["dist"]`; the centroid of a frontier is `region_centroids(fr["sum_rc"], fr["area"])`."""
         d = np.asarray(cost.cpu() if torch.is_tensor(cost) else cost, dtype=np.int64)
         return np.where(d == 2 ** 31 - 1, np.inf, d.astype(np.float64) / 5.0 * self.res)
 

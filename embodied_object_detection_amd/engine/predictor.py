@@ -136,6 +136,20 @@ class EmbodiedPredictor:
         its heads and the memory are neither read nor changed."""
         return self.model.sight(objects, object_labels, map_shape=map_shape, from_cells=from_cells, range2=range2, passable=passable)
 
+    def cover(self, data: Dict, stamp: Optional[int] = None, exclude_cell: int = -1):
+        """Record what the camera covered in the frame `data` (the dict the predictor was called with): `CustomRCNNRecurrent.cover`
+        on `data["proj_indices"]`.  Returns `last_seen` int32 [N].  Nothing the frame computes changes."""
+        return self.model.cover(data["proj_indices"], stamp=stamp, exclude_cell=exclude_cell)
+
+    def frontiers(self, object_labels, map_shape=None, since: int = 0, last_seen=None, from_cell: Optional[int] = None, route=None,
+                  passable=None, min_cells: int = 2, topk: int = 16, rank_by="behind") -> Dict:
+        """Where the known space ends and what lies beyond: the dict of `CustomRCNNRecurrent.frontiers` (`frontier`, `area`,
+        `behind_area`, `reach_cell`, `reach_cost`, `frontier_labels`, `unknown_labels`, `counts`, ...) for the label map of an
+        `inventory` on the grid `map_shape` = (rows, cols), from the record `cover` keeps (`last_seen` None) or the `last_seen` given.  The model,
+        its heads and the memory are not changed."""
+        return self.model.frontiers(object_labels, map_shape=map_shape, since=since, last_seen=last_seen, from_cell=from_cell,
+                                    route=route, passable=passable, min_cells=min_cells, topk=topk, rank_by=rank_by)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

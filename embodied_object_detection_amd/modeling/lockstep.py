@@ -41,8 +41,9 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
-from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _clearance, _describe, _det_stream, _instances, _map_inventory, _map_regions,
-                        _place, _relations, _result_sets, _route, _sched_streams, _semmap_locate, _semmap_query, _sight, _ticket)
+from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _clearance, _cover, _describe, _det_stream, _frontiers, _instances,
+                        _map_inventory, _map_regions, _observed, _place, _relations, _result_sets, _route, _sched_streams,
+                        _semmap_locate, _semmap_query, _sight, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -81,6 +82,8 @@ class LockstepScenes:
         self.trail_detection_pass = True     # step t's detection mask pass + paste under step t + 1's latency-bound front
         self.implicit_memory: Optional[torch.Tensor] = None     # [B,N,512]
         self.observations: Optional[torch.Tensor] = None        # [B,N]
+        self._last_seen: Optional[torch.Tensor] = None          # [B,N] int32: the stamp of the last `cover` of each cell, -1: none
+        self._cover_stamp = [0] * self.B
         self._mem_f16 = self._dirty = None
         self._f16_valid = False
         self._dirty_pending = False
@@ -180,6 +183,8 @@ class LockstepScenes:
         _lib.check(lib.eod_fill_f32(obs.data_ptr(), 0.0, obs.numel(), s), "fill")
         _lib.check(lib.eod_fill_i32(m16.data_ptr(), 0, m16.numel() // 2, s), "fill")
         _lib.check(lib.eod_fill_i32(dirty.data_ptr(), 0, dirty.numel(), s), "fill")
+        if self._last_seen is not None:
+            self._last_seen[b].fill_(-1)
         self._started[b] = True
 
     def invalidate_memory_snapshot(self):
@@ -314,6 +319,56 @@ class LockstepScenes:
                    for b in range(B)]
             return {k: torch.stack([p[k] for p in per]) for k in per[0]}
         return _sight(objects, object_labels, map_shape, from_cells, range2, passable)
+
+    def cover(self, scene: int, proj_indices, stamp: Optional[int] = None, exclude_cell: int = -1):
+        """`CustomRCNNRecurrent.cover` for scene `scene`: the record is int32 [B, N], a row per scene with a stamp counter of its
+        own, made at the first call and cleared to -1 for a scene by its `reset_memory`; the scene's counter goes on across a reset, so a
+        stamp never repeats and `since=` the stamp of the first call after the reset asks for what was covered since.  Returns the
+        scene's row."""
+        if not 0 <= int(scene) < self.B:
+            raise IndexError(f"scene {scene} of a lock-step batch of {self.B}")
+        if self.implicit_memory is None:
+            raise _lib.EodError("cover: no memory yet (no frame has run)")
+        b, n_cells = int(scene), int(self.implicit_memory.shape[1])
+        if self._last_seen is None or self._last_seen.shape[1] != n_cells:
+            self._last_seen = torch.full((self.B, n_cells), -1, dtype=torch.int32, device=self.device)
+        if stamp is None:
+            stamp = self._cover_stamp[b]
+        row = _cover(self.model, proj_indices, self._last_seen[b], n_cells, stamp, exclude_cell)
+        self._cover_stamp[b] = max(self._cover_stamp[b], int(stamp) + 1)
+        return row
+
+    def frontiers(self, object_labels, map_shape=None, since: int = 0, last_seen=None, from_cell=None, route=None, passable=None,
+                  min_cells: int = 2, topk: int = 16, rank_by="behind", scene: Optional[int] = None):
+        """`CustomRCNNRecurrent.frontiers`; with the `[B, N]` object_labels of `inventory(None, ...)` the op runs once per scene
+        and every entry of the dict gains a leading [B]: `last_seen` is [B, N] (None: the record `cover` keeps, or
+        `observations > 0` where it was never called), `from_cell` None, one int or a sequence of B, `route` None or a sequence of
+        the B dicts of `route` (or one dict whose `dist` is [B, N]).  With object_labels [N], `scene` picks the scene whose record
+        to take.  Nothing of the batch model changes."""
+        if last_seen is None:
+            last_seen = self._last_seen
+            if last_seen is None and self.observations is not None:
+                last_seen = _observed(self.observations)
+        if isinstance(object_labels, torch.Tensor) and object_labels.dim() == 2:
+            B = int(object_labels.shape[0])
+            if not isinstance(last_seen, torch.Tensor) or last_seen.dim() != 2 or last_seen.shape[0] != B:
+                raise _lib.EodError(f"frontiers: last_seen {tuple(getattr(last_seen, 'shape', ()))}: expected [B, N] beside object_labels "
+                                    f"{tuple(object_labels.shape)}")
+            cells = list(from_cell) if hasattr(from_cell, "__len__") else [from_cell] * B
+            if isinstance(route, dict):
+                routes = [route["dist"][b].contiguous() for b in range(B)]
+            else:
+                routes = list(route) if route is not None else [None] * B
+            if len(cells) != B or len(routes) != B:
+                raise _lib.EodError(f"frontiers: from_cell and route: expected one entry for each of the {B} scenes")
+            per = [_frontiers(object_labels[b].contiguous(), map_shape, last_seen[b].contiguous(), since,
+                              None if cells[b] is None else int(cells[b]), routes[b], passable, min_cells, topk, rank_by) for b in range(B)]
+            return {k: torch.stack([p[k] for p in per]) for k in per[0]}
+        if isinstance(last_seen, torch.Tensor) and last_seen.dim() == 2:
+            if scene is None or not 0 <= int(scene) < last_seen.shape[0]:
+                raise _lib.EodError(f"frontiers: object_labels [N] beside a record of {last_seen.shape[0]} scenes: pass scene=")
+            last_seen = last_seen[int(scene)].contiguous()
+        return _frontiers(object_labels, map_shape, last_seen, since, from_cell, route, passable, min_cells, topk, rank_by)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

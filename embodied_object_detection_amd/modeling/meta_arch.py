@@ -215,6 +215,43 @@ def _sight(objects, object_labels, map_shape, from_cells, range2=None, passable=
     return res
 
 
+def _cover(model, proj_indices, last_seen, n_cells, stamp, exclude_cell):
+    """`cover` on one scene: `ops.map_cover` into `last_seen` (None: a new int32 [n_cells] of -1).  Returns the buffer."""
+    proj = model._device_proj({"proj_indices": proj_indices})
+    if last_seen is None:
+        last_seen = torch.full((int(n_cells),), -1, dtype=torch.int32, device=proj.device)
+    return ops.map_cover(proj, last_seen, stamp, exclude_cell)
+
+
+def _frontiers(object_labels, map_shape, last_seen, since=0, from_cell=None, route=None, passable=None, min_cells=2, topk=16,
+               rank_by="behind"):
+    """`frontiers` on one label map: `ops.map_frontier` on the grid `map_shape`.  Reads no model and no memory."""
+    if map_shape is None:
+        raise _lib.EodError("frontiers: map_shape (rows, cols) is required: the neighbours are those of the grid")
+    rows, cols = int(map_shape[0]), int(map_shape[1])
+    if not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or rows < 1 or cols < 1 or rows * cols != object_labels.shape[0]:
+        raise _lib.EodError(f"frontiers: map_shape {tuple(map_shape)} does not hold the {tuple(getattr(object_labels, 'shape', ()))} "
+                            "cells of object_labels")
+    if not object_labels.is_cuda:
+        raise _lib.EodError("frontiers: object_labels on the host (no CPU fallback)")
+    if last_seen is None:
+        raise _lib.EodError("frontiers: no record of what was covered: call cover(proj_indices) on every frame, or pass last_seen")
+    dist = None
+    if route is not None:
+        dist = route["dist"] if isinstance(route, dict) else route
+    res = ops.map_frontier(object_labels, last_seen, cols, since=since, dist=dist, from_cell=-1 if from_cell is None else from_cell,
+                           passable=passable, min_cells=min_cells, topk=topk, rank_by=rank_by)
+    status = int(res["status"][0])                                   # the results are handed over here
+    if status != 0:
+        raise _lib.EodError(f"frontiers: a bounded loop of eod_map_frontier reached its bound (status {status}); the result is void")
+    return res
+
+
+def _observed(observations):
+    """The weaker record where `cover` never ran: 0 where the memory was written, -1 elsewhere."""
+    return torch.where(observations > 0, 0, -1).to(torch.int32)
+
+
 def _route(objects, object_labels, map_shape, from_cell, passable=None, path_max=256, sweeps=None, body_radius2=None):
     """`route` on one label map: `ops.map_route` on the grid `map_shape`, resumed while the sweeps run out (each resumed call with
     twice the sweeps of the last, `ops.ROUTE_RESUMES` of them at the most).  With `body_radius2` the route runs on the `inflated`
@@ -468,6 +505,8 @@ class CustomRCNNRecurrent:
         self.implicit_memory: Optional[torch.Tensor] = None   # [N,512] f32  (== semmap_features)
         self.observations: Optional[torch.Tensor] = None      # [N] f32      (== observation_count)
         self.semmap = None
+        self._last_seen: Optional[torch.Tensor] = None        # [N] int32: the stamp of the last `cover` of each cell, -1: none
+        self._cover_stamp = 0
         self._mem_f16: Optional[torch.Tensor] = None
         self._dirty: Optional[torch.Tensor] = None          # int32 [N]: rows of the fp16 snapshot that are out of date
         self._f16_valid = False
@@ -521,6 +560,7 @@ class CustomRCNNRecurrent:
         self._f16_valid = True
         self._dirty_pending = False
         self.semmap = None
+        self._last_seen = None
 
     def invalidate_memory_snapshot(self):
         """Call after writing `implicit_memory` / `observations` from outside (e.g. a loaded snapshot): the next frame
@@ -1090,6 +1130,52 @@ class CustomRCNNRecurrent:
         a device tensor, as in the lines above, is copied there first, one synchronisation; a sequence of ints costs none.  Never
         hand `eod_map_sight` itself a device pointer for it.  The status is read here.  Reads neither the model nor the memory."""
         return _sight(objects, object_labels, map_shape, from_cells, range2, passable)
+
+    def cover(self, proj_indices, stamp: Optional[int] = None, exclude_cell: int = -1) -> torch.Tensor:
+        """Record what the camera covered: every cell under a pixel of the frame's `proj_indices` (numpy or tensor, [H, W] or
+        [H, W, 1]; the cells outside the map and `exclude_cell` are dropped, as in `place`) takes the stamp of this call in
+        `last_seen` int32 [N], which is returned (-1: never covered).  The buffer is made at the first call after a
+        `reset_memory` and dropped by the next one.  `stamp` None: a counter that grows by one per call, from 0, and goes on across a
+        `reset_memory` (a stamp never repeats; `since=` the first stamp after the reset asks for what was covered since); an int:
+        that stamp, and the counter goes on behind it.  One launch of `ops.map_cover`; the frame itself never calls it, and nothing it
+        computes changes."""
+        if self.implicit_memory is None:
+            raise _lib.EodError("cover: no memory yet (no frame has run)")
+        if stamp is None:
+            stamp = self._cover_stamp
+        self._last_seen = _cover(self, proj_indices, self._last_seen, int(self.implicit_memory.shape[0]), stamp, exclude_cell)
+        self._cover_stamp = max(self._cover_stamp, int(stamp) + 1)
+        return self._last_seen
+
+    def frontiers(self, object_labels, map_shape=None, since: int = 0, last_seen=None, from_cell: Optional[int] = None, route=None,
+                  passable=None, min_cells: int = 2, topk: int = 16, rank_by="behind") -> dict:
+        """Where the known space ends and what lies beyond: the dict of `ops.map_frontier` for `object_labels` int32 [N]
+        (`inv["object_labels"]` of `inventory`) on the grid `map_shape` = (rows, cols), which is required.  A labelled cell is
+        BLOCKED unless its label is one of `passable`; every other cell is OPEN when `last_seen >= since` and UNKNOWN when not.  A
+        frontier is an 8-connected set of OPEN cells that each have an UNKNOWN 4-neighbour.  Per frontier, ranked by `rank_by`
+        ("behind": the cells of the largest unknown region it opens onto; "area": its own cells), `frontier` (its label, the
+        lowest cell; -1: padding), `area`, `bbox`, `sum_rc` (`RobotFrontEnd.region_centroids`), `open_edges`, `behind_area` /
+        `behind_label`, and `reach_cell` / `reach_cost`: the known free cell of it to drive to (`RobotFrontEnd.cell_centers`) and
+        what the way costs: with `route=` (the dict of `route`, or its `dist`) the cost of the route there
+        (`RobotFrontEnd.route_metres`; a frontier no route reaches has INT_MAX / -1), otherwise with `from_cell` the squared
+        distance in cells (`RobotFrontEnd.relation_metres`), otherwise 0 and the lowest cell.  Per cell `frontier_labels`,
+        `unknown_labels`, `unknown_area`; `count`, `counts` (BLOCKED, OPEN, UNKNOWN, frontier cells, unknown regions).
+
+            model.cover(data["proj_indices"], exclude_cell=front.exclude_cell(pose))        # after every frame
+            rt = model.route(inv["object"], inv["object_labels"], shape, from_cell=here)
+            fr = model.frontiers(inv["object_labels"], shape, route=rt)
+            front.cell_centers(fr["reach_cell"][:1])     # where to drive to look into the largest unknown region
+
+        `last_seen` None takes the record `cover` keeps.  Where `cover` was never called since the last `reset_memory` it takes
+        `observations > 0` as 0 / -1, a weaker record: the memory counts a cell only where a proposal's mask covered a pixel that
+        landed in it, so bare floor and walls the camera saw without proposing anything there stay UNKNOWN, and the frontiers lie
+        round the detected objects rather than at the edge of the view.  Raises when `status` is not 0.  Changes nothing of the
+        model."""
+        if last_seen is None:
+            last_seen = self._last_seen
+            if last_seen is None and self.observations is not None:
+                last_seen = _observed(self.observations)
+        return _frontiers(object_labels, map_shape, last_seen, since, from_cell, route, passable, min_cells, topk, rank_by)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

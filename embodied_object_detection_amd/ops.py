@@ -2153,3 +2153,141 @@ def map_sight(object_labels: torch.Tensor, objects: torch.Tensor, cols: int, fro
             "near_d2": part["near_d2"], "near_cell": part["near_cell"], "best_key": best_key, "best_seen": part["best_seen"],
             "best_source": part["best_source"], "source_counts": part["source_counts"], "counts": part["counts"],
             "status": part["status"]}
+
+
+FRONTIER_P_MAX, FRONTIER_TOPK_MAX, FRONTIER_N_MAX, FRONTIER_DIM_MAX, FRONTIER_PIXELS_MAX = 64, 64, 1 << 22, 32767, 1 << 24
+FRONTIER_RANKS = {"area": 0, "behind": 1}                # rank_by: by the frontier's own cells, or by the unknown region behind it
+FRONTIER_NO_WAY = 2 ** 31 - 1                            # reach_cost where no cell of the frontier can be reached
+
+
+def _whole(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def map_cover(proj_indices: torch.Tensor, last_seen: torch.Tensor, stamp: int, exclude_cell: int = -1) -> torch.Tensor:
+    """The record of what the camera covered (eod_map_cover; include/eod_frontier.h): for every pixel of `proj_indices` (int32, any
+    shape, contiguous) whose cell c has 0 <= c < N and c != `exclude_cell`, `last_seen[c] = max(last_seen[c], stamp)`, in place.
+    `last_seen` is int32 [N], filled with -1 by the caller once; `stamp` >= 0.  Every other pixel is dropped.  One launch, integer
+    atomics only: the result depends neither on the order of the pixels nor on that of the frames with one stamp.  Returns
+    `last_seen`."""
+    if (not isinstance(proj_indices, torch.Tensor) or proj_indices.dtype != torch.int32 or not proj_indices.is_contiguous()):
+        raise _lib.EodError(f"map_cover: proj_indices {_describe_what(proj_indices)}: expected contiguous int32")
+    if (not isinstance(last_seen, torch.Tensor) or last_seen.dim() != 1 or last_seen.dtype != torch.int32 or not last_seen.is_contiguous()
+            or last_seen.device != proj_indices.device):
+        raise _lib.EodError(f"map_cover: last_seen {_describe_what(last_seen)}: expected contiguous int32 [N] on the pixels' device")
+    P, N = int(proj_indices.numel()), int(last_seen.shape[0])
+    if P > FRONTIER_PIXELS_MAX or not 1 <= N <= FRONTIER_N_MAX:
+        raise _lib.EodError(f"map_cover: {P} pixels (at most {FRONTIER_PIXELS_MAX}), {N} cells (1..{FRONTIER_N_MAX})")
+    if not _whole(stamp) or not 0 <= int(stamp) <= 2 ** 31 - 1:
+        raise _lib.EodError(f"map_cover: stamp {stamp} outside 0..{2 ** 31 - 1}")
+    if not _whole(exclude_cell) or not -2 ** 31 <= int(exclude_cell) <= 2 ** 31 - 1:
+        raise _lib.EodError(f"map_cover: exclude_cell {exclude_cell}: expected an int (-1: none)")
+    if not last_seen.is_cuda:
+        raise _lib.EodError("map_cover: last_seen on the host (no CPU fallback)")
+    check(_lib.load().eod_map_cover(proj_indices.data_ptr() if P else None, P, N, int(stamp), int(exclude_cell), last_seen.data_ptr(),
+                                    _stream()), "eod_map_cover")
+    return last_seen
+
+
+def map_frontier_workspace(N: int, cols: int) -> int:
+    """int32 words of a `map_frontier` workspace (eod_map_frontier_workspace_bytes / 4)."""
+    need = int(_lib.load().eod_map_frontier_workspace_bytes(int(N), int(cols)))
+    if need == 0:
+        raise _lib.EodError(f"map_frontier_workspace: N {N}, cols {cols}")
+    return need // 4
+
+
+def map_frontier(object_labels: torch.Tensor, last_seen: torch.Tensor, cols: int, since: int = 0, dist: Optional[torch.Tensor] = None,
+                 from_cell: int = -1, passable=None, min_cells: int = 2, topk: int = 16, rank_by="behind",
+                 workspace: Optional[torch.Tensor] = None) -> dict:
+    """Where the known space ends and what lies beyond (eod_map_frontier; the semantics are those of include/eod_frontier.h).
+    `object_labels` int32 [N], cell i = r * cols + c; `last_seen` int32 [N], the record of `map_cover`.  A cell is BLOCKED when its
+    label is >= 0 and not one of `passable` (None, int32 [P], P <= 64, or a sequence), otherwise OPEN when `last_seen >= since` and
+    UNKNOWN when not.  A frontier cell is an OPEN cell with an UNKNOWN 4-neighbour; a frontier an 8-connected component of them; an
+    unknown region a 4-connected component of UNKNOWN cells; a label the lowest cell.  Returns per cell `frontier_labels`,
+    `unknown_labels` (-1 elsewhere) and `unknown_area` (at a region's label cell its cells, 0 elsewhere), int32 [N]; `count` [1], the
+    frontiers of at least `min_cells` cells; for the `topk` (1..64) of them with the largest rank key, in descending order
+    (`rank_by` "area" or 0: (area << 32) | ~label; "behind" or 1: (behind_area << 32) | ~label), `frontier` (the label; -1 in a
+    padding slot), `area`, `bbox` [K, 4], `sum_rc` int64 [K, 2], `open_edges` (pairs of a frontier cell and an UNKNOWN neighbour),
+    `behind_key` int64 with its halves `behind_area` and `behind_label` (the largest unknown region the frontier opens onto; 0 and
+    -1), `reach_key` int64 (the minimum of (v << 32) | cell over the frontier's cells with v < INT_MAX; all ones) with its halves
+    `reach_cost` (INT_MAX) and `reach_cell` (-1): v is `dist[cell]` with `dist` int32 [N] (the `dist` of `map_route`), otherwise the
+    squared distance in cells from `from_cell` (0..N-1), otherwise 0.  `counts` int32 [5]: BLOCKED, OPEN, UNKNOWN cells, frontier
+    cells, unknown regions; `status` int32 [2] (bit 1 of status[0]: a bounded loop reached its bound), which is not read here.
+    `workspace`: int32, 8-byte aligned, at least `map_frontier_workspace(N, cols)` words, any contents.  Integer comparisons,
+    additions and atomics only: the same bits on every call."""
+    if (not isinstance(object_labels, torch.Tensor) or object_labels.dim() != 1 or object_labels.dtype != torch.int32
+            or not object_labels.is_contiguous()):
+        raise _lib.EodError(f"map_frontier: object_labels {_describe_what(object_labels)}: expected contiguous int32 [N]")
+    N = int(object_labels.shape[0])
+    if not 1 <= N <= FRONTIER_N_MAX:
+        raise _lib.EodError(f"map_frontier: object_labels: N {N} outside 1..{FRONTIER_N_MAX}")
+    dev = object_labels.device
+    if (not isinstance(last_seen, torch.Tensor) or last_seen.shape != object_labels.shape or last_seen.dtype != torch.int32
+            or not last_seen.is_contiguous() or last_seen.device != dev):
+        raise _lib.EodError(f"map_frontier: last_seen {_describe_what(last_seen)}: expected contiguous int32 [{N}] on the labels' device")
+    if dist is not None and (not isinstance(dist, torch.Tensor) or dist.shape != object_labels.shape or dist.dtype != torch.int32
+                             or not dist.is_contiguous() or dist.device != dev):
+        raise _lib.EodError(f"map_frontier: dist {_describe_what(dist)}: expected None or contiguous int32 [{N}] on the labels' device")
+    if not _whole(cols) or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_frontier: cols {cols} does not divide the {N} cells")
+    if int(cols) > FRONTIER_DIM_MAX or N // int(cols) > FRONTIER_DIM_MAX:
+        raise _lib.EodError(f"map_frontier: cols {cols}: {N // int(cols)} rows x {cols} columns, more than {FRONTIER_DIM_MAX} one way")
+    if not _whole(since) or not -2 ** 31 <= int(since) <= 2 ** 31 - 1:
+        raise _lib.EodError(f"map_frontier: since {since}: expected an int32")
+    if from_cell is None:
+        from_cell = -1
+    if not _whole(from_cell) or not -1 <= int(from_cell) < N:
+        raise _lib.EodError(f"map_frontier: from_cell {from_cell} is no cell of the {N} (-1 or None: none)")
+    if not _whole(min_cells) or not 1 <= int(min_cells) <= 2 ** 31 - 1:
+        raise _lib.EodError(f"map_frontier: min_cells {min_cells}: expected at least 1")
+    if not _whole(topk) or not 1 <= int(topk) <= FRONTIER_TOPK_MAX:
+        raise _lib.EodError(f"map_frontier: topk {topk} outside 1..{FRONTIER_TOPK_MAX}")
+    if isinstance(rank_by, str) and rank_by in FRONTIER_RANKS:
+        rank_by = FRONTIER_RANKS[rank_by]
+    if not _whole(rank_by) or int(rank_by) not in (0, 1):
+        raise _lib.EodError(f"map_frontier: rank_by {rank_by!r}: expected 'area' (0) or 'behind' (1)")
+    if passable is not None and not isinstance(passable, torch.Tensor):
+        try:
+            passable = torch.as_tensor(np.asarray(list(passable), dtype=np.int64).astype(np.int32).reshape(-1), device=dev)
+        except (TypeError, ValueError, OverflowError):
+            raise _lib.EodError(f"map_frontier: passable {type(passable).__name__}: expected None, int32 [P] or a sequence of "
+                                "labels") from None
+    if passable is not None and (passable.dim() != 1 or passable.dtype != torch.int32 or not passable.is_contiguous()
+                                 or passable.device != dev or passable.shape[0] > FRONTIER_P_MAX):
+        raise _lib.EodError(f"map_frontier: passable {_describe_what(passable)}: expected contiguous int32 [P], P <= "
+                            f"{FRONTIER_P_MAX}, on the labels' device")
+    P = 0 if passable is None else int(passable.shape[0])
+    if not object_labels.is_cuda:
+        raise _lib.EodError("map_frontier: object_labels on the host (no CPU fallback)")
+    need = map_frontier_workspace(N, int(cols))
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev
+                                  or workspace.data_ptr() % 8 != 0):
+        raise _lib.EodError(f"map_frontier: workspace: expected {need} contiguous, 8-byte aligned int32 on the labels' device")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+    K = int(topk)
+    cells = torch.empty((3, N), dtype=torch.int32, device=dev)       # frontier_labels, unknown_labels, unknown_area
+    keys = torch.empty((4 * K,), dtype=torch.int64, device=dev)      # sum_rc, behind_key, reach_key
+    out = torch.empty((12 * K + 8,), dtype=torch.int32, device=dev)
+    part = {}
+    at = 0
+    for name, n, shape in (("count", 1, (1,)), ("frontier", K, (K,)), ("area", K, (K,)), ("bbox", 4 * K, (K, 4)),
+                           ("open_edges", K, (K,)), ("behind_area", K, (K,)), ("behind_label", K, (K,)), ("reach_cost", K, (K,)),
+                           ("reach_cell", K, (K,)), ("counts", 5, (5,)), ("status", 2, (2,))):
+        part[name] = out[at:at + n].view(shape)
+        at += n
+    sum_rc, behind_key, reach_key = keys[:2 * K].view(K, 2), keys[2 * K:3 * K], keys[3 * K:]
+    check(_lib.load().eod_map_frontier(
+        object_labels.data_ptr(), _ptr(passable) if P else None, last_seen.data_ptr(), None if dist is None else dist.data_ptr(), N, P,
+        int(cols), int(since), int(from_cell), int(min_cells), K, int(rank_by), cells[0].data_ptr(), cells[1].data_ptr(),
+        cells[2].data_ptr(), part["count"].data_ptr(), part["frontier"].data_ptr(), part["area"].data_ptr(), part["bbox"].data_ptr(),
+        sum_rc.data_ptr(), part["open_edges"].data_ptr(), behind_key.data_ptr(), part["behind_area"].data_ptr(),
+        part["behind_label"].data_ptr(), reach_key.data_ptr(), part["reach_cost"].data_ptr(), part["reach_cell"].data_ptr(),
+        part["counts"].data_ptr(), part["status"].data_ptr(), workspace.data_ptr(), workspace.numel() * 4, _stream()), "eod_map_frontier")
+    return {"frontier_labels": cells[0], "unknown_labels": cells[1], "unknown_area": cells[2], "count": part["count"],
+            "frontier": part["frontier"], "area": part["area"], "bbox": part["bbox"], "sum_rc": sum_rc,
+            "open_edges": part["open_edges"], "behind_key": behind_key, "behind_area": part["behind_area"],
+            "behind_label": part["behind_label"], "reach_key": reach_key, "reach_cost": part["reach_cost"],
+            "reach_cell": part["reach_cell"], "counts": part["counts"], "status": part["status"]}
