@@ -1,7 +1,8 @@
 """ctypes binding of libeod_hip.so (C ABI declared in include/eod_hip.h; the frame-side map queries in include/eod_place.h, the
 map regions in include/eod_regions.h, the map inventory in include/eod_inventory.h, the object descriptions in
 include/eod_describe.h, the object relations in include/eod_relations.h, the routes in include/eod_route.h, the clearance map in
-include/eod_clearance.h, the line of sight in include/eod_sight.h, the frontiers in include/eod_frontier.h).
+include/eod_clearance.h, the line of sight in include/eod_sight.h, the frontiers in include/eod_frontier.h, the obstacles in
+include/eod_obstacles.h).
 
 Fails loudly: there is no CPU fallback.  If the shared library is missing or a call returns a negative
 EOD_ERR_* code, an exception is raised.
@@ -293,6 +294,13 @@ FRONTIER_SIGNATURES = {
     "eod_map_frontier": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p] * 18 + [C.c_size_t, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/eod_obstacles.h declares (the height record of the frames, the obstacles of a map)
+OBSTACLES_SIGNATURES = {
+    "eod_map_heights": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 6 + [C.c_void_p] * 5),
+    "eod_map_obstacles_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    "eod_map_obstacles": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p] * 16 + [C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -308,7 +316,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES, **REGIONS_SIGNATURES, **INVENTORY_SIGNATURES,
                               **DESCRIBE_SIGNATURES, **RELATIONS_SIGNATURES, **ROUTE_SIGNATURES, **CLEARANCE_SIGNATURES,
-                              **SIGHT_SIGNATURES, **FRONTIER_SIGNATURES}.items():
+                              **SIGHT_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLES_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

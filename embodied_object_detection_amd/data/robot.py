@@ -57,20 +57,35 @@ class RobotFrontEnd:
         self.sequence_name = sequence_name
         self._first = True
 
-    def frame(self, rgb_hwc_u8: np.ndarray, depth_mm: np.ndarray, pose_xyt: Sequence[float], file_name: str = "") -> Dict:
+    def frame(self, rgb_hwc_u8: np.ndarray, depth_mm: np.ndarray, pose_xyt: Sequence[float], file_name: str = "",
+              heights: bool = False) -> Dict:
+        """The frame dict the model takes.  `heights=True` adds `"heights"`, float32 [H, W]: the world y of every pixel in metres,
+        from the same launch that makes `proj_indices` (for `heights` of the model and the predictor); a `projector` of the
+        caller's own must then take `want_xyz=True` and say so with an attribute `returns_xyz = True` (`synthetic.hip_projector`
+        does), otherwise the call raises.  The default leaves the dict as it always was."""
         if self.projector is None:
             from .synthetic import hip_projector
             self.projector = hip_projector()
+        if heights and not getattr(self.projector, "returns_xyz", False):
+            raise ValueError("RobotFrontEnd.frame(heights=True): the projector cannot return heights (it needs a want_xyz argument "
+                             "and the attribute returns_xyz = True, as synthetic.hip_projector has)")
         H, W = depth_mm.shape
         # robot_demo.py:515-517: uint16 millimetres / 1000 in float64, then FloatTensor (one rounding to fp32)
         depth_m = (np.asarray(depth_mm, dtype=np.float64) / 1000).astype(np.float32)
         T = robot_transform(pose_xyt)
-        proj = self.projector(depth_m, T, ROBOT_INTRINSICS, (0.0, 0.0, 0.0), self.map_shift, self.res, self.map_w, self.map_h, 1)
+        args = (depth_m, T, ROBOT_INTRINSICS, (0.0, 0.0, 0.0), self.map_shift, self.res, self.map_w, self.map_h, 1)
+        if heights:
+            proj, xyz = self.projector(*args, want_xyz=True)
+        else:
+            proj = self.projector(*args)
         image = torch.from_numpy(np.ascontiguousarray(np.asarray(rgb_hwc_u8).transpose(2, 0, 1)))
         reset, self._first = self._first, False
-        return {"image": image, "height": H, "width": W, "proj_indices": np.ascontiguousarray(proj, dtype=np.int32).reshape(H, W, 1),
-                "memory": np.zeros((self.n_cells, 1), dtype=np.float32), "memory_reset": reset,
-                "sequence_name": self.sequence_name, "observations": None, "file_name": file_name}
+        out = {"image": image, "height": H, "width": W, "proj_indices": np.ascontiguousarray(proj, dtype=np.int32).reshape(H, W, 1),
+               "memory": np.zeros((self.n_cells, 1), dtype=np.float32), "memory_reset": reset,
+               "sequence_name": self.sequence_name, "observations": None, "file_name": file_name}
+        if heights:
+            out["heights"] = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(H, W, 3)[:, :, 1])
+        return out
 
     def robot_cell(self, pose_xyt: Sequence[float]) -> Tuple[int, int]:
         """Robot position on the map (robot_demo.py:536-538)."""
@@ -141,6 +156,15 @@ class RobotFrontEnd:
         `body_radius2` rounds, and INT_MAX (unbounded) from there on.  The `near_d2` of `sight` in metres is
         `relation_metres(near_d2)`."""
         return int(min(np.floor((float(metres) / self.res) ** 2 + 1e-9), 2 ** 31 - 1))
+
+    def height_band_mm(self, lo_m: float, hi_m: float) -> Tuple[int, int]:
+        """The `band_mm` of `heights` for a body that clears what is lower than `lo_m` and passes under what is higher than `hi_m`
+        (metres above the world's zero, the floor the camera height `ROBOT_CAMERA_HEIGHT` is measured from): whole millimetres,
+        rounded to nearest."""
+        lo, hi = int(round(float(lo_m) * 1000.0)), int(round(float(hi_m) * 1000.0))
+        if not -1000000 <= lo <= hi <= 1000000:
+            raise ValueError(f"height_band_mm: {lo_m} .. {hi_m} m: expected lo <= hi within +-1000 m")
+        return lo, hi
 
     def exclude_cell(self, pose_xyt: Sequence[float]) -> int:
         """The robot's own cell as the memory's index `x * map_h + y`: the `exclude_cell` of `place`."""

@@ -44,10 +44,16 @@ def transform3d(xyzhe) -> np.ndarray:
 def hip_projector(device="cuda:0") -> Callable:
     from .. import ops
 
-    def fn(depth: np.ndarray, T, intr, proj_shift, map_shift, cell, map_w, map_h, order=0) -> np.ndarray:
+    def fn(depth: np.ndarray, T, intr, proj_shift, map_shift, cell, map_w, map_h, order=0, want_xyz: bool = False):
+        """The cell under every pixel, int32 [H, W]; with `want_xyz` the pair of it and the world points float32 [H, W, 3] of the
+        same launch (column 1 is the height)."""
         d = torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(device)
+        if want_xyz:
+            idx, xyz = ops.unproject_grid_index(d, T, intr, proj_shift, map_shift, cell, map_w, map_h, order, want_xyz=True)
+            return idx.cpu().numpy(), xyz.cpu().numpy()
         idx = ops.unproject_grid_index(d, T, intr, proj_shift, map_shift, cell, map_w, map_h, order)
         return idx.cpu().numpy()
+    fn.returns_xyz = True                 # RobotFrontEnd.frame(..., heights=True) asks for this before it passes want_xyz
     return fn
 
 

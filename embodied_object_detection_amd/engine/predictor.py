@@ -150,6 +150,25 @@ class EmbodiedPredictor:
         return self.model.frontiers(object_labels, map_shape=map_shape, since=since, last_seen=last_seen, from_cell=from_cell,
                                     route=route, passable=passable, min_cells=min_cells, topk=topk, rank_by=rank_by)
 
+    def heights(self, data: Dict, band_mm=(100, 1500), exclude_cell: int = -1):
+        """Record how high the things under the camera stand in the frame `data` (the dict the predictor was called with, made with
+        `RobotFrontEnd.frame(..., heights=True)`): `CustomRCNNRecurrent.heights` on `data["proj_indices"]` and `data["heights"]`.
+        Returns the height record int32 [4, N].  Nothing the frame computes changes."""
+        if "heights" not in data:
+            from .. import _lib
+            raise _lib.EodError("heights: the frame carries no \"heights\" (RobotFrontEnd.frame(..., heights=True))")
+        return self.model.heights(data["proj_indices"], data["heights"], band_mm=band_mm, exclude_cell=exclude_cell)
+
+    def obstacles(self, object_labels=None, objects=None, map_shape=None, record=None, min_hits: int = 4, min_cells: int = 2,
+                  topk: int = 16) -> Dict:
+        """What stands in the way, from the heights alone, merged with the detected objects: the dict of
+        `CustomRCNNRecurrent.obstacles` (`merged_labels`, `kind`, `structure_labels`, `structure`, `area`, `top_mm`, `obj_top_mm`,
+        `counts`, ...) on the grid `map_shape` = (rows, cols), from the record `heights` keeps (`record` None) or the one given;
+        `route`, `clearance`, `sight` and `frontiers` take `merged_labels` in place of `object_labels`.  The model, its heads and
+        the memory are not changed."""
+        return self.model.obstacles(object_labels, objects, map_shape=map_shape, record=record, min_hits=min_hits, min_cells=min_cells,
+                                    topk=topk)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

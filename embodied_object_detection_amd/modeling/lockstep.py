@@ -41,8 +41,8 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
-from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _clearance, _cover, _describe, _det_stream, _frontiers, _instances,
-                        _map_inventory, _map_regions, _observed, _place, _relations, _result_sets, _route, _sched_streams,
+from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _clearance, _cover, _describe, _det_stream, _frontiers, _heights, _instances,
+                        _map_inventory, _map_regions, _observed, _obstacles, _place, _relations, _result_sets, _route, _sched_streams,
                         _semmap_locate, _semmap_query, _sight, _ticket)
 from .roi_heads import RoiBuffers
 
@@ -84,6 +84,7 @@ class LockstepScenes:
         self.observations: Optional[torch.Tensor] = None        # [B,N]
         self._last_seen: Optional[torch.Tensor] = None          # [B,N] int32: the stamp of the last `cover` of each cell, -1: none
         self._cover_stamp = [0] * self.B
+        self._height_record: Optional[torch.Tensor] = None      # [B,4,N] int32: the record of `heights`, one row per scene
         self._mem_f16 = self._dirty = None
         self._f16_valid = False
         self._dirty_pending = False
@@ -185,6 +186,9 @@ class LockstepScenes:
         _lib.check(lib.eod_fill_i32(dirty.data_ptr(), 0, dirty.numel(), s), "fill")
         if self._last_seen is not None:
             self._last_seen[b].fill_(-1)
+        if self._height_record is not None:
+            for plane, v in enumerate(ops.HEIGHT_RECORD_INIT):
+                self._height_record[b, plane].fill_(v)
         self._started[b] = True
 
     def invalidate_memory_snapshot(self):
@@ -369,6 +373,47 @@ class LockstepScenes:
                 raise _lib.EodError(f"frontiers: object_labels [N] beside a record of {last_seen.shape[0]} scenes: pass scene=")
             last_seen = last_seen[int(scene)].contiguous()
         return _frontiers(object_labels, map_shape, last_seen, since, from_cell, route, passable, min_cells, topk, rank_by)
+
+    def heights(self, scene: int, proj_indices, heights, band_mm=(100, 1500), exclude_cell: int = -1):
+        """`CustomRCNNRecurrent.heights` for scene `scene`: the record is int32 [B, 4, N], a row per scene, made at the first call
+        and emptied for a scene by its `reset_memory`.  Returns the scene's row [4, N]."""
+        if not 0 <= int(scene) < self.B:
+            raise IndexError(f"scene {scene} of a lock-step batch of {self.B}")
+        if self.implicit_memory is None:
+            raise _lib.EodError("heights: no memory yet (no frame has run)")
+        b, n_cells = int(scene), int(self.implicit_memory.shape[1])
+        if self._height_record is None or self._height_record.shape[2] != n_cells:
+            self._height_record = torch.stack([ops.new_height_record(n_cells, self.device) for _ in range(self.B)])
+        return _heights(self.model, proj_indices, heights, self._height_record[b], n_cells, band_mm, exclude_cell)
+
+    def obstacles(self, object_labels=None, objects=None, map_shape=None, record=None, min_hits: int = 4, min_cells: int = 2,
+                  topk: int = 16, scene: Optional[int] = None):
+        """`CustomRCNNRecurrent.obstacles` (`merged_labels`, `kind`, ...); `record` None takes the [B, 4, N] record `heights` keeps.  With the `[B, N]`
+        object_labels (and `[B, K]` objects) of `inventory(None, ...)`, or with neither and no `scene`, the op runs once per scene
+        and every entry of the dict gains a leading [B].  With object_labels [N] or None, `scene` picks the scene whose record to
+        take.  Nothing of the batch model changes."""
+        if record is None:
+            record = self._height_record
+        if record is None:
+            raise _lib.EodError("obstacles: no height record: call heights(scene, proj_indices, heights) on every frame, or pass record")
+        batched = isinstance(object_labels, torch.Tensor) and object_labels.dim() == 2
+        if batched or (object_labels is None and scene is None and isinstance(record, torch.Tensor) and record.dim() == 3):
+            if not isinstance(record, torch.Tensor) or record.dim() != 3 or (batched and record.shape[0] != object_labels.shape[0]):
+                raise _lib.EodError(f"obstacles: record {tuple(getattr(record, 'shape', ()))}: expected [B, 4, N] beside object_labels "
+                                    f"{tuple(getattr(object_labels, 'shape', ()))}")
+            B = int(record.shape[0])
+            if objects is not None:
+                objects = torch.as_tensor(objects, dtype=torch.int32, device=record.device)
+                if objects.dim() != 2 or objects.shape[0] != B:
+                    raise _lib.EodError(f"obstacles: objects {tuple(objects.shape)}: expected [B, K] for the {B} scenes")
+            per = [_obstacles(record[b], map_shape, object_labels[b].contiguous() if batched else None,
+                              None if objects is None else objects[b].contiguous(), min_hits, min_cells, topk) for b in range(B)]
+            return {k: torch.stack([p[k] for p in per]) for k in per[0]}
+        if isinstance(record, torch.Tensor) and record.dim() == 3:
+            if scene is None or not 0 <= int(scene) < record.shape[0]:
+                raise _lib.EodError(f"obstacles: object_labels [N] beside a record of {record.shape[0]} scenes: pass scene=")
+            record = record[int(scene)]
+        return _obstacles(record, map_shape, object_labels, objects, min_hits, min_cells, topk)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

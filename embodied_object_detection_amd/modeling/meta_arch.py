@@ -247,6 +247,49 @@ def _frontiers(object_labels, map_shape, last_seen, since=0, from_cell=None, rou
     return res
 
 
+def _device_heights(heights, device):
+    """The heights of a frame's pixels (numpy or tensor; [H, W], [H, W, 1] or xyz [H, W, 3]) as contiguous float32 on the device."""
+    h = heights
+    if not torch.is_tensor(h):
+        h = torch.from_numpy(np.ascontiguousarray(h))
+    if h.dim() == 3 and h.shape[2] == 1:
+        h = h.squeeze(2)
+    if h.dtype != torch.float32:
+        h = h.to(torch.float32)
+    return h.to(device, non_blocking=True).contiguous()
+
+
+def _heights(model, proj_indices, heights, record, n_cells, band_mm, exclude_cell):
+    """`heights` on one scene: `ops.map_heights` into `record` (None: a new one of `ops.new_height_record`).  Returns the record."""
+    if heights is None:
+        raise _lib.EodError("heights: the frame carries no heights (RobotFrontEnd.frame(..., heights=True), or the xyz of "
+                            "ops.unproject_grid_index(..., want_xyz=True))")
+    proj = model._device_proj({"proj_indices": proj_indices})
+    if record is None:
+        record = ops.new_height_record(int(n_cells), proj.device)
+    return ops.map_heights(proj, _device_heights(heights, proj.device), record, band_mm=band_mm, exclude_cell=exclude_cell)
+
+
+def _obstacles(record, map_shape, object_labels=None, objects=None, min_hits=4, min_cells=2, topk=16):
+    """`obstacles` on one record: `ops.map_obstacles` on the grid `map_shape`.  Reads no model and no memory."""
+    if map_shape is None:
+        raise _lib.EodError("obstacles: map_shape (rows, cols) is required: the neighbours are those of the grid")
+    if record is None:
+        raise _lib.EodError("obstacles: no height record: call heights(proj_indices, heights) on every frame, or pass record")
+    rows, cols = int(map_shape[0]), int(map_shape[1])
+    if not isinstance(record, torch.Tensor) or record.dim() != 2 or rows < 1 or cols < 1 or rows * cols != record.shape[1]:
+        raise _lib.EodError(f"obstacles: map_shape {tuple(map_shape)} does not hold the cells of the record "
+                            f"{tuple(getattr(record, 'shape', ()))}")
+    if not record.is_cuda:
+        raise _lib.EodError("obstacles: record on the host (no CPU fallback)")
+    res = ops.map_obstacles(record, cols, object_labels=object_labels, objects=objects, min_hits=min_hits, min_cells=min_cells,
+                            topk=topk)
+    status = int(res["status"][0])                                   # the results are handed over here
+    if status != 0:
+        raise _lib.EodError(f"obstacles: a bounded loop of eod_map_obstacles reached its bound (status {status}); the result is void")
+    return res
+
+
 def _observed(observations):
     """The weaker record where `cover` never ran: 0 where the memory was written, -1 elsewhere."""
     return torch.where(observations > 0, 0, -1).to(torch.int32)
@@ -507,6 +550,7 @@ class CustomRCNNRecurrent:
         self.semmap = None
         self._last_seen: Optional[torch.Tensor] = None        # [N] int32: the stamp of the last `cover` of each cell, -1: none
         self._cover_stamp = 0
+        self._height_record: Optional[torch.Tensor] = None    # [4,N] int32: hits, band_hits, h_min_mm, h_max_mm of `heights`
         self._mem_f16: Optional[torch.Tensor] = None
         self._dirty: Optional[torch.Tensor] = None          # int32 [N]: rows of the fp16 snapshot that are out of date
         self._f16_valid = False
@@ -561,6 +605,7 @@ class CustomRCNNRecurrent:
         self._dirty_pending = False
         self.semmap = None
         self._last_seen = None
+        self._height_record = None
 
     def invalidate_memory_snapshot(self):
         """Call after writing `implicit_memory` / `observations` from outside (e.g. a loaded snapshot): the next frame
@@ -1090,7 +1135,8 @@ class CustomRCNNRecurrent:
         robot's body in cells (`RobotFrontEnd.body_radius2`); the call then runs `clearance(radius2=body_radius2,
         keep_cell=from_cell, passable=passable)` first and routes on its `inflated` labels, and the dict gains `clearance_d2` and
         `inflated_labels` [N].  Every object is then grown by the radius: `goal_cell` lies on the rim of the inflated object, where
-        the body's centre may stand, and `cells` counts the inflated cells.  Reads neither the model nor the memory."""
+        the body's centre may stand, and `cells` counts the inflated cells.  Reads neither the model nor the memory.  See also
+        `obstacles`: `model.route(inv["object"], obs["merged_labels"], ...)` goes round the walls the heights show as well."""
         return _route(objects, object_labels, map_shape, from_cell, passable, path_max, sweeps, body_radius2)
 
     def clearance(self, objects, object_labels, map_shape=None, radius2: int = 0, keep_cell: Optional[int] = None, passable=None) -> dict:
@@ -1104,7 +1150,8 @@ class CustomRCNNRecurrent:
         pass `body_radius2` there.  Per object `cells`, `territory` (the free cells nearest to it), and `widest_cell` / `widest_d2`:
         the most open cell of its territory (`sight` says whether the object is in view from it); `open_key`: the most open cell of the map;
         `counts`: blocked, free and inflated cells.  Metres: `RobotFrontEnd.clearance_metres`.  The status is read here.  Reads
-        neither the model nor the memory."""
+        neither the model nor the memory.  See also `obstacles`: `model.clearance(inv["object"], obs["merged_labels"], ...)`
+        measures the room between the walls the heights show as well."""
         return _clearance(objects, object_labels, map_shape, radius2, keep_cell, passable)
 
     def sight(self, objects, object_labels, map_shape=None, from_cells=None, range2: Optional[int] = None, passable=None) -> dict:
@@ -1128,7 +1175,8 @@ class CustomRCNNRecurrent:
 
         `from_cells` is the one argument the entry point reads on the host (a cell outside the map is refused before any launch):
         a device tensor, as in the lines above, is copied there first, one synchronisation; a sequence of ints costs none.  Never
-        hand `eod_map_sight` itself a device pointer for it.  The status is read here.  Reads neither the model nor the memory."""
+        hand `eod_map_sight` itself a device pointer for it.  The status is read here.  Reads neither the model nor the memory.  See
+        also `obstacles`: `model.sight(inv["object"], obs["merged_labels"], ...)` stops at the walls the heights show as well."""
         return _sight(objects, object_labels, map_shape, from_cells, range2, passable)
 
     def cover(self, proj_indices, stamp: Optional[int] = None, exclude_cell: int = -1) -> torch.Tensor:
@@ -1170,12 +1218,47 @@ class CustomRCNNRecurrent:
         `observations > 0` as 0 / -1, a weaker record: the memory counts a cell only where a proposal's mask covered a pixel that
         landed in it, so bare floor and walls the camera saw without proposing anything there stay UNKNOWN, and the frontiers lie
         round the detected objects rather than at the edge of the view.  Raises when `status` is not 0.  Changes nothing of the
-        model."""
+        model.  See also `obstacles`: `model.frontiers(obs["merged_labels"], ...)` takes a cell a wall's pixels covered as BLOCKED."""
         if last_seen is None:
             last_seen = self._last_seen
             if last_seen is None and self.observations is not None:
                 last_seen = _observed(self.observations)
         return _frontiers(object_labels, map_shape, last_seen, since, from_cell, route, passable, min_cells, topk, rank_by)
+
+    def heights(self, proj_indices, heights, band_mm=(100, 1500), exclude_cell: int = -1) -> torch.Tensor:
+        """Record how high the things under the camera stand: every pixel of the frame's `proj_indices` (numpy or tensor, [H, W]
+        or [H, W, 1]) brings its world height `heights` (float32 metres, [H, W], or the xyz [H, W, 3] of the projector, whose y is
+        read in place; `frame["heights"]` of `RobotFrontEnd.frame(..., heights=True)`) to its cell of the height record int32
+        [4, N], which is returned: hits, band_hits (the pixels with `band_mm[0]` <= millimetres <= `band_mm[1]`: the band a body
+        takes, `RobotFrontEnd.height_band_mm`), h_min_mm, h_max_mm.  The cells outside the map, `exclude_cell` (the robot's own,
+        where zero-depth pixels land) and heights that are not finite or beyond 1000 m are dropped.  The record is made at the first
+        call after a `reset_memory` and dropped by the next one.  One launch of `ops.map_heights`; the frame itself never calls it,
+        and nothing it computes changes."""
+        if self.implicit_memory is None:
+            raise _lib.EodError("heights: no memory yet (no frame has run)")
+        self._height_record = _heights(self, proj_indices, heights, self._height_record, int(self.implicit_memory.shape[0]), band_mm,
+                                       exclude_cell)
+        return self._height_record
+
+    def obstacles(self, object_labels=None, objects=None, map_shape=None, record=None, min_hits: int = 4, min_cells: int = 2,
+                  topk: int = 16) -> dict:
+        """What stands in the way, whether the vocabulary has a word for it or not: the dict of `ops.map_obstacles` for the height
+        record `heights` keeps (`record` None) or the one given, on the grid `map_shape` = (rows, cols), which is required.  A
+        cell is an OBSTACLE where at least `min_hits` pixels of the band landed; obstacle cells that touch (8 neighbours) form a
+        structure (a wall, a cupboard), one of fewer than `min_cells` cells is dropped as noise.  `merged_labels` int32 [N] holds
+        the labels of `object_labels` (None, or `inv["object_labels"]` of `inventory`) and, beside them, the structures' labels:
+        the label map the other queries take as it stands,
+
+            model.heights(data["proj_indices"], data["heights"], exclude_cell=front.exclude_cell(pose))     # after every frame
+            obs = model.obstacles(inv["object_labels"], inv["object"], shape)
+            rt = model.route(inv["object"], obs["merged_labels"], shape, from_cell=here)                    # round the walls
+
+        and `clearance`, `sight` and `frontiers` alike.  Per cell also `kind` (0 UNSEEN, 1 CLEAR, 2 OBSTACLE, 3 OBJECT) and
+        `structure_labels`; per structure `structure`, `area`, `bbox`, `sum_rc` (`RobotFrontEnd.region_centroids`), `top_mm`; per
+        slot of `objects` (`inv["object"]`) `obj_cells`, `obj_seen_cells`, `obj_top_mm`, `obj_base_mm`: how high the table is;
+        `count`, `counts`.  Raises when `status` is not 0.  Changes nothing of the model."""
+        return _obstacles(self._height_record if record is None else record, map_shape, object_labels, objects, min_hits, min_cells,
+                          topk)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

@@ -2291,3 +2291,155 @@ def map_frontier(object_labels: torch.Tensor, last_seen: torch.Tensor, cols: int
             "open_edges": part["open_edges"], "behind_key": behind_key, "behind_area": part["behind_area"],
             "behind_label": part["behind_label"], "reach_key": reach_key, "reach_cost": part["reach_cost"],
             "reach_cell": part["reach_cell"], "counts": part["counts"], "status": part["status"]}
+
+
+OBSTACLES_K_MAX, OBSTACLES_TOPK_MAX, OBSTACLES_N_MAX, OBSTACLES_DIM_MAX, OBSTACLES_PIXELS_MAX, OBSTACLES_BAND_MAX = (
+    64, 64, 1 << 22, 32767, 1 << 24, 1000000)
+OBSTACLES_KINDS = {"unseen": 0, "clear": 1, "obstacle": 2, "object": 3}       # the values of `kind`
+HEIGHT_RECORD_INIT = (0, 0, 2 ** 31 - 1, -2 ** 31)                             # hits, band_hits, h_min_mm, h_max_mm of an empty record
+
+
+def new_height_record(n_cells: int, device) -> torch.Tensor:
+    """An empty record for `map_heights`: int32 [4, N], the planes hits, band_hits, h_min_mm, h_max_mm holding 0, 0, INT_MAX,
+    INT_MIN."""
+    if not _whole(n_cells) or not 1 <= int(n_cells) <= OBSTACLES_N_MAX:
+        raise _lib.EodError(f"new_height_record: n_cells {n_cells} outside 1..{OBSTACLES_N_MAX}")
+    record = torch.empty((4, int(n_cells)), dtype=torch.int32, device=device)
+    for plane, v in enumerate(HEIGHT_RECORD_INIT):
+        record[plane].fill_(v)
+    return record
+
+
+def _check_height_record(what: str, record, device=None) -> int:
+    if (not isinstance(record, torch.Tensor) or record.dim() != 2 or record.shape[0] != 4 or record.dtype != torch.int32
+            or not record.is_contiguous() or (device is not None and record.device != device)):
+        raise _lib.EodError(f"{what}: record {_describe_what(record)}: expected contiguous int32 [4, N] (new_height_record)"
+                            + (" on the pixels' device" if device is not None else ""))
+    N = int(record.shape[1])
+    if not 1 <= N <= OBSTACLES_N_MAX:
+        raise _lib.EodError(f"{what}: record: N {N} outside 1..{OBSTACLES_N_MAX}")
+    return N
+
+
+def map_heights(proj_indices: torch.Tensor, heights: torch.Tensor, record: torch.Tensor, band_mm=(100, 1500),
+                exclude_cell: int = -1) -> torch.Tensor:
+    """The per-cell record of the heights the pixels of a frame brought (eod_map_heights; include/eod_obstacles.h), in place.
+    `proj_indices` int32, any shape, contiguous: the cell under each pixel.  `heights` float32, contiguous: the world y of each
+    pixel in metres, either of the pixels' shape or `xyz` of shape [..., 3] (`unproject_grid_index(..., want_xyz=True)`), whose
+    column 1 is then read with stride 3 and without a copy.  A pixel counts when its cell c has 0 <= c < N and c !=
+    `exclude_cell` and its height is finite with |y| <= 1000; it then has q = rint(float32(y) * float32(1000)) millimetres and
+    does hits[c] += 1, band_hits[c] += (band_mm[0] <= q <= band_mm[1]), h_min_mm[c] = min(.., q), h_max_mm[c] = max(.., q) on the
+    planes of `record` int32 [4, N] (`new_height_record`).  `band_mm`: two ints, lo <= hi, within +-1 000 000
+    (`RobotFrontEnd.height_band_mm`).  One launch, integer atomics only: the record depends neither on the order of the pixels or of
+    the frames nor on how the pixels are split over calls.  Returns `record`."""
+    if not isinstance(proj_indices, torch.Tensor) or proj_indices.dtype != torch.int32 or not proj_indices.is_contiguous():
+        raise _lib.EodError(f"map_heights: proj_indices {_describe_what(proj_indices)}: expected contiguous int32")
+    dev = proj_indices.device
+    P = int(proj_indices.numel())
+    if (not isinstance(heights, torch.Tensor) or heights.dtype != torch.float32 or not heights.is_contiguous() or heights.device != dev
+            or (heights.numel() != P and (heights.dim() < 1 or heights.shape[-1] != 3 or heights.numel() != 3 * P))):
+        raise _lib.EodError(f"map_heights: heights {_describe_what(heights)}: expected contiguous float32 with one value a pixel "
+                            f"({P}) or xyz [..., 3], on the pixels' device")
+    xyz = heights.numel() != P or (P == 0 and heights.dim() >= 1 and heights.shape[-1] == 3)
+    N = _check_height_record("map_heights", record, dev)
+    if P > OBSTACLES_PIXELS_MAX:
+        raise _lib.EodError(f"map_heights: proj_indices: {P} pixels (at most {OBSTACLES_PIXELS_MAX})")
+    try:
+        lo, hi = band_mm
+    except (TypeError, ValueError):
+        lo = hi = None
+    if not _whole(lo) or not _whole(hi) or not -OBSTACLES_BAND_MAX <= int(lo) <= int(hi) <= OBSTACLES_BAND_MAX:
+        raise _lib.EodError(f"map_heights: band_mm {band_mm!r}: expected two ints lo <= hi within +-{OBSTACLES_BAND_MAX}")
+    if not _whole(exclude_cell) or not -2 ** 31 <= int(exclude_cell) <= 2 ** 31 - 1:
+        raise _lib.EodError(f"map_heights: exclude_cell {exclude_cell}: expected an int (-1: none)")
+    if not record.is_cuda:
+        raise _lib.EodError("map_heights: record on the host (no CPU fallback)")
+    at = (heights.data_ptr() + (4 if xyz else 0)) if P else None
+    check(_lib.load().eod_map_heights(proj_indices.data_ptr() if P else None, at, 3 if xyz else 1, P, N, int(lo), int(hi),
+                                      int(exclude_cell), record[0].data_ptr(), record[1].data_ptr(), record[2].data_ptr(),
+                                      record[3].data_ptr(), _stream()), "eod_map_heights")
+    return record
+
+
+def map_obstacles_workspace(N: int, cols: int) -> int:
+    """int32 words of a `map_obstacles` workspace (eod_map_obstacles_workspace_bytes / 4)."""
+    need = int(_lib.load().eod_map_obstacles_workspace_bytes(int(N), int(cols)))
+    if need == 0:
+        raise _lib.EodError(f"map_obstacles_workspace: N {N}, cols {cols}")
+    return need // 4
+
+
+def map_obstacles(record: torch.Tensor, cols: int, object_labels: Optional[torch.Tensor] = None, objects=None, min_hits: int = 4,
+                  min_cells: int = 2, topk: int = 16, workspace: Optional[torch.Tensor] = None) -> dict:
+    """Which cells something stands in, from the heights alone, merged with the detected objects (eod_map_obstacles; the semantics
+    are those of include/eod_obstacles.h).  `record` int32 [4, N] of `map_heights`, cell i = r * cols + c.  A cell's `kind` (uint8
+    [N]) is OBJECT 3 where `object_labels` (None or int32 [N]) is >= 0, else OBSTACLE 2 where band_hits >= `min_hits`, else CLEAR 1
+    where hits > 0, else UNSEEN 0.  A structure is an 8-connected component of OBSTACLE cells, its label its lowest cell; one of
+    fewer than `min_cells` cells is a speck.  Per cell `structure_labels` (specks included, -1 elsewhere) and `merged_labels`
+    int32 [N]: the object's label, or the label of a structure that is no speck, or -1: the label map `map_route`,
+    `map_clearance`, `map_sight` and `map_frontier` take as it stands.  `count` [1]: the structures of at least `min_cells` cells;
+    for the `topk` (1..64) largest, `structure` (the label; -1 in a padding slot), `area`, `bbox` [K, 4], `sum_rc` int64 [K, 2],
+    `top_mm` (the highest point, INT_MIN in a padding slot).  Per slot of `objects` (None, int32 [K_obj], K_obj <= 64, or a
+    sequence; a cell belongs to the lowest slot that holds its label): `obj_cells`, `obj_seen_cells` (those with hits > 0),
+    `obj_top_mm` and `obj_base_mm` over the seen ones (INT_MIN / INT_MAX if none).  `counts` int32 [6]: UNSEEN, CLEAR, OBSTACLE and
+    OBJECT cells, structures (specks included), speck cells; `status` int32 [2] (bit 1 of status[0]: a bounded loop reached its
+    bound), which is not read here.  `workspace`: int32, 8-byte aligned, at least `map_obstacles_workspace(N, cols)` words, any
+    contents.  Integer comparisons, additions and atomics only: the same bits on every call; `record` is not written."""
+    N = _check_height_record("map_obstacles", record)
+    dev = record.device
+    if not _whole(cols) or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_obstacles: cols {cols} does not divide the {N} cells")
+    if int(cols) > OBSTACLES_DIM_MAX or N // int(cols) > OBSTACLES_DIM_MAX:
+        raise _lib.EodError(f"map_obstacles: cols {cols}: {N // int(cols)} rows x {cols} columns, more than {OBSTACLES_DIM_MAX} one way")
+    if object_labels is not None and (not isinstance(object_labels, torch.Tensor) or object_labels.shape != (N,)
+                                      or object_labels.dtype != torch.int32 or not object_labels.is_contiguous()
+                                      or object_labels.device != dev):
+        raise _lib.EodError(f"map_obstacles: object_labels {_describe_what(object_labels)}: expected None or contiguous int32 [{N}] on "
+                            "the record's device")
+    if objects is not None and not isinstance(objects, torch.Tensor):
+        try:
+            objects = torch.as_tensor(np.asarray(list(objects), dtype=np.int64).astype(np.int32).reshape(-1), device=dev)
+        except (TypeError, ValueError, OverflowError):
+            raise _lib.EodError(f"map_obstacles: objects {type(objects).__name__}: expected None, int32 [K_obj] or a sequence of "
+                                "labels") from None
+    if objects is not None and (objects.dim() != 1 or objects.dtype != torch.int32 or not objects.is_contiguous()
+                                or objects.device != dev or objects.shape[0] > OBSTACLES_K_MAX):
+        raise _lib.EodError(f"map_obstacles: objects {_describe_what(objects)}: expected contiguous int32 [K_obj], K_obj <= "
+                            f"{OBSTACLES_K_MAX}, on the record's device")
+    for name, v in (("min_hits", min_hits), ("min_cells", min_cells)):
+        if not _whole(v) or not 1 <= int(v) <= 2 ** 31 - 1:
+            raise _lib.EodError(f"map_obstacles: {name} {v}: expected at least 1")
+    if not _whole(topk) or not 1 <= int(topk) <= OBSTACLES_TOPK_MAX:
+        raise _lib.EodError(f"map_obstacles: topk {topk} outside 1..{OBSTACLES_TOPK_MAX}")
+    if not record.is_cuda:
+        raise _lib.EodError("map_obstacles: record on the host (no CPU fallback)")
+    need = map_obstacles_workspace(N, int(cols))
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev
+                                  or workspace.data_ptr() % 8 != 0):
+        raise _lib.EodError(f"map_obstacles: workspace: expected {need} contiguous, 8-byte aligned int32 on the record's device")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+    K, Ko = int(topk), 0 if objects is None else int(objects.shape[0])
+    kind = torch.empty((N,), dtype=torch.uint8, device=dev)
+    cells = torch.empty((2, N), dtype=torch.int32, device=dev)        # structure_labels, merged_labels
+    sum_rc = torch.empty((K, 2), dtype=torch.int64, device=dev)
+    out = torch.empty((7 * K + 4 * Ko + 9,), dtype=torch.int32, device=dev)
+    part = {}
+    at = 0
+    for name, n, shape in (("count", 1, (1,)), ("structure", K, (K,)), ("area", K, (K,)), ("bbox", 4 * K, (K, 4)), ("top_mm", K, (K,)),
+                           ("obj_cells", Ko, (Ko,)), ("obj_seen_cells", Ko, (Ko,)), ("obj_top_mm", Ko, (Ko,)),
+                           ("obj_base_mm", Ko, (Ko,)), ("counts", 6, (6,)), ("status", 2, (2,))):
+        part[name] = out[at:at + n].view(shape)
+        at += n
+    obj = lambda name: part[name].data_ptr() if Ko else None
+    check(_lib.load().eod_map_obstacles(
+        record[0].data_ptr(), record[1].data_ptr(), record[2].data_ptr(), record[3].data_ptr(), _ptr(object_labels),
+        objects.data_ptr() if Ko else None, N, int(cols), Ko, int(min_hits), int(min_cells), K, kind.data_ptr(), cells[0].data_ptr(),
+        cells[1].data_ptr(), part["count"].data_ptr(), part["structure"].data_ptr(), part["area"].data_ptr(), part["bbox"].data_ptr(),
+        sum_rc.data_ptr(), part["top_mm"].data_ptr(), obj("obj_cells"), obj("obj_seen_cells"), obj("obj_top_mm"), obj("obj_base_mm"),
+        part["counts"].data_ptr(), part["status"].data_ptr(), workspace.data_ptr(), workspace.numel() * 4, _stream()), "eod_map_obstacles")
+    return {"kind": kind, "structure_labels": cells[0], "merged_labels": cells[1], "count": part["count"],
+            "structure": part["structure"], "area": part["area"], "bbox": part["bbox"], "sum_rc": sum_rc, "top_mm": part["top_mm"],
+            "obj_cells": part["obj_cells"], "obj_seen_cells": part["obj_seen_cells"], "obj_top_mm": part["obj_top_mm"],
+            "obj_base_mm": part["obj_base_mm"], "counts": part["counts"], "status": part["status"]}
