@@ -301,6 +301,12 @@ OBSTACLES_SIGNATURES = {
     "eod_map_obstacles": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p] * 16 + [C.c_size_t, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/eod_rooms.h declares (the free space split at its doorways, the objects by room)
+ROOMS_SIGNATURES = {
+    "eod_map_rooms_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    "eod_map_rooms": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p] * 22 + [C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -316,7 +322,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **PLACE_SIGNATURES, **REGIONS_SIGNATURES, **INVENTORY_SIGNATURES,
                               **DESCRIBE_SIGNATURES, **RELATIONS_SIGNATURES, **ROUTE_SIGNATURES, **CLEARANCE_SIGNATURES,
-                              **SIGHT_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLES_SIGNATURES}.items():
+                              **SIGHT_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLES_SIGNATURES, **ROOMS_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libeod_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_fp32.hip", "conv_pointwise.hip", "conv_bf16x3.hip", "conv_f16.hip", "elementwise.hip", "roi_align.hip", "select.hip", "heads.hip", "memory.hip", "semmap.hip", "place.hip", "regions.hip", "inventory.hip", "memory_read.hip", "memory_backward.hip", "conv_wgrad.hip", "train_losses.hip", "describe.hip", "relations.hip", "route.hip", "clearance.hip", "sight.hip", "frontier.hip", "obstacles.hip"]
+SOURCES = ["conv_igemm.hip", "conv_fp32.hip", "conv_pointwise.hip", "conv_bf16x3.hip", "conv_f16.hip", "elementwise.hip", "roi_align.hip", "select.hip", "heads.hip", "memory.hip", "semmap.hip", "place.hip", "regions.hip", "inventory.hip", "memory_read.hip", "memory_backward.hip", "conv_wgrad.hip", "train_losses.hip", "describe.hip", "relations.hip", "route.hip", "clearance.hip", "sight.hip", "frontier.hip", "obstacles.hip", "rooms.hip"]
 ARCH = "gfx950"
 
 
@@ -19,7 +19,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("eod_hip.h", "eod_place.h", "eod_regions.h", "eod_inventory.h", "eod_describe.h", "eod_relations.h", "eod_route.h", "eod_clearance.h", "eod_sight.h", "eod_frontier.h", "eod_obstacles.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("eod_hip.h", "eod_place.h", "eod_regions.h", "eod_inventory.h", "eod_describe.h", "eod_relations.h", "eod_route.h", "eod_clearance.h", "eod_sight.h", "eod_frontier.h", "eod_obstacles.h", "eod_rooms.h")]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

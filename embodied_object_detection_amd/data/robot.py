@@ -151,6 +151,12 @@ class RobotFrontEnd:
         squared and rounded down (1e-9 keeps a radius that is a whole number of cells from falling short by rounding)."""
         return int(np.floor((float(metres) / self.res) ** 2 + 1e-9))
 
+    def door_r2(self, width_m: float) -> int:
+        """The `door_r2` of `rooms` for doorways up to `width_m` metres wide: half the width in cells, squared and rounded down, as
+        `body_radius2` rounds.  A free cell at most that far (squared) from a wall is no core of a room, so an opening up to
+        about that wide divides two rooms and a wider one joins them."""
+        return int(np.floor((float(width_m) / (2.0 * self.res)) ** 2 + 1e-9))
+
     def sight_range2(self, metres: float) -> int:
         """The `range2` of `sight` for a sensor that reaches `metres`: the range in cells, squared and rounded down, as
         `body_radius2` rounds, and INT_MAX (unbounded) from there on.  The `near_d2` of `sight` in metres is

@@ -169,6 +169,15 @@ class EmbodiedPredictor:
         return self.model.obstacles(object_labels, objects, map_shape=map_shape, record=record, min_hits=min_hits, min_cells=min_cells,
                                     topk=topk)
 
+    def rooms(self, labels, objects=None, map_shape=None, door_r2: Optional[int] = None, min_cells: Optional[int] = None,
+              topk: int = 16, passable=None, known=None, clearance=None, sweeps: Optional[int] = None) -> Dict:
+        """The rooms of the map: the dict of `CustomRCNNRecurrent.rooms` (`room_labels`, `grow_dist`, `room`, `area`, `widest_cell`,
+        `door_cell`, `door_d2`, `obj_room`, `obj_room_label`, `counts`, ...) for a label map (`obs["merged_labels"]` of `obstacles`)
+        on the grid `map_shape` = (rows, cols); `describe(rooms["room"], rooms["room_labels"], classifier=<room vocabulary>)` names them.  The
+        model, its heads and the memory are neither read nor changed."""
+        return self.model.rooms(labels, objects, map_shape=map_shape, door_r2=door_r2, min_cells=min_cells, topk=topk,
+                                passable=passable, known=known, clearance=clearance, sweeps=sweeps)
+
     def place(self, instances, data: Dict, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> Dict:
         """Where on the map the detections stand: the dict of `CustomRCNNRecurrent.place` for `instances` (what the call on `data`
         returned under "instances") and `data`, the dict the predictor was called with.  The model is left as it is."""

@@ -42,8 +42,8 @@ import torch
 
 from .. import _lib, ops
 from .meta_arch import (RESULT_SETS, CustomRCNNRecurrent, _clearance, _cover, _describe, _det_stream, _frontiers, _heights, _instances,
-                        _map_inventory, _map_regions, _observed, _obstacles, _place, _relations, _result_sets, _route, _sched_streams,
-                        _semmap_locate, _semmap_query, _sight, _ticket)
+                        _map_inventory, _map_regions, _observed, _obstacles, _place, _relations, _result_sets, _rooms, _rooms_batched, _route,
+                        _sched_streams, _semmap_locate, _semmap_query, _sight, _ticket)
 from .roi_heads import RoiBuffers
 
 PYRAMID_SETS = 3      # the step's own, the one computed ahead, the previous step's (its detection pass may trail)
@@ -414,6 +414,15 @@ class LockstepScenes:
                 raise _lib.EodError(f"obstacles: object_labels [N] beside a record of {record.shape[0]} scenes: pass scene=")
             record = record[int(scene)]
         return _obstacles(record, map_shape, object_labels, objects, min_hits, min_cells, topk)
+
+    def rooms(self, labels, objects=None, map_shape=None, door_r2: Optional[int] = None, min_cells: Optional[int] = None,
+              topk: int = 16, passable=None, known=None, clearance=None, sweeps: Optional[int] = None):
+        """`CustomRCNNRecurrent.rooms` (`room_labels`, `room`, `door_cell`, `obj_room`, ...); with the `[B, N]` labels of
+        `obstacles` (and `[B, K]` objects, `[B, N]` known, and a clearance whose `d2` is [B, N]) the op runs once per scene and
+        every entry of the dict gains a leading [B].  Nothing of the batch model changes."""
+        if isinstance(labels, torch.Tensor) and labels.dim() == 2:
+            return _rooms_batched("rooms", labels, objects, map_shape, door_r2, min_cells, topk, passable, known, clearance, sweeps)
+        return _rooms(labels, objects, map_shape, door_r2, min_cells, topk, passable, known, clearance, sweeps)
 
     def place(self, scene: int, instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False):
         """`CustomRCNNRecurrent.place` with scene `scene`'s cell count.  Nothing of the batch model changes."""

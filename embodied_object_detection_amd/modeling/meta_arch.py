@@ -290,6 +290,62 @@ def _obstacles(record, map_shape, object_labels=None, objects=None, min_hits=4, 
     return res
 
 
+def _rooms(labels, objects, map_shape, door_r2, min_cells, topk=16, passable=None, known=None, clearance=None, sweeps=None):
+    """`rooms` on one label map: `ops.map_rooms` on the grid `map_shape`, after `ops.map_clearance` unless `clearance` brings its
+    `d2`; run again with twice the sweeps while they run out.  Reads no model and no memory."""
+    if map_shape is None:
+        raise _lib.EodError("rooms: map_shape (rows, cols) is required: the neighbours are those of the grid")
+    rows, cols = int(map_shape[0]), int(map_shape[1])
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or rows < 1 or cols < 1 or rows * cols != labels.shape[0]:
+        raise _lib.EodError(f"rooms: map_shape {tuple(map_shape)} does not hold the {tuple(getattr(labels, 'shape', ()))} cells of labels")
+    if door_r2 is None or min_cells is None:
+        raise _lib.EodError("rooms: door_r2 and min_cells are required: the squared half-width in cells of the widest gap that still "
+                            "counts as a doorway (RobotFrontEnd.door_r2) and the fewest core cells of a room")
+    if not labels.is_cuda:
+        raise _lib.EodError("rooms: labels on the host (no CPU fallback)")
+    if objects is not None and not isinstance(objects, torch.Tensor):
+        objects = torch.as_tensor(objects, dtype=torch.int32, device=labels.device).reshape(-1)
+    if passable is not None and not isinstance(passable, torch.Tensor):
+        passable = torch.as_tensor(passable, dtype=torch.int32, device=labels.device).reshape(-1)
+    if clearance is None:
+        slots = objects if objects is not None and objects.numel() > 0 else torch.full((1,), -1, dtype=torch.int32, device=labels.device)
+        clearance = _clearance(slots, labels, map_shape, 0, None, passable)
+    d2 = clearance["d2"] if isinstance(clearance, dict) else clearance
+    n = ops.map_route_sweeps(rows, cols) if sweeps is None else int(sweeps)
+    for _ in range(ops.ROUTE_RESUMES + 1):
+        res = ops.map_rooms(labels, d2, cols, door_r2, min_cells=min_cells, topk=topk, objects=objects, passable=passable, known=known,
+                            sweeps=n)
+        status = int(res["status"][0])                               # the results are handed over here
+        if status != 1 or n >= ops.ROOMS_SWEEPS_MAX:
+            break
+        n = min(2 * n, ops.ROOMS_SWEEPS_MAX)
+    if status & 2:
+        raise _lib.EodError(f"rooms: a bounded loop of eod_map_rooms reached its bound (status {status}); the result is void")
+    if status != 0:
+        raise _lib.EodError(f"rooms: the keys had not settled after {n} sweeps (status {status}); the result is void")
+    res = dict(res)
+    res["clearance_d2"] = d2
+    return res
+
+
+def _rooms_batched(what, labels, objects, map_shape, door_r2, min_cells, topk, passable, known, clearance, sweeps):
+    """The `[B, N]` form of `rooms` of the lock-step batch: one call per scene, every entry gaining a leading [B]."""
+    B = int(labels.shape[0])
+    if objects is not None:
+        objects = torch.as_tensor(objects, dtype=torch.int32, device=labels.device)
+        if objects.dim() != 2 or objects.shape[0] != B:
+            raise _lib.EodError(f"{what}: objects {tuple(objects.shape)}: expected [B, K] beside labels {tuple(labels.shape)}")
+    if known is not None and (not isinstance(known, torch.Tensor) or known.dim() != 2 or known.shape[0] != B):
+        raise _lib.EodError(f"{what}: known {tuple(getattr(known, 'shape', ()))}: expected [B, N] beside labels {tuple(labels.shape)}")
+    d2 = clearance["d2"] if isinstance(clearance, dict) else clearance
+    if d2 is not None and (not isinstance(d2, torch.Tensor) or d2.dim() != 2 or d2.shape[0] != B):
+        raise _lib.EodError(f"{what}: clearance {tuple(getattr(d2, 'shape', ()))}: expected d2 [B, N] beside labels {tuple(labels.shape)}")
+    per = [_rooms(labels[b].contiguous(), None if objects is None else objects[b].contiguous(), map_shape, door_r2, min_cells, topk,
+                  passable, None if known is None else known[b].contiguous(), None if d2 is None else d2[b].contiguous(), sweeps)
+           for b in range(B)]
+    return {k: torch.stack([p[k] for p in per]) for k in per[0]}
+
+
 def _observed(observations):
     """The weaker record where `cover` never ran: 0 where the memory was written, -1 elsewhere."""
     return torch.where(observations > 0, 0, -1).to(torch.int32)
@@ -1259,6 +1315,30 @@ class CustomRCNNRecurrent:
         `count`, `counts`.  Raises when `status` is not 0.  Changes nothing of the model."""
         return _obstacles(self._height_record if record is None else record, map_shape, object_labels, objects, min_hits, min_cells,
                           topk)
+
+    def rooms(self, labels, objects=None, map_shape=None, door_r2: Optional[int] = None, min_cells: Optional[int] = None,
+              topk: int = 16, passable=None, known=None, clearance=None, sweeps: Optional[int] = None) -> dict:
+        """The rooms of the map: the dict of `ops.map_rooms` for the label map `labels` int32 [N] (`obs["merged_labels"]` of
+        `obstacles`, so that the walls divide the space) on the grid `map_shape` = (rows, cols); `map_shape`, `door_r2` and
+        `min_cells` are required.  A free cell farther than `door_r2` (squared, in cells; `RobotFrontEnd.door_r2`) from every
+        blocked cell is core; core cells that touch along a row or column form a region, one of at least `min_cells` cells is a
+        room (its label its lowest cell), and every other free cell goes to the room that reaches it first by `route`'s moves.
+        `known` (None, or uint8 [N]: `obs["kind"]`) takes the cells it holds 0 for out of every room.  `clearance`: the dict of
+        `clearance` on the same labels and `passable`, or its `d2`; None: `ops.map_clearance` runs first, as in
+        `route(body_radius2=...)`, and the dict gains `clearance_d2` either way.
+
+            obs = model.obstacles(inv["object_labels"], inv["object"], shape)
+            rooms = model.rooms(obs["merged_labels"], inv["object"], shape, door_r2=front.door_r2(1.0), min_cells=20, known=obs["kind"])
+            rooms["obj_room"][k]                                   # the slot of the room object k stands in: "the chair in the other room"
+            rooms["door_cell"][a, b]                               # the cell of room a in the door to room b (-1: no door)
+            names = model.describe(rooms["room"], rooms["room_labels"], classifier=room_vocabulary)      # "kitchen", "bedroom"
+
+        Per cell `room_labels` and `grow_dist`; per room `room`, `area`, `core_area`, `bbox`, `sum_rc`
+        (`RobotFrontEnd.region_centroids`), `widest_cell` / `widest_d2` (where to stand), `room_objects`; per pair `door_edges`,
+        `door_d2`, `door_cell`; per object `obj_room_cells`, `obj_room`, `obj_room_label`; `count`, `counts`.  `sweeps` None takes
+        `ops.map_route_sweeps`; the status is read here, a call whose sweeps ran out is run again with twice as many, and
+        `EodError` is raised if the keys have not settled by then.  Reads neither the model nor the memory."""
+        return _rooms(labels, objects, map_shape, door_r2, min_cells, topk, passable, known, clearance, sweeps)
 
     def place(self, instances: Instances, proj_indices, topk: int = 4, exclude_cell: int = -1, attach: bool = False) -> dict:
         """Where on the map the detections of a frame stand: for every instance the grid cells under its mask, as

@@ -2443,3 +2443,114 @@ def map_obstacles(record: torch.Tensor, cols: int, object_labels: Optional[torch
             "structure": part["structure"], "area": part["area"], "bbox": part["bbox"], "sum_rc": sum_rc, "top_mm": part["top_mm"],
             "obj_cells": part["obj_cells"], "obj_seen_cells": part["obj_seen_cells"], "obj_top_mm": part["obj_top_mm"],
             "obj_base_mm": part["obj_base_mm"], "counts": part["counts"], "status": part["status"]}
+
+
+ROOMS_K_MAX, ROOMS_P_MAX, ROOMS_TOPK_MAX, ROOMS_N_MAX, ROOMS_DIM_MAX, ROOMS_SWEEPS_MAX = 64, 64, 64, 1 << 22, 32767, 1024
+ROOMS_UNASSIGNED = 2 ** 31 - 1                           # grow_dist of a cell that is in no room
+
+
+def map_rooms_workspace(N: int, cols: int) -> int:
+    """int32 words of a `map_rooms` workspace (eod_map_rooms_workspace_bytes / 4)."""
+    need = int(_lib.load().eod_map_rooms_workspace_bytes(int(N), int(cols)))
+    if need == 0:
+        raise _lib.EodError(f"map_rooms_workspace: N {N}, cols {cols}")
+    return need // 4
+
+
+def map_rooms(labels: torch.Tensor, d2: torch.Tensor, cols: int, door_r2: int, min_cells: int = 1, topk: int = 16, objects=None,
+              passable=None, known: Optional[torch.Tensor] = None, sweeps: Optional[int] = None,
+              workspace: Optional[torch.Tensor] = None) -> dict:
+    """The free space of a label map split at its doorways, and the objects by room (eod_map_rooms; the semantics are those of
+    include/eod_rooms.h).  `labels` int32 [N], cell i = r * cols + c: `obs["merged_labels"]` of `map_obstacles` or any other label
+    map; `d2` int32 [N]: `d2` of `map_clearance` on the same `labels` and `passable` (it is not recomputed here).  A cell is BLOCKED
+    when its label is >= 0 and not one of `passable` (None, or int32 [P], P <= 64, or a sequence), VOID when it is not blocked and
+    `known` (None or uint8 [N]; `obs["kind"]` fits) is 0 there, FREE otherwise.  A free cell with d2 > `door_r2` is CORE; a
+    4-connected region of core cells with at least `min_cells` cells is a room, its label its lowest cell; every free cell goes to
+    the room that reaches it at the smallest cost of `map_route`'s moves (the lowest label on a tie).  Returns per cell
+    `room_labels` (-1: blocked, void, unassigned) and `grow_dist` int32 [N] (0 on a room's core, INT_MAX where unassigned);
+    `count` [1]: the rooms; for the `topk` (1..64) largest by area, `room` (the label; -1 in a padding slot), `area`, `core_area`,
+    `bbox` [K, 4], `sum_rc` int64 [K, 2], `widest_key` int64 [K], `widest_d2`, `widest_cell` (the most open cell: where to stand),
+    `room_objects`; between ranked rooms `door_edges` [K, K], `door_key` int64 [K, K], `door_d2`, `door_cell` [K, K]
+    (`door_cell[a, b]`: the cell of a in the middle of the door to b; -1: none); per slot of `objects` (None, int32 [K_obj],
+    K_obj <= 64, or a sequence; a cell belongs to the lowest slot that holds its label) `obj_room_cells` [K_obj, K] (the cells of
+    room s beside the object), `obj_room` (the slot with the most; -1) and `obj_room_label`; `counts` int32 [6]: blocked, void,
+    free, core cells of rooms, grown cells, unassigned free cells; `status` int32 [2]: status[0] bit 0: the `sweeps` (1..1024;
+    None: `map_route_sweeps`) ran out before the keys had settled, bit 1: a bounded loop reached its bound; it is not read here,
+    so nothing synchronises.  `workspace`: int32, 8-byte aligned, at least `map_rooms_workspace(N, cols)` words, any contents.
+    Integer comparisons, additions and atomics only: at status 0 the same bits on every call."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.dtype != torch.int32 or not labels.is_contiguous():
+        raise _lib.EodError(f"map_rooms: labels {_describe_what(labels)}: expected contiguous int32 [N]")
+    N = int(labels.shape[0])
+    if not 1 <= N <= ROOMS_N_MAX:
+        raise _lib.EodError(f"map_rooms: labels: N {N} outside 1..{ROOMS_N_MAX}")
+    dev = labels.device
+    if (not isinstance(d2, torch.Tensor) or tuple(d2.shape) != (N,) or d2.dtype != torch.int32 or not d2.is_contiguous()
+            or d2.device != dev):
+        raise _lib.EodError(f"map_rooms: d2 {_describe_what(d2)}: expected contiguous int32 [{N}] on the labels' device (the d2 of "
+                            "map_clearance)")
+    if not _whole(cols) or int(cols) < 1 or N % int(cols) != 0:
+        raise _lib.EodError(f"map_rooms: cols {cols} does not divide the {N} cells")
+    if int(cols) > ROOMS_DIM_MAX or N // int(cols) > ROOMS_DIM_MAX:
+        raise _lib.EodError(f"map_rooms: cols {cols}: {N // int(cols)} rows x {cols} columns, more than {ROOMS_DIM_MAX} one way")
+    if not _whole(door_r2) or not 0 <= int(door_r2) <= 2 ** 31 - 1:
+        raise _lib.EodError(f"map_rooms: door_r2 {door_r2}: expected at least 0 (RobotFrontEnd.door_r2)")
+    if not _whole(min_cells) or not 1 <= int(min_cells) <= 2 ** 31 - 1:
+        raise _lib.EodError(f"map_rooms: min_cells {min_cells}: expected at least 1")
+    if not _whole(topk) or not 1 <= int(topk) <= ROOMS_TOPK_MAX:
+        raise _lib.EodError(f"map_rooms: topk {topk} outside 1..{ROOMS_TOPK_MAX}")
+    lists = {}
+    for name, v, cap in (("objects", objects, ROOMS_K_MAX), ("passable", passable, ROOMS_P_MAX)):
+        if v is not None and not isinstance(v, torch.Tensor):
+            try:
+                v = torch.as_tensor(np.asarray(list(v), dtype=np.int64).astype(np.int32).reshape(-1), device=dev)
+            except (TypeError, ValueError, OverflowError):
+                raise _lib.EodError(f"map_rooms: {name} {type(v).__name__}: expected None, int32 [n] or a sequence of labels") from None
+        if v is not None and (v.dim() != 1 or v.dtype != torch.int32 or not v.is_contiguous() or v.device != dev or v.shape[0] > cap):
+            raise _lib.EodError(f"map_rooms: {name} {_describe_what(v)}: expected contiguous int32 [n], n <= {cap}, on the labels' device")
+        lists[name] = v
+    objects, passable = lists["objects"], lists["passable"]
+    if known is not None and (not isinstance(known, torch.Tensor) or tuple(known.shape) != (N,) or known.dtype != torch.uint8
+                              or not known.is_contiguous() or known.device != dev):
+        raise _lib.EodError(f"map_rooms: known {_describe_what(known)}: expected None or contiguous uint8 [{N}] on the labels' device")
+    if sweeps is None:
+        sweeps = map_route_sweeps(N // int(cols), int(cols))
+    if not _whole(sweeps) or not 1 <= int(sweeps) <= ROOMS_SWEEPS_MAX:
+        raise _lib.EodError(f"map_rooms: sweeps {sweeps} outside 1..{ROOMS_SWEEPS_MAX}")
+    if not labels.is_cuda:
+        raise _lib.EodError("map_rooms: labels on the host (no CPU fallback)")
+    need = map_rooms_workspace(N, int(cols))
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1
+                                  or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev
+                                  or workspace.data_ptr() % 8 != 0):
+        raise _lib.EodError(f"map_rooms: workspace: expected {need} contiguous, 8-byte aligned int32 on the labels' device")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.int32, device=dev)
+    K = int(topk)
+    Ko, P = 0 if objects is None else int(objects.shape[0]), 0 if passable is None else int(passable.shape[0])
+    cells = torch.empty((2, N), dtype=torch.int32, device=dev)        # room_labels, grow_dist
+    wide = torch.empty((3 * K + K * K,), dtype=torch.int64, device=dev)
+    sum_rc, widest_key, door_key = wide[:2 * K].view(K, 2), wide[2 * K:3 * K], wide[3 * K:].view(K, K)
+    out = torch.empty((10 * K + 3 * K * K + Ko * K + 2 * Ko + 9,), dtype=torch.int32, device=dev)
+    part = {}
+    at = 0
+    for name, n, shape in (("count", 1, (1,)), ("room", K, (K,)), ("area", K, (K,)), ("core_area", K, (K,)), ("bbox", 4 * K, (K, 4)),
+                           ("widest_d2", K, (K,)), ("widest_cell", K, (K,)), ("room_objects", K, (K,)), ("door_edges", K * K, (K, K)),
+                           ("door_d2", K * K, (K, K)), ("door_cell", K * K, (K, K)), ("obj_room_cells", Ko * K, (Ko, K)),
+                           ("obj_room", Ko, (Ko,)), ("obj_room_label", Ko, (Ko,)), ("counts", 6, (6,)), ("status", 2, (2,))):
+        part[name] = out[at:at + n].view(shape)
+        at += n
+    obj = lambda name: part[name].data_ptr() if Ko else None
+    check(_lib.load().eod_map_rooms(
+        labels.data_ptr(), passable.data_ptr() if P else None, d2.data_ptr(), _ptr(known), objects.data_ptr() if Ko else None, N, P,
+        int(cols), Ko, int(door_r2), int(min_cells), K, int(sweeps), cells[0].data_ptr(), cells[1].data_ptr(), part["count"].data_ptr(),
+        part["room"].data_ptr(), part["area"].data_ptr(), part["core_area"].data_ptr(), part["bbox"].data_ptr(), sum_rc.data_ptr(),
+        widest_key.data_ptr(), part["widest_d2"].data_ptr(), part["widest_cell"].data_ptr(), part["room_objects"].data_ptr(),
+        part["door_edges"].data_ptr(), door_key.data_ptr(), part["door_d2"].data_ptr(), part["door_cell"].data_ptr(),
+        obj("obj_room_cells"), obj("obj_room"), obj("obj_room_label"), part["counts"].data_ptr(), part["status"].data_ptr(),
+        workspace.data_ptr(), workspace.numel() * 4, _stream()), "eod_map_rooms")
+    return {"room_labels": cells[0], "grow_dist": cells[1], "count": part["count"], "room": part["room"], "area": part["area"],
+            "core_area": part["core_area"], "bbox": part["bbox"], "sum_rc": sum_rc, "widest_key": widest_key,
+            "widest_d2": part["widest_d2"], "widest_cell": part["widest_cell"], "room_objects": part["room_objects"],
+            "door_edges": part["door_edges"], "door_key": door_key, "door_d2": part["door_d2"], "door_cell": part["door_cell"],
+            "obj_room_cells": part["obj_room_cells"], "obj_room": part["obj_room"], "obj_room_label": part["obj_room_label"],
+            "counts": part["counts"], "status": part["status"]}
